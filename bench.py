@@ -29,7 +29,20 @@ timed steps (fsk_counts_digest). profiles/k_digests.json holds the single-GPU di
 a multi-GPU line compares its own — on every rank, after the reduce — with them: `bit_identical_to_1gpu`
 (BASELINE.md's "result identical at 1/2/4/8 GPUs" gate), and the run exits non-zero when that is false.
 
-One JSON line on rank 0. Extra objects:
+A plain run sets up, warms up, times the steps and prints one JSON line with the headline figure (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the config). `--full` adds everything below: the digests and their
+checks, the measurement-mode step and the roofline, the preflight, `alt`, `comm`, `end_to_end`, the in-process leg,
+`also` and `cpu_baseline`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed (float64 .npy files, < 64 MB in all):
+  sample_rows, sample_cols  a fixed, seeded sample of cells (row >= col) of the triangle (of rank 0's own rows when the
+                            kernel matrix stays distributed);
+  counts_sample             the integer kernel K at those cells;
+  kernel_sample             the normalised kernel at those cells (when the step writes the whole triangle);
+  kernel_block              the normalised top-left block of up to 1024 x 1024.
+The inputs are the same from run to run, so two builds can be compared output for output.
+
+One JSON line on rank 0. Extra objects (--full):
   roofline      the dominant kernel. Config 5: k_dense_tile_dma is bound by the integer-VALU issue
                 rate (v_dot8_u32_u4), so `frac` = count-MACs/s over that peak; the SURVEY 8(d)
                 algorithmic bytes (16*U + sort + input per combo), the measured HBM traffic and the
@@ -345,6 +358,40 @@ def committed_digest(key):
         return None
 
 
+# ---- --dump-outputs: what the last timed step computed, as float64 .npy files (5 x 8 MB at most)
+DUMP_CELLS = 1 << 20
+DUMP_BLOCK = 1024
+
+
+def sample_cells(n_cells, seed=20201214):
+    """A fixed, seeded sample of the triangle's cells [0, n_cells) (all of them when there are few), sorted, with their
+    (row, col): cell = row * (row + 1) / 2 + col, col <= row."""
+    if n_cells <= DUMP_CELLS:
+        cells = np.arange(n_cells, dtype=np.int64)
+    else:
+        rng = np.random.Generator(np.random.PCG64(seed))
+        cells = np.sort(rng.choice(n_cells, size=DUMP_CELLS, replace=False, shuffle=False)).astype(np.int64)
+    rows = ((np.sqrt(8.0 * cells + 1.0) - 1.0) / 2.0).astype(np.int64)
+    rows -= (rows * (rows + 1) // 2 > cells).astype(np.int64)
+    rows += ((rows + 1) * (rows + 2) // 2 <= cells).astype(np.int64)
+    return cells, rows, cells - rows * (rows + 1) // 2
+
+
+def tri_head_square(head, nb):
+    """The symmetric nb x nb block from the first nb * (nb + 1) / 2 cells of a triangle."""
+    blk = np.zeros((nb, nb), dtype=np.float64)
+    il = np.tril_indices(nb)
+    blk[il] = head
+    blk.T[il] = head
+    return blk
+
+
+def dump_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def describe(mode, world, replicate):
     if world == 1:
         return "single GPU"
@@ -520,6 +567,11 @@ def parse_args():
     ap.add_argument("--no-watchdog", action="store_true", help="no stage bounds (debugging under a profiler)")
     ap.add_argument("--engine-lib", default=None, help=argparse.SUPPRESS)  # (tests: a build of the engine with fault hooks, tests/hooks)
     ap.add_argument("--step-bound", type=float, default=0.0, help="seconds one step may take before the watchdog gives up (default: from the 1-GPU step time)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline and traffic passes, k_digest checks, preflight, alt, comm, "
+                         "end_to_end, the in-process leg, configs 1-4 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; a seeded sample)")
     return ap.parse_args()
 
 
@@ -539,6 +591,13 @@ def workload_of(args):
         workload = "config5: synthetic DNA %d x %d bp, g=%d m=%d exact" % (N, L, g, m)
         data = "synthetic"
     return tokens, offsets, N, L, g, m, workload, data
+
+
+def dtype_of(dense):
+    """The result line's `dtype`: the number formats of the dataflow the engine took."""
+    if dense:
+        return "u4 count planes (v_dot8_u32_u4), u32 register sums, u64 triangle (plain stores on the first pass over reset rows, else atomics)"
+    return "u32/u64 packed k-mer keys, u32 LDS sums, u64 triangle (read-modify-write by the owner band, atomics beyond)"
 
 
 def roofline_of(args, s0, s1, dense, world, combos_rank, share_rows, offsets, n_mine, prof=None):
@@ -603,7 +662,7 @@ def roofline_of(args, s0, s1, dense, world, combos_rank, share_rows, offsets, n_
                     "(16*U + sort + input per combo), which this kernel does NOT move through HBM — not a fraction of anything",
         }
         phases = {"count": d("ms_count") / args.steps, "tile": d("ms_tile") / args.steps, "accumulate_total": d("ms_total") / args.steps}
-        dtype = "u4 count planes (v_dot8_u32_u4), u32 register sums, u64 triangle (plain stores on the first pass over reset rows, else atomics)"
+        dtype = dtype_of(True)
     else:
         # ---- sparse pipeline: SURVEY 8(d) algorithmic bytes over the GPU time of the pipeline
         U = d("cell_updates") / max(1, args.steps)   # (the sparse dataflow counts its `+=` in every mode)
@@ -644,16 +703,16 @@ def roofline_of(args, s0, s1, dense, world, combos_rank, share_rows, offsets, n_
         }
         phases = {k: v / args.steps for k, v in fam.items()}
         phases["accumulate_total"] = d("ms_total") / args.steps
-        dtype = "u32/u64 packed k-mer keys, u32 LDS sums, u64 triangle (read-modify-write by the owner band, atomics beyond)"
+        dtype = dtype_of(False)
     return roofline, phases, dtype
 
 
 def finish(out, args, N, L, g, m, _native):
     """rank 0 / the single process: extras that do not depend on the job's ranks, then the ONE JSON line."""
     world = out["n_gpus"]
-    if world == 1 and not args.no_also:
+    if world == 1 and args.full and not args.no_also:
         out["also"] = other_configs(_native)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         full_n, full_L = (N, L) if args.config == 5 else (100000, 300)
         bg, bm = (g, m) if args.config == 5 else (12, 8)
         out["cpu_baseline"] = cpu_baseline(bg, bm, full_L, full_n, args.cpu_seconds)
@@ -719,47 +778,56 @@ def main_inproc(args):
         eng.synchronize()
         elapsed = time.perf_counter() - t0
         s1 = eng.stats()
-        stage("one step in measurement mode (exact U)", step_bound + 60.0)
-        eng.set_tuning("profile", 1)
-        p0 = eng.stats()
-        step()
-        eng.synchronize()
-        p1 = eng.stats()
-        eng.set_tuning("profile", 2)
+        if args.dump_outputs:
+            stage("dump outputs", step_bound + 60.0)
+            cells, rows, cols = sample_cells(N * (N + 1) // 2)
+            nb = min(N, DUMP_BLOCK)
+            dump_outputs(args.dump_outputs, {"sample_rows": rows, "sample_cols": cols, "counts_sample": eng.get_counts_cells(rows, cols),
+                                             "kernel_block": eng.get_block(0, nb, 0, nb)})
+        if args.full:
+            stage("one step in measurement mode (exact U)", step_bound + 60.0)
+            eng.set_tuning("profile", 1)
+            p0 = eng.stats()
+            step()
+            eng.synchronize()
+            p1 = eng.stats()
+            eng.set_tuning("profile", 2)
         stage("digest + line", step_bound)
     except _native.FskError as exc:
         fatal(wd, 0, args.gpus, args, "the in-process group failed: %s" % exc, wd.name if wd else "step",
               {"memory_plan_GB": {k: round(v / 1e9, 2) for k, v in plan.items()}})
     info = eng.multi_info()
-    digest = eng.counts_digest()
-    key = digest_key(args.config, N, L, g, m, ncomb)
-    want = committed_digest(key)
-    # engine 0's share: its stats carry the HIP-event times
-    n0 = info["combos_per_engine"][0]
-    e0, s0e, q0, q1 = dict(s1), dict(s0), dict(p0), dict(p1)
-    # (cell_updates / dense_macs in a group's stats are sums over the engines: bring them back to engine 0's share)
-    for k in ("cell_updates", "dense_macs"):
-        for dct, src in ((e0, s1), (s0e, s0), (q0, p0), (q1, p1)):
-            dct[k] = src[k] * n0 / max(1, ncomb)
-    roofline, phases, dtype = roofline_of(args, s0e, e0, dense, args.gpus, n0 * args.steps, 1.0, offsets, n0, prof=(q0, q1))
     out = {
         "metric": "gkm kernel build: mismatch-combos/s", "value": ncomb * args.steps / elapsed, "unit": "combos/s",
         "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": dtype, "data": data,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": dtype_of(dense), "data": data,
         "config": {"workload": workload, "n_seq": N, "seq_len": L, "g": g, "m": m, "combos": int(ncomb),
                    "parallelism": "in-process x%d: one engine per GPU behind one handle (fsk_create_multi / FastSK(devices=...)), combos c = "
                                   "engine (mod %d), one logical all-reduce issued in %d row bands on exchange streams under the next band's kernels"
                                   % (args.gpus, args.gpus, info["bands"]),
                    "path": "dense" if dense else "sparse"},
-        "roofline": roofline, "load_seconds_untimed": t_load, "phases_ms_per_step": phases,
+        "load_seconds_untimed": t_load,
         "comm": {"backend": "%s called from the host C++ (no torch in this process)" % ("RCCL" if info["collective"] == "rccl" else "engine P2P kernels"),
                  "rccl_ranks": info["comm_ranks"] if info["collective"] == "rccl" else 0, "ranks": info["comm_ranks"],
                  "allreduce_payload_bytes": info["reduce_bytes"], "allreduce_dtype": "int32" if info["narrow"] else "uint64",
                  "bands": info["bands"], "combos_per_engine": info["combos_per_engine"],
                  "latency_bound": not dense},
-        "k_digest": dict(digest_hex(digest), key=key, committed=want),
-        "bit_identical_to_1gpu": None if want is None else (digest_hex(digest) == {"sum": want["sum"], "xor": want["xor"]}),
     }
+    if args.full:
+        digest = eng.counts_digest()
+        key = digest_key(args.config, N, L, g, m, ncomb)
+        want = committed_digest(key)
+        # engine 0's share: its stats carry the HIP-event times
+        n0 = info["combos_per_engine"][0]
+        e0, s0e, q0, q1 = dict(s1), dict(s0), dict(p0), dict(p1)
+        # (cell_updates / dense_macs in a group's stats are sums over the engines: bring them back to engine 0's share)
+        for k in ("cell_updates", "dense_macs"):
+            for dct, src in ((e0, s1), (s0e, s0), (q0, p0), (q1, p1)):
+                dct[k] = src[k] * n0 / max(1, ncomb)
+        out["roofline"], out["phases_ms_per_step"], _ = roofline_of(args, s0e, e0, dense, args.gpus, n0 * args.steps, 1.0, offsets, n0,
+                                                                    prof=(q0, q1))
+        out["k_digest"] = dict(digest_hex(digest), key=key, committed=want)
+        out["bit_identical_to_1gpu"] = None if want is None else (digest_hex(digest) == {"sum": want["sum"], "xor": want["xor"]})
     eng.close()
     if wd:
         wd.finish()
@@ -859,7 +927,7 @@ def main():
     # ---- preflight: the same multi-GPU code on a job that takes a fraction of a second and whose single-GPU digest
     # is committed (config 5 at N = 16000): a broken interconnect or a wrong reduce is reported in seconds
     preflight = None
-    if use_dist and world > 1 and args.config == 5 and not args.no_preflight and N >= 16000:
+    if args.full and use_dist and world > 1 and args.config == 5 and not args.no_preflight and N >= 16000:
         stage("preflight (N = 16000, one step, digest committed)", max(90.0, step_bound))
         pN = 16000
         ptok, poff, _ = synthetic(pN, args.seq_len)
@@ -919,6 +987,7 @@ def main():
         mode = "combos"  # rows needs the dense dataflow and one 128-row band per rank
     my_rows = (edges[rank], edges[rank + 1]) if mode == "rows" else (0, N)
     mine = every if mode == "rows" else np.arange(rank, ncomb, world, dtype=np.int32)
+    last = {}  # the normalised block of the last step (when the whole triangle does not fit)
 
     def barrier():
         torch.cuda.synchronize()
@@ -947,7 +1016,7 @@ def main():
         if whole:
             eng.get_triangle_torch(tri)   # fsk_get_triangle_device: returns when the triangle is written
         else:
-            eng.get_block_torch(0, nblk, 0, nblk)
+            last["block"] = eng.get_block_torch(0, nblk, 0, nblk)
 
     def gather_digest(how):
         """The digest of the job's triangle after a step of decomposition `how`, and whether every rank agrees:
@@ -996,7 +1065,7 @@ def main():
             tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        return dt, a, b, gather_digest(how)
+        return dt, a, b, gather_digest(how) if args.full else (None, None)
 
     key = digest_key(args.config, N, L, g, m, ncomb)
     want = committed_digest(key)
@@ -1012,18 +1081,34 @@ def main():
         return obj, digest_hex(dg) == {"sum": want["sum"], "xor": want["xor"]}
 
     elapsed, s0, s1, (dg, agree) = timed(mode, args.warmup, args.steps)
-    k_digest, identical = verdict(dg, agree)
-    # ---- one more step in measurement mode (profile = 1, outside the timed region): the exact update count U and the
-    # count-MACs including the flagged rows' remainder products — what the product dataflow does not compute
-    stage("one step in measurement mode (exact U)", step_bound + 60.0)
-    eng.set_tuning("profile", 1)
-    p0 = eng.stats()
-    step(mode)
-    torch.cuda.synchronize()
-    p1 = eng.stats()
-    eng.set_tuning("profile", 2)
-    alt = None
-    if world > 1 and not args.no_alt and edges is not None:
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: K (the integer triangle) and the normalised result; a rank of the distributed
+        # row-band form holds only its own rows of K, and its kernel blocks are normalised where they are served
+        stage("dump outputs", step_bound + 60.0)
+        owned = use_dist and mode == "rows" and not args.replicate
+        cells, rows, cols = sample_cells(distributed.cell(edges[1]) if owned else pairs)
+        arrays = {"sample_rows": rows, "sample_cols": cols, "counts_sample": eng.get_counts_cells(rows, cols)}
+        if not owned:
+            nb = min(N, DUMP_BLOCK)
+            if whole:
+                arrays["kernel_sample"] = tri[torch.from_numpy(cells).to(tri.device)].cpu().numpy()
+                arrays["kernel_block"] = tri_head_square(tri[:nb * (nb + 1) // 2].cpu().numpy(), nb)
+            else:
+                arrays["kernel_block"] = last["block"][:nb, :nb].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
+    k_digest, identical, alt, comm, end_to_end = None, None, None, None, None
+    if args.full:
+        k_digest, identical = verdict(dg, agree)
+        # ---- one more step in measurement mode (profile = 1, outside the timed region): the exact update count U and the
+        # count-MACs including the flagged rows' remainder products — what the product dataflow does not compute
+        stage("one step in measurement mode (exact U)", step_bound + 60.0)
+        eng.set_tuning("profile", 1)
+        p0 = eng.stats()
+        step(mode)
+        torch.cuda.synchronize()
+        p1 = eng.stats()
+        eng.set_tuning("profile", 2)
+    if args.full and world > 1 and not args.no_alt and edges is not None:
         other = "combos" if mode == "rows" else "rows"
         dt, _, _, (adg, aagree) = timed(other, args.warmup, args.steps)
         akd, aid = verdict(adg, aagree)
@@ -1035,9 +1120,8 @@ def main():
 
     # ---- the exchange by itself: the same band-wise all-reduce, nothing overlapping it (untimed extras;
     # K is garbage afterwards and is reset by whatever runs next)
-    comm = None
     stage("the exchange by itself", step_bound)
-    if use_dist:
+    if args.full and use_dist:
         narrow = ncomb * eng.stats()["max_windows"] ** 2 < 2 ** 31
         tiles = ((N + 127) // 128) * ((N + 127) // 128 + 1) // 2
         nb = args.bands or ((16 if tiles >= 16 * 16384 else 8) if (dense and N >= 8192) else 1)
@@ -1066,9 +1150,8 @@ def main():
     # ---- SURVEY 8(d)'s metric boundary, literally: H2D of the packed sequences + every combo + normalise, the
     # whole triangle (fastsk_kernel.cpp:96-103 over all N(N+1)/2 cells, device resident) when a second
     # triangle of doubles fits beside the integer one, else a 4096 x 4096 block (single GPU only)
-    end_to_end = None
     stage("end_to_end", 4 * step_bound)
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         eng.load_sequences(tokens, offsets, N, 0)
@@ -1107,13 +1190,11 @@ def main():
 
     out = None
     if rank == 0:
-        share_rows = ((my_rows[1] * (my_rows[1] + 1) - my_rows[0] * (my_rows[0] + 1)) // 2) / pairs
-        roofline, phases, dtype = roofline_of(args, s0, s1, dense, world, len(mine) * args.steps, share_rows, offsets, len(mine), prof=(p0, p1))
         out = {
             "metric": "gkm kernel build: mismatch-combos/s", "value": ncomb * args.steps / elapsed, "unit": "combos/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": dtype, "data": data,
+            "vs_baseline": None, "dtype": dtype_of(dense), "data": data,
             "config": {"workload": workload, "n_seq": N, "seq_len": L, "g": g, "m": m, "combos": int(ncomb),
                        "parallelism": describe(mode, world, args.replicate),
                        "path": "dense" if dense else "sparse"},
@@ -1122,12 +1203,14 @@ def main():
                               "the engine runs its product dataflow (fsk_config.profile = 2: HIP events recorded, never waited for)"
                               % (" + the all-reduce of the partial triangles" if use_dist else "",
                                  "the WHOLE triangle, %d float64 cells" % pairs if whole else "a %d x %d block: no room for a second triangle" % (nblk, nblk)),
-            "roofline": roofline,
             "load_seconds_untimed": t_load,
-            "phases_ms_per_step": phases,
-            "k_digest": k_digest,
-            "bit_identical_to_1gpu": identical,
         }
+        if args.full:
+            share_rows = ((my_rows[1] * (my_rows[1] + 1) - my_rows[0] * (my_rows[0] + 1)) // 2) / pairs
+            out["roofline"], out["phases_ms_per_step"], _ = roofline_of(args, s0, s1, dense, world, len(mine) * args.steps, share_rows,
+                                                                        offsets, len(mine), prof=(p0, p1))
+            out["k_digest"] = k_digest
+            out["bit_identical_to_1gpu"] = identical
         if alt is not None:
             out["alt"] = alt
         if comm is not None:
@@ -1149,11 +1232,12 @@ def main():
         dist.barrier()
     eng.close()
     del K, tri
+    last.clear()
     torch.cuda.empty_cache()
     # ---- the same job from ONE process (FastSK(devices=[...])'s engine), measured once the ranks have let go of
     # their GPUs: rank 0 starts a fresh child (it has touched the GPU itself: a child process, never an exec)
     # and the others wait on the rendezvous store, not on a collective that would spin on their GPUs.
-    if world > 1 and backend == "nccl" and not args.no_inproc_leg:
+    if args.full and world > 1 and backend == "nccl" and not args.no_inproc_leg:
         import datetime
         stage("in-process leg (child of rank 0)", args.inproc_timeout + 180.0)
         if wd and out is not None:
@@ -1166,7 +1250,7 @@ def main():
             try:
                 cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--inproc", "--steps", str(args.steps), "--warmup",
                        str(args.warmup), "--config", str(args.config), "--n-seq", str(args.n_seq), "--seq-len", str(args.seq_len),
-                       "--no-also", "--no-cpu-baseline"] + (["--bands", str(args.bands)] if args.bands else [])
+                       "--full", "--no-also", "--no-cpu-baseline"] + (["--bands", str(args.bands)] if args.bands else [])
                 env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                                          "GROUP_RANK", "ROLE_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.inproc_timeout, env=env)

@@ -59,6 +59,16 @@ def load_tokens(data):
             int(z["n_test"]), z["y_train"], z["y_test"])
 
 
+def reference_fasta(name, tmp_path):
+    """The reference's data/<name>.fasta, stored gzipped in tests/golden/fasta, unpacked into tmp_path; returns the path."""
+    import gzip
+    import shutil
+    path = os.path.join(str(tmp_path), name + ".fasta")
+    with gzip.open(os.path.join(GOLD, "fasta", name + ".fasta.gz"), "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    return path
+
+
 def tri_to_square(tri, N):
     full = np.zeros((N, N), dtype=tri.dtype)
     il = np.tril_indices(N)

@@ -999,7 +999,7 @@ def test_bench_two_ranks_sharing_the_gpu(native, shard):
     env = dict(os.environ, FSK_BENCH_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--n-seq", "8000", "--shard", shard], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])   # the JSON line is the last thing printed
@@ -1039,7 +1039,7 @@ def test_bench_fails_fast_with_a_json_line_when_a_rank_hangs(native):
     import sys
     import time
     from conftest import ROOT
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-seq", "16000",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-seq", "16000",
             "--no-alt", "--no-inproc-leg"]
     r = subprocess.run(base, env=_bench_env(FSK_BENCH_SHARE_GPU="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -1088,7 +1088,7 @@ def test_bench_rccl_leg_on_one_rank(native):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     for extra, path in ((["--n-seq", "8000"], "dense"), (["--config", "4"], "sparse")):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "1", "--warmup", "1",
                             "--no-cpu-baseline", "--no-also"] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1113,7 +1113,7 @@ def test_bench_inproc(native, gpus, share):
     if share:
         env["FSK_BENCH_SHARE_GPU"] = "1"
     for extra, path in ((["--n-seq", "8000"], "dense"), (["--config", "4"], "sparse")):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--inproc", "--steps", "2", "--warmup", "1",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--inproc", "--steps", "2", "--warmup", "1",
                             "--no-cpu-baseline", "--no-also"] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1122,6 +1122,41 @@ def test_bench_inproc(native, gpus, share):
         assert d["comm"]["ranks"] == gpus and d["comm"]["rccl_ranks"] == (0 if share else 1)
         assert d["comm"]["allreduce_dtype"] == "int32" and sum(d["comm"]["combos_per_engine"]) == d["config"]["combos"]
         assert set(d["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
+
+
+@pytest.mark.parametrize("inproc", [False, True])
+def test_bench_plain_run_dumps_what_its_last_step_computed(native, tmp_path, inproc):
+    """A plain `bench.py --gpus 1` run (torch ranks, or --inproc: the fsk_create_multi group) reports the headline figure and
+    nothing behind --full, and `--dump-outputs` writes what its last timed step computed — the counts (and, where the step
+    writes the whole normalised triangle, the kernel) at a seeded sample of cells, and the top-left block of the kernel —
+    equal to one fsk_compute of the same workload."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    N, L = 4000, 300
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--n-seq", str(N),
+                        "--seq-len", str(L), "--dump-outputs", str(out_dir)] + (["--inproc"] if inproc else []),
+                       env=_bench_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "combos/s" and d["dtype"] and d["config"]["n_seq"] == N and d["config"]["combos"] == 495
+    assert not set(d) & {"roofline", "phases_ms_per_step", "k_digest", "end_to_end", "also", "cpu_baseline"}
+    got = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert set(got) == {"sample_rows", "sample_cols", "counts_sample", "kernel_block"} | (set() if inproc else {"kernel_sample"})
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    rows, cols = got["sample_rows"].astype(np.int64), got["sample_cols"].astype(np.int64)
+    assert len(rows) > 1000 and (cols <= rows).all() and rows.max() < N
+    tokens, offsets = synthetic_dna(N, L)
+    e = native.Engine(12, 8)
+    e.compute(tokens, offsets, N, 0)
+    assert np.array_equal(got["counts_sample"], e.get_counts_cells(rows, cols).astype(np.float64))
+    if not inproc:
+        assert np.array_equal(got["kernel_sample"], e.get_triangle()[rows * (rows + 1) // 2 + cols])
+    assert np.array_equal(got["kernel_block"], e.get_block(0, 1024, 0, 1024))
+    e.close()
 
 
 @pytest.mark.parametrize("surface", ["ctypes", "pybind"])

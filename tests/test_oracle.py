@@ -3,12 +3,13 @@ reference, against the compiled reference itself when present, and against an in
 brute-force statement of the kernel definition. CPU only."""
 import hashlib
 import itertools
+import os
 from collections import Counter
 
 import numpy as np
 import pytest
 
-from conftest import golden_names, load_golden, tri_to_square, load_tokens
+from conftest import golden_names, load_golden, tri_to_square, load_tokens, GOLD
 
 
 def sha(a):
@@ -130,35 +131,51 @@ def test_sub_block_property(port):
     assert np.array_equal(tri_to_square(cb, 90)[np.ix_(sub, sub)], tri_to_square(cs, 25))
 
 
-def test_port_matches_compiled_reference_fresh_inputs(port, ref):
-    """Beyond the stored vectors: random ragged inputs, straight against the compiled reference."""
-    rng = np.random.default_rng(11)
-    for sigma, g, m, n in [(4, 8, 4, 30), (20, 7, 3, 25), (3, 6, 5, 12)]:
-        X = [rng.integers(1, sigma + 1, size=int(L)).astype(np.int32) for L in rng.integers(g, 60, size=n)]
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([len(x) for x in X])
-        tokens = np.concatenate(X)
-        ntr = n - 7
-        tri_r, sd_r = ref.full_triangle(tokens, offsets, ntr, 7, g, m, t=3)
-        tri_p, sd_p, _ = port.compute(tokens, offsets, ntr, 7, g, m, t=3)
-        assert np.array_equal(tri_r, tri_p)
-        nc = port.num_combos(g, m)
-        order = ref.shuffle_order(42, nc)
-        tri_r, sd_r = ref.full_triangle(tokens, offsets, ntr, 7, g, m, t=1, approx=True, seed=42)
-        tri_p, sd_p, _ = port.compute(tokens, offsets, ntr, 7, g, m, t=1, approx=True, order=order)
-        assert np.array_equal(tri_r, tri_p) and np.array_equal(sd_r, sd_p)
+def compiled_ref():
+    """The compiled reference where oracle/_ref was built, else None (its outputs for the checks below are stored in
+    tests/golden/ref_checks.npz by make_golden_ref_checks.py)."""
+    from oracle import loader
+    return loader.ref() if loader.have_ref() else None
 
 
-def test_port_matches_compiled_reference_edge_cases(port, ref):
+def ref_checks():
+    return np.load(os.path.join(GOLD, "ref_checks.npz"))
+
+
+def test_port_matches_compiled_reference_fresh_inputs(port):
+    """Beyond the stored vectors: random ragged inputs, against the compiled reference's outputs (stored, and live where
+    oracle/_ref was built)."""
+    from make_golden_ref_checks import fresh_cases
+    want, ref = ref_checks(), compiled_ref()
+    for i, (tokens, offsets, ntr, nte, g, m) in enumerate(fresh_cases()):
+        tri_p, sd_p, _ = port.compute(tokens, offsets, ntr, nte, g, m, t=3)
+        assert np.array_equal(want["fresh%d_exact" % i], tri_p)
+        if ref is not None:
+            tri_r, sd_r = ref.full_triangle(tokens, offsets, ntr, nte, g, m, t=3)
+            assert np.array_equal(tri_r, tri_p)
+        order = want["fresh%d_order" % i]
+        assert len(order) == port.num_combos(g, m)
+        tri_p, sd_p, _ = port.compute(tokens, offsets, ntr, nte, g, m, t=1, approx=True, order=order)
+        assert np.array_equal(want["fresh%d_approx_tri" % i], tri_p) and np.array_equal(want["fresh%d_approx_sd" % i], sd_p)
+        if ref is not None:
+            assert np.array_equal(ref.shuffle_order(42, len(order)), order)
+            tri_r, sd_r = ref.full_triangle(tokens, offsets, ntr, nte, g, m, t=1, approx=True, seed=42)
+            assert np.array_equal(tri_r, tri_p) and np.array_equal(sd_r, sd_p)
+
+
+def test_port_matches_compiled_reference_edge_cases(port):
     """The degenerate shapes the engine tests use (conftest.EDGE_CASES): one sequence, lengths == g,
     identical sequences, k = 1, nothing shared, m = 0."""
     from conftest import EDGE_CASES
     from fastsk_amd import _native
-    for X, ntr, nte, g, m in EDGE_CASES:
+    want, ref = ref_checks(), compiled_ref()
+    for i, (X, ntr, nte, g, m) in enumerate(EDGE_CASES):
         tokens, offsets = _native.flatten(X)
-        tri_r, _ = ref.full_triangle(tokens, offsets, ntr, nte, g, m, t=1)
         tri_p, _, _ = port.compute(tokens, offsets, ntr, nte, g, m, t=1)
-        assert np.array_equal(tri_r, tri_p), (X, g, m)
+        assert np.array_equal(want["edge%d" % i], tri_p), (X, g, m)
+        if ref is not None:
+            tri_r, _ = ref.full_triangle(tokens, offsets, ntr, nte, g, m, t=1)
+            assert np.array_equal(tri_r, tri_p), (X, g, m)
 
 
 def test_fasta_reader_matches_reference_tokens(tmp_path):
@@ -178,8 +195,9 @@ def test_fasta_reader_matches_reference_tokens(tmp_path):
 
 def test_fast_fasta_reader_equals_slow_reader(tmp_path):
     """FastaUtility.read_packed (vectorised) == read_data (the reference's tokenisation), incl.
-    the shared vocabulary across train and test files."""
-    import os
+    the shared vocabulary across train and test files — on random files and on the 1.1 data set of the reference's
+    data/ folder (stored gzipped in tests/golden/fasta)."""
+    from conftest import reference_fasta
     from fastsk_amd.utils import FastaUtility
     rng = np.random.default_rng(0)
     alpha = "ACGTNacgtn"
@@ -193,8 +211,7 @@ def test_fast_fasta_reader_equals_slow_reader(tmp_path):
     files = [str(tmp_path / "a.train.fasta"), str(tmp_path / "a.test.fasta")]
     write(files[0], 30)
     write(files[1], 11)
-    if os.path.isdir("/root/reference/data"):
-        files += ["/root/reference/data/1.1.train.fasta", "/root/reference/data/1.1.test.fasta"]
+    files += [reference_fasta("1.1.train", tmp_path), reference_fasta("1.1.test", tmp_path)]
     slow, fast = FastaUtility(), FastaUtility()
     for fpath in files:
         X, Y = slow.read_data(fpath)
@@ -205,18 +222,23 @@ def test_fast_fasta_reader_equals_slow_reader(tmp_path):
     assert str(slow._vocab) == str(fast._vocab)
 
 
-def test_seed_order_is_the_references_shuffle(ref):
+def test_seed_order_is_the_references_shuffle():
     """fsk_set_seed(S) stands for the order the reference draws when time(0) == S: libstdc++'s std::shuffle over
     std::default_random_engine (fastsk_kernel.cpp:31-38), restated in the engine (fsk_seed_order) — against the compiled
     reference's own std::shuffle for lengths on both sides of its two-swaps-a-draw limit (n * n <= 2^31 - 3) and seeds
     incl. the ones minstd_rand0 folds (0 and 2^31 - 1 both seed as 1)."""
     from fastsk_amd import _native
+    from make_golden_ref_checks import SHUFFLE_N, SHUFFLE_SEEDS
     lib = _native.library()
-    for n in (0, 1, 2, 3, 4, 210, 495, 1001, 38760, 46340, 46341, 50000, 184756):
-        for seed in (0, 1, 42, 777, 2 ** 31 - 2, 2 ** 31 - 1, 2 ** 31, 1759622400, 2 ** 40 + 12345):
-            want = ref.shuffle_order(seed, n) if n else np.zeros(0, dtype=np.int32)
+    stored, ref = ref_checks(), compiled_ref()
+    for seed in SHUFFLE_SEEDS:
+        assert len(lib.seed_order(seed, 0)) == 0
+    for n in SHUFFLE_N:
+        for seed in SHUFFLE_SEEDS:
             got = lib.seed_order(seed, n)
-            assert np.array_equal(got, want), (n, seed)
+            assert got.dtype == np.int32 and sha(got) == str(stored["shuffle__%d__%d" % (n, seed)]), (n, seed)
+            if ref is not None:
+                assert np.array_equal(got, ref.shuffle_order(seed, n)), (n, seed)
 
 
 def test_seed_order_reproduces_every_golden_order():

@@ -1,15 +1,14 @@
 """The native FASTA reader (fsk_read_fasta behind fastsk.utils.FastaUtility) against the
 reference's reader: token arrays captured from the reference for the four FASTA configs of
-BASELINE.json (tests/golden/tokens_*.npz; needs the data files, build container only) and for
-small messy files of our own (tests/golden/fasta/, travels everywhere). SURVEY 8f-2."""
+BASELINE.json (tests/golden/tokens_*.npz, from the reference's data files stored gzipped in tests/golden/fasta/)
+and for small messy files of our own (tests/golden/fasta/). SURVEY 8f-2."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLD
+from conftest import GOLD, reference_fasta
 
-REF_DATA = "/root/reference/data"
 FASTA = os.path.join(GOLD, "fasta")
 
 
@@ -19,10 +18,8 @@ def flat(X):
 
 @pytest.mark.parametrize("name", ["EP300", "EP300_47848", "1.1", "2.19", "small"])
 @pytest.mark.parametrize("api", ["read_data", "read_packed"])
-def test_reference_datasets(name, api):
-    tr, te = (os.path.join(REF_DATA, "%s.%s.fasta" % (name, part)) for part in ("train", "test"))
-    if not (os.path.exists(tr) and os.path.exists(te)):
-        pytest.skip("reference data files not present on this box")
+def test_reference_datasets(name, api, tmp_path):
+    tr, te = (reference_fasta("%s.%s" % (name, part), tmp_path) for part in ("train", "test"))
     from fastsk.utils import FastaUtility  # the reference's import path
     z = np.load(os.path.join(GOLD, "tokens_%s.npz" % name))
     rd = FastaUtility()
