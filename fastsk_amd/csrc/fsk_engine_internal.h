@@ -111,7 +111,6 @@ using fsk_detail::DevBuf;
     X(blocks_sub_shift, 14, 4, 14, "sparse, blocks: log2 of the cells one k_sxb_consume workgroup sums in LDS (tests: small blocks on small inputs)") \
     X(blocks_max_bands, 512, 2, 512, "sparse, blocks: bands of one pass at most (tests: several passes on small inputs)")            \
     X(blocks_band_shift_max, 23, 4, 23, "sparse, blocks: log2 of a band's cells at most (tests)")                                    \
-    X(blocks_scatter_threads, 0, 0, 1024, "sparse, blocks: threads of a k_sxb_scatter workgroup, 256 / 512 / 1024 (0: 256)")          \
     X(blocks_pass_words, 0, 0, (int64_t)1 << 32, "sparse, blocks: update words of one pass at most (0: 2^31)")                       \
     X(sparse_desc, 0, -1, 1, "sparse, owner bands and two-level blocks: entries of many partners leave k_sx_emit as descriptors (one an entry; blocks: one per sub-band its partners fall into) that k_sx_consume / k_sxb_consume expand in LDS — 1 = always, -1 = never (0: once a batch of these sequences has shown sparse_desc_from pairs per record)") \
     X(sparse_desc_blocks, 1, 0, 1, "sparse, two-level blocks: 0 = never descriptors there (1: as sparse_desc says — one record per sub-band an entry's partners fall into)") \
@@ -259,7 +258,7 @@ struct fsk_engine {
     bool sx_lists = false, owner_ready = false;
     int n_cu = 256;   // compute units of the device (persistent launches)
     int sx_form = 0;  // the update stage of the sparse dataflow for these sequences: 0 = owner bands, 1 = 64-bit atomics, 2 = two-level blocks
-    int sx_form_used = -1;  // ... what the last batch really took (tuning key sparse_form_used reads it)
+    int sx_form_used = -1;  // ... what the last batch really took (fsk_stats.sparse_form)
     u64 sx_passes = 0;      // blocks form: passes run since the sequences were loaded
     int sx_share_used = 0;  // shared prefixes: leading positions / groups of the last batch (fsk_stats)
     uint32_t sx_share_groups = 0;

@@ -5,6 +5,8 @@
 #include "fsk_engine_internal.h"
 #include "fsk_kernels_sparse.h"
 
+#include <type_traits>
+
 using namespace fsk_detail;
 
 namespace fsk_detail {
@@ -123,8 +125,15 @@ void sx_choose_form(fsk_engine* e) {
                                                                         : 1;
 }
 
-// descriptors for this batch? (owner bands only; see fsk_engine::sx_desc_now)
-inline bool sx_desc_wanted(const fsk_engine* e) { return e->sx_desc_now(); }
+// Runtime flags as template arguments: f(std::bool_constant<flag>{}...), the flags in the order given. Every combination
+// is instantiated: what a launch never takes, its lambda maps onto an instance it does take.
+template <typename F>
+void sx_with_flags(F&& f) { f(); }
+template <typename F, typename... Flags>
+void sx_with_flags(F&& f, bool flag, Flags... rest) {
+    if (flag) sx_with_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else sx_with_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
 
 // The LSD passes over `bits` bits from bit `shift0` of the records of n_slots slots (the digits of the first pass have been
 // counted by whoever wrote the records). *cur: which of rec[0] / rec[1] holds the result.
@@ -141,11 +150,11 @@ int sx_sort(fsk_engine* e, SxScratch& S, hipStream_t stream, T* const rec[2], ui
             FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_sx_hist<T>), dim3(tps, n_slots), dim3(256), 0, stream, (const T*)rec[cur], nfeat, tps, shift,
                        (1u << nbits) - 1u, S.d_blockhist.p);
         FSK_LAUNCH(fsk::k_sx_scan_slot, dim3(n_slots), dim3(1024), 0, stream, S.d_blockhist.p, tps, S.d_totals.p);
-        {   // (function pointers: a template-id with a comma cannot pass through the launch macro)
-            auto k_scatter = nbits <= 4 ? fsk::k_sx_scatter<T, 4> : nbits == 5 ? fsk::k_sx_scatter<T, 5>
-                             : nbits == 6 ? fsk::k_sx_scatter<T, 6> : nbits == 7 ? fsk::k_sx_scatter<T, 7>
-                                                                                 : fsk::k_sx_scatter<T, 8>;
-            FSK_LAUNCH(k_scatter, dim3(fsk::xcd_grid(tps * n_slots)), dim3(256), 0, stream, (const T*)rec[cur], rec[cur ^ 1], nfeat, tps, n_slots,
+        {   // (function pointers: a template-id with a comma cannot pass through the launch macro; 4 bits at least)
+            decltype(&fsk::k_sx_scatter<T, 8>) const k_scatter[] = {fsk::k_sx_scatter<T, 4>, fsk::k_sx_scatter<T, 5>, fsk::k_sx_scatter<T, 6>,
+                                                                    fsk::k_sx_scatter<T, 7>, fsk::k_sx_scatter<T, 8>};
+            const auto k = k_scatter[std::max(nbits, 4) - 4];
+            FSK_LAUNCH(k, dim3(fsk::xcd_grid(tps * n_slots)), dim3(256), 0, stream, (const T*)rec[cur], rec[cur ^ 1], nfeat, tps, n_slots,
                        shift, nbits, (const uint32_t*)S.d_blockhist.p, (const uint32_t*)S.d_totals.p);
         }
         cur ^= 1;
@@ -208,55 +217,89 @@ SxShare sx_plan_share(fsk_engine* e, const int32_t* combos, int nb, int recbits_
     return best;
 }
 
-// `pos_pin` / `stat_pin`: pinned staging of this batch (positions in, {pairs, words} out), untouched by
-// anyone else until the batch's counts have been read. `guard_cap` == 0: the call waits for the
-// counts and sizes the streams exactly; else it only enqueues, for streams of at most guard_cap words.
+// One batch of the sparse dataflow: the call's arguments, what every stage reads (computed once, by sx_batch_begin) and
+// what a stage leaves for the stages after it.
+struct SxBatch {
+    fsk_engine* e;
+    SxScratch* S;               // the lane's scratch set and stream
+    hipStream_t stream;
+    const int32_t* combos;
+    int nb;
+    u64* K;
+    int64_t row0, row1;
+    u64 slot_stride;            // != 0 (variance mode): combo q adds into its own u32 triangle, slot_stride cells apart
+    unsigned char* pos_pin;     // pinned staging of this batch (positions in, {pairs, words} out), untouched by anyone else
+    u64* stat_pin;              // until the batch's counts have been read
+    u64 guard_cap;              // 0: the batch waits for its counts and sizes its streams exactly; else streams of at most guard_cap words
+    size_t pos_off;             // where the batch's positions lie in e->d_pos (the batches of an exact accumulate in two lanes: a piece each)
+    hipEvent_t k_wait, k_done;  // the kernels that touch K wait for the first and are followed by the second (a band with one part adds
+                                // into K with a plain read-modify-write: the consume passes of the two lanes may not overlap)
+    uint32_t nfeat = 0, tps = 0, tpg = 0, ntiles = 0;  // windows a slot; sort tiles and segment tiles a slot; segment tiles in all
+    size_t nrec = 0;
+    SxShare sh;
+    int keybits = 0, form = 0, pairs = 0, col16 = 0;
+    bool slot16 = false, skipping = false, packed = false, by_id = false;
+    uint32_t O = 0, OC = 0, desc = 0, short_max = 0, skip_from = 0, uc = 0, nchunks = 0, maxprod = 0, cmax = 0;
+    fsk::SxIds ids{};
+    const uint8_t* pos_tab = nullptr;  // the kept positions of the batch's combos, on the device
+    const void* sorted = nullptr;      // the sort: the buffer that holds the sorted records
+    void* colp = nullptr;              // the segments: the entries' column array (descriptors; null: none)
+};
+
+// The batch's plan — every value the stages read — then its scratch, the owner bands' table and its positions.
 template <typename RecT>
-int sparse_batch(fsk_engine* e, const int32_t* combos, int nb, u64* K, int64_t row0, int64_t row1, u64 slot_stride,
-                 unsigned char* pos_pin, u64* stat_pin, u64 guard_cap, int lane, size_t pos_off = 0, hipEvent_t k_wait = nullptr,
-                 hipEvent_t k_done = nullptr) {
-    // pos_off: where this batch's positions lie in e->d_pos (the batches of one exact accumulate, in flight in two lanes, each
-    // have their own piece); k_wait / k_done: the kernels that touch K wait for the first and are followed by the second (a
-    // band with one part adds into K with a plain read-modify-write: the consume passes of the two lanes may not overlap)
-    SxScratch& S = e->sxs[lane];
-    hipStream_t stream = lane ? e->lane_stream : e->stream;
-    const uint32_t nfeat = (uint32_t)e->nfeat;
-    const size_t nrec = (size_t)nb * nfeat;
+int sx_batch_begin(SxBatch& c) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    const int nb = c.nb;
+    const uint32_t nfeat = c.nfeat = (uint32_t)e->nfeat;
+    const size_t nrec = c.nrec = (size_t)nb * nfeat;
     if (nrec == 0) return FSK_OK;
     // Only the k-mer bits are sorted: the records of a slot are generated in sequence order and every
     // LSD pass is stable, so equal k-mers end up contiguous with their sequence ids ascending.
-    const int sb = e->sx_sb;
     // (consecutive combos keep the same leading positions for long stretches: those are sorted once per group)
-    const SxShare sh = nb > 16 ? sx_plan_share(e, combos, nb, 8 * (int)sizeof(RecT)) : SxShare();
-    const int keybits = sh.share ? sh.lowbits : e->sx_keybits;  // what every slot sorts
+    const SxShare sh = c.sh = nb > 16 ? sx_plan_share(e, c.combos, nb, 8 * (int)sizeof(RecT)) : SxShare();
+    c.keybits = sh.share ? sh.lowbits : e->sx_keybits;  // (what every slot sorts)
     e->sx_share_used = sh.share;
     e->sx_share_groups = sh.groups;
     if (e->trace())
         fprintf(stderr, "[fsk] sparse batch: %d slots, shared leading positions %d (%u groups, %d + %d key bits; plain %d)\n", nb, sh.share, sh.groups,
                 sh.topbits, sh.lowbits, e->sx_keybits);
-    const int passes = (keybits + 7) / 8;
-    const uint32_t dmask = (1u << sx_first_pass_bits(keybits)) - 1u;  // (the extraction counts the first pass's digits)
-    const uint32_t tps = (nfeat + fsk::SX_TILE - 1) / fsk::SX_TILE;   // sort tiles per slot
-    const uint32_t tpg = (nfeat + fsk::SG_TILE - 1) / fsk::SG_TILE;   // segment tiles per slot
-    const uint32_t ntiles = tpg * (uint32_t)nb;
+    c.tps = (nfeat + fsk::SX_TILE - 1) / fsk::SX_TILE;
+    c.tpg = (nfeat + fsk::SG_TILE - 1) / fsk::SG_TILE;
+    const uint32_t ntiles = c.ntiles = c.tpg * (uint32_t)nb;
     // the form of the update stage (sx_choose_form); a batch of slot triangles (variance mode) knows the owner bands only
-    const int form = slot_stride != 0 ? ((e->sx_lists && e->sx_form != 1) ? 0 : 1) : e->sx_form;
-    const bool blocks = form == 2;
-    const bool lists = form == 0;
-    e->sx_form_used = form;
-    const int pairs = lists && e->sx_pairs ? 1 : 0;  // (unit products as bare cells, two to a word: plan_owner_bands)
-    const bool slot16 = slot_stride != 0 && e->sx_slot16_used;  // (u16 slot triangles: set by accumulate_sparse for a deferred batch)
-    const uint32_t O = blocks ? (uint32_t)e->tune.blocks_max_bands : e->n_owners;  // (blocks: the most bands a pass can have)
-    // descriptors (owner bands only): entries of more than short_max partners leave k_sx_emit as one descriptor each and
-    // k_sx_consume walks their partners; the count matrix and the stream offsets then have two columns a band
-    const uint32_t desc = !sx_desc_wanted(e) ? 0u : lists ? 1u : (blocks && e->tune.sparse_desc_blocks) ? 2u : 0u;  // (1: one descriptor an entry; 2: one per sub-band)
-    const uint32_t short_max = desc && e->tune.sparse_desc_min > 0 ? (uint32_t)std::min<int64_t>(e->tune.sparse_desc_min, (int64_t)fsk::SX_SHORT) : fsk::SX_SHORT;
-    const uint32_t OC = desc ? 2u * O : O;  // columns
-    e->sx_desc_used = desc != 0;
+    c.form = c.slot_stride != 0 ? ((e->sx_lists && e->sx_form != 1) ? 0 : 1) : e->sx_form;
+    const bool lists = c.form == 0, blocks = c.form == 2;
+    e->sx_form_used = c.form;
+    c.pairs = lists && e->sx_pairs ? 1 : 0;  // (unit products as bare cells, two to a word: plan_owner_bands)
+    c.slot16 = c.slot_stride != 0 && e->sx_slot16_used;  // (u16 slot triangles: set by accumulate_sparse for a deferred batch)
+    c.O = blocks ? (uint32_t)e->tune.blocks_max_bands : e->n_owners;  // (blocks: the most bands a pass can have)
+    // descriptors (fsk_engine::sx_desc_now): entries of more than short_max partners leave k_sx_emit as one descriptor each (1,
+    // owner bands) or one per sub-band (2, blocks) and the consume kernels walk their partners; the count matrix and the
+    // stream offsets then have two columns a band
+    c.desc = !e->sx_desc_now() ? 0u : lists ? 1u : (blocks && e->tune.sparse_desc_blocks) ? 2u : 0u;
+    c.short_max = c.desc && e->tune.sparse_desc_min > 0 ? (uint32_t)std::min<int64_t>(e->tune.sparse_desc_min, (int64_t)fsk::SX_SHORT) : fsk::SX_SHORT;
+    c.OC = c.desc ? 2u * c.O : c.O;  // columns
+    e->sx_desc_used = c.desc != 0;
+    // skip_test_block: test rows pair only with the train entries of their runs (and themselves)
+    c.skip_from = e->cfg.skip_test_block && e->n_test > 0 ? (uint32_t)e->n_train : 0xffffffffu;
+    c.skipping = c.skip_from != 0xffffffffu;
+    // tiles per chunk of the column scans: 64, fewer for a batch of few tiles (variance mode's: a few thousand) so that the
+    // chunk kernels have a few hundred workgroups and short chains of dependent steps
+    c.uc = ntiles >= 16384u ? (uint32_t)fsk::UC_CHUNK : ntiles >= 4096u ? 16u : 8u;
+    c.nchunks = (ntiles + c.uc - 1) / c.uc;
+    // entries in the packed format (4 + 2 + 2 bytes) when sequence ids, multiplicities and ranks fit 16 bits; the descriptors'
+    // column array: col16 = bits of a sequence id << 1 | two-byte columns (what is left of the 16 or 32 bits holds the multiplicity)
+    c.packed = e->N < 65535 && e->maxW < 65536u && !e->tune.sparse_unpacked;
+    c.col16 = (std::max(1, sx_bits_below((u64)e->N)) << 1) | (e->N < 32768 && e->tune.sparse_desc_cols == 3 ? 1 : 0);
+    c.maxprod = (1u << e->sx_pb) - 1u;
+    c.cmax = c.maxprod / std::max<uint32_t>(1u, e->maxW);  // multiplicities up to here: one word per pair
+
     // (the presort's records, 4 or 8 bytes a window and group, go through the same two buffers first)
     const size_t pre_bytes = sh.share ? (size_t)sh.groups * nfeat * (sh.pre64 ? 8 : 4) : 0;
     for (int b = 0; b < 2; ++b) FSK_HIP(S.d_keys[b].reserve(std::max(pre_bytes, nrec * sizeof(RecT))));
-    FSK_HIP(S.d_blockhist.reserve((size_t)256 * tps * nb));
+    FSK_HIP(S.d_blockhist.reserve((size_t)256 * c.tps * nb));
     FSK_HIP(S.d_totals.reserve((size_t)256 * nb));
     FSK_HIP(S.d_tile_ent.reserve(ntiles));
     FSK_HIP(S.d_tile_lrh.reserve(ntiles));
@@ -264,514 +307,542 @@ int sparse_batch(fsk_engine* e, const int32_t* combos, int nb, u64* K, int64_t r
     FSK_HIP(S.d_ebase.reserve((size_t)ntiles + 1));
     FSK_HIP(S.d_E.reserve(nrec + 2));  // (+ 16 bytes: the descriptors' partners are read in whole 16-byte pieces)
     FSK_HIP(S.d_Pk.reserve(nrec));
-    // skip_test_block: test rows pair only with the train entries of their runs (and themselves)
-    const uint32_t skip_from = e->cfg.skip_test_block && e->n_test > 0 ? (uint32_t)e->n_train : 0xffffffffu;
-    const bool skipping = skip_from != 0xffffffffu;
-    if (skipping) {
+    if (c.skipping) {
         FSK_HIP(S.d_Tk.reserve(nrec));
         FSK_HIP(S.d_tile_lth.reserve(ntiles));
         FSK_HIP(S.d_tile_ts.reserve(ntiles));
     }
     FSK_HIP(S.d_sxstat.reserve(3));
     FSK_HIP(S.d_tile_stat.reserve((size_t)2 * ntiles));
-    FSK_HIP(e->d_pos.reserve(pos_off + (size_t)nb * e->k));
+    FSK_HIP(e->d_pos.reserve(c.pos_off + (size_t)nb * e->k));
     if (!e->owner_ready) {
         FSK_HIP(e->d_owner_r0.reserve(e->h_owner_r0.size()));
         // (once per set of sequences, and every lane's kernels read it: a synchronous copy)
         FSK_HIP(hipMemcpy(e->d_owner_r0.p, e->h_owner_r0.data(), e->h_owner_r0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         e->owner_ready = true;
     }
-    // tiles per chunk of the column scans: 64, fewer for a batch of few tiles (variance mode's: a few thousand) so that the
-    // chunk kernels have a few hundred workgroups and short chains of dependent steps
-    const uint32_t uc = ntiles >= 16384u ? (uint32_t)fsk::UC_CHUNK : ntiles >= 4096u ? 16u : 8u;
-    const uint32_t nchunks = (ntiles + uc - 1) / uc;
     if (lists || blocks) {
-        FSK_HIP(S.d_ucount.reserve((size_t)OC * ntiles));
-        FSK_HIP(S.d_uchunk.reserve((size_t)OC * nchunks));
-        FSK_HIP(S.d_utot.reserve(OC));
-        FSK_HIP(S.d_list_off.reserve((size_t)OC + 1));
-        FSK_HIP(S.d_part_base.reserve((size_t)O + 2));
+        FSK_HIP(S.d_ucount.reserve((size_t)c.OC * ntiles));
+        FSK_HIP(S.d_uchunk.reserve((size_t)c.OC * c.nchunks));
+        FSK_HIP(S.d_utot.reserve(c.OC));
+        FSK_HIP(S.d_list_off.reserve((size_t)c.OC + 1));
+        FSK_HIP(S.d_part_base.reserve((size_t)c.O + 2));
     }
-    fsk::SxIds ids{};
-    const bool by_id = nb <= 16;  // (variance mode: a handful of combos per batch) positions from the resident table
-    bool consecutive = !by_id;
-    if (by_id) {
-        if (!e->allpos_ready) {
-            FSK_HIP(e->d_allpos.reserve(e->all_pos.size()));
-            FSK_HIP(hipMemcpy(e->d_allpos.p, e->all_pos.data(), e->all_pos.size(), hipMemcpyHostToDevice));
-            e->allpos_ready = true;
-        }
-        for (int s = 0; s < nb; ++s) ids.id[s] = combos[s];
-    } else {
-        // (a run of consecutive combo ids — every exact call — reads its kept positions from the resident table of all
-        // combos; the batch's statistics are zeroed by the extraction kernel: no copy or fill command in front of a batch)
-        for (int s = 1; s < nb && consecutive; ++s) consecutive = combos[s] == combos[0] + s;
-        if (consecutive) {
-            if (!e->allpos_ready) {
-                FSK_HIP(e->d_allpos.reserve(e->all_pos.size()));
-                FSK_HIP(hipMemcpy(e->d_allpos.p, e->all_pos.data(), e->all_pos.size(), hipMemcpyHostToDevice));
-                e->allpos_ready = true;
-            }
-        } else {
-            for (int s = 0; s < nb; ++s)
-                memcpy(pos_pin + (size_t)s * e->k, &e->all_pos[(size_t)combos[s] * e->k], e->k);
-            FSK_HIP(hipMemcpyAsync(e->d_pos.p + pos_off, pos_pin, (size_t)nb * e->k, hipMemcpyHostToDevice, stream));
-        }
+    // positions: a handful of combos (variance mode) by id, a run of consecutive combo ids (every exact call) as a piece of
+    // the resident table of all combos, anything else through the pinned staging (the batch's statistics are zeroed by the
+    // extraction kernel: no copy or fill command in front of a batch)
+    c.by_id = nb <= 16;
+    bool consecutive = !c.by_id;
+    for (int s = 1; s < nb && consecutive; ++s) consecutive = c.combos[s] == c.combos[0] + s;
+    if ((c.by_id || consecutive) && !e->allpos_ready) {
+        FSK_HIP(e->d_allpos.reserve(e->all_pos.size()));
+        FSK_HIP(hipMemcpy(e->d_allpos.p, e->all_pos.data(), e->all_pos.size(), hipMemcpyHostToDevice));
+        e->allpos_ready = true;
     }
+    if (c.by_id) {
+        for (int s = 0; s < nb; ++s) c.ids.id[s] = c.combos[s];
+    } else if (!consecutive) {
+        for (int s = 0; s < nb; ++s) memcpy(c.pos_pin + (size_t)s * e->k, &e->all_pos[(size_t)c.combos[s] * e->k], e->k);
+        FSK_HIP(hipMemcpyAsync(e->d_pos.p + c.pos_off, c.pos_pin, (size_t)nb * e->k, hipMemcpyHostToDevice, c.stream));
+    }
+    c.pos_tab = c.by_id ? (const uint8_t*)e->d_allpos.p
+                : consecutive ? (const uint8_t*)e->d_allpos.p + (size_t)c.combos[0] * e->k : (const uint8_t*)e->d_pos.p + c.pos_off;
+    return FSK_OK;
+}
 
-    RecT* rec[2] = {(RecT*)S.d_keys[0].p, (RecT*)S.d_keys[1].p};
+// Shared prefixes: the windows in the order of their leading part, once per group of slots (presort records of T: 4 or 8
+// bytes), in the group's copy that its slots extract from.
+template <typename RecT, typename T>
+int sx_presort(const SxBatch& c, const fsk::SxSrc& src, bool small) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    const SxShare& sh = c.sh;
+    const uint32_t G = sh.groups, nfeat = c.nfeat, tps = c.tps;
+    FSK_HIP(S.d_group_of.reserve((size_t)c.nb));
+    FSK_HIP(S.d_group_head.reserve((size_t)c.nb));
+    FSK_HIP(S.d_winp.reserve((size_t)G * nfeat * e->win_words));
+    FSK_HIP(S.d_part.reserve((size_t)G * nfeat * sizeof(RecT)));
+    FSK_LAUNCH(fsk::k_sx_group_tables, dim3(1), dim3(1024), 0, c.stream, src, (uint32_t)c.nb, sh.share, S.d_group_of.p, S.d_group_head.p);
+    T* pre[2] = {(T*)S.d_keys[0].p, (T*)S.d_keys[1].p};
+    const uint32_t dmask_top = (1u << sx_first_pass_bits(sh.topbits)) - 1u;
+    sx_with_flags([&](auto w2, auto sm) {
+        auto k = fsk::k_sx_group_extract<T, w2 ? 2 : 4, sm && sizeof(T) == 4>;
+        FSK_LAUNCH(k, dim3(tps, G), dim3(256), 0, c.stream, src, (const uint32_t*)S.d_group_head.p, sh.share, sh.wb, nfeat, tps, pre[0],
+                   S.d_blockhist.p, dmask_top);
+    }, e->win_words == 2, small);
+    int cur = 0;
+    const int rc = sx_sort<T>(e, S, c.stream, pre, nfeat, tps, G, sh.wb, sh.topbits, &cur);
+    if (rc) return rc;
+    sx_with_flags([&](auto w2) {
+        auto k = fsk::k_sx_group_gather<T, RecT, w2 ? 2 : 4>;
+        FSK_LAUNCH(k, dim3((nfeat + 255u) / 256u, G), dim3(256), 0, c.stream, (const T*)pre[cur], (const uint32_t*)e->d_win.p,
+                   (const uint32_t*)e->d_featseq.p, nfeat, sh.wb, sh.lowbits + e->sx_sb, S.d_winp.p, (RecT*)S.d_part.p);
+    }, e->win_words == 2);
+    e->st.launches += 3;
+    return FSK_OK;
+}
 
-    e->tic(stream);
-    const uint8_t* const pos_tab = by_id ? (const uint8_t*)e->d_allpos.p
-                                   : consecutive ? (const uint8_t*)e->d_allpos.p + (size_t)combos[0] * e->k : (const uint8_t*)e->d_pos.p + pos_off;
+// Extraction: the sort records of every slot, the digits of the first sort pass counted on the way — from its group's
+// presorted windows (shared prefixes), from the packed windows, or symbol by symbol (g-mers beyond 128 bits).
+template <typename RecT>
+int sx_extract(const SxBatch& c) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    const uint32_t nfeat = c.nfeat, tps = c.tps, nb = (uint32_t)c.nb;
+    RecT* const rec = (RecT*)S.d_keys[0].p;
+    const uint32_t dmask = (1u << sx_first_pass_bits(c.keybits)) - 1u;
     u64* const zeroed_stats = S.d_sxstat.p;
     const int ww = e->win_words;
     constexpr bool R32 = sizeof(RecT) == 4;
     const bool small = R32 && e->V <= ((u64)1 << 24) && e->sigma < (1u << 24);  // (the k-mer and every prefix of it fit 24 bits)
+    // (four slots per workgroup share the window loads when that still leaves a few thousand workgroups)
+    const bool four = e->tune.extract_slots ? e->tune.extract_slots == 4 : (u64)tps * (u64)nb >= 8192;
+    const dim3 grid(tps, four ? (nb + 3u) / 4u : nb);
+    e->tic(c.stream);
     fsk::SxSrc src{};
-    src.win = e->d_win.p; src.feat_seq = e->d_featseq.p; src.combo_pos = pos_tab;
-    src.k = e->k; src.sb = sb; src.bits = e->bits; src.by_id = by_id ? 1 : 0; src.sigma = e->sigma; src.symbits = e->sx_symbits; src.ids = ids;
+    src.win = e->d_win.p; src.feat_seq = e->d_featseq.p; src.combo_pos = c.pos_tab;
+    src.k = e->k; src.sb = e->sx_sb; src.bits = e->bits; src.by_id = c.by_id ? 1 : 0; src.sigma = e->sigma; src.symbits = e->sx_symbits; src.ids = c.ids;
     src.c0 = 0;
-    if (sh.share) {
-        // the presort: the windows in the order of their leading part, once per group of slots; every slot then extracts from
-        // its group's copy and sorts by the rest of its key alone
-        const uint32_t G = sh.groups;
-        FSK_HIP(S.d_group_of.reserve((size_t)nb));
-        FSK_HIP(S.d_group_head.reserve((size_t)nb));
-        FSK_HIP(S.d_winp.reserve((size_t)G * nfeat * ww));
-        FSK_HIP(S.d_part.reserve((size_t)G * nfeat * sizeof(RecT)));
-        FSK_LAUNCH(fsk::k_sx_group_tables, dim3(1), dim3(1024), 0, stream, src, (uint32_t)nb, sh.share, S.d_group_of.p, S.d_group_head.p);
-        const uint32_t dmask_top = (1u << sx_first_pass_bits(sh.topbits)) - 1u;
-        const dim3 ggrid((nfeat + 255u) / 256u, G);
-        RecT* const part = reinterpret_cast<RecT*>(S.d_part.p);
-        int rcs = FSK_OK, pcur = 0;
-        if (!sh.pre64) {
-            uint32_t* pre[2] = {(uint32_t*)S.d_keys[0].p, (uint32_t*)S.d_keys[1].p};
-            auto k_ge = ww == 2 ? (small ? fsk::k_sx_group_extract<uint32_t, 2, true> : fsk::k_sx_group_extract<uint32_t, 2, false>)
-                                : (small ? fsk::k_sx_group_extract<uint32_t, 4, true> : fsk::k_sx_group_extract<uint32_t, 4, false>);
-            FSK_LAUNCH(k_ge, dim3(tps, G), dim3(256), 0, stream, src, (const uint32_t*)S.d_group_head.p, sh.share, sh.wb, nfeat, tps, pre[0],
-                       S.d_blockhist.p, dmask_top);
-            rcs = sx_sort<uint32_t>(e, S, stream, pre, nfeat, tps, G, sh.wb, sh.topbits, &pcur);
-            if (rcs) return rcs;
-            auto k_gg = ww == 2 ? fsk::k_sx_group_gather<uint32_t, RecT, 2> : fsk::k_sx_group_gather<uint32_t, RecT, 4>;
-            FSK_LAUNCH(k_gg, ggrid, dim3(256), 0, stream, (const uint32_t*)pre[pcur], (const uint32_t*)e->d_win.p, (const uint32_t*)e->d_featseq.p,
-                       nfeat, sh.wb, sh.lowbits + sb, S.d_winp.p, part);
-        } else {
-            u64* pre[2] = {(u64*)S.d_keys[0].p, (u64*)S.d_keys[1].p};
-            auto k_ge = ww == 2 ? fsk::k_sx_group_extract<u64, 2, false> : fsk::k_sx_group_extract<u64, 4, false>;
-            FSK_LAUNCH(k_ge, dim3(tps, G), dim3(256), 0, stream, src, (const uint32_t*)S.d_group_head.p, sh.share, sh.wb, nfeat, tps, pre[0],
-                       S.d_blockhist.p, dmask_top);
-            rcs = sx_sort<u64>(e, S, stream, pre, nfeat, tps, G, sh.wb, sh.topbits, &pcur);
-            if (rcs) return rcs;
-            auto k_gg = ww == 2 ? fsk::k_sx_group_gather<u64, RecT, 2> : fsk::k_sx_group_gather<u64, RecT, 4>;
-            FSK_LAUNCH(k_gg, ggrid, dim3(256), 0, stream, (const u64*)pre[pcur], (const uint32_t*)e->d_win.p, (const uint32_t*)e->d_featseq.p,
-                       nfeat, sh.wb, sh.lowbits + sb, S.d_winp.p, part);
-        }
-        e->st.launches += 3;
+    if (c.sh.share) {
+        const int rc = c.sh.pre64 ? sx_presort<RecT, u64>(c, src, small) : sx_presort<RecT, uint32_t>(c, src, small);
+        if (rc) return rc;
         src.win = S.d_winp.p;
-        src.c0 = sh.share;
-        const bool four = e->tune.extract_slots ? e->tune.extract_slots == 4 : (u64)tps * (u64)nb >= 8192;
-#define FSK_EXTRACT_SHARED(SPW)                                                                                              \
-    (ww == 2 ? (small ? fsk::k_sx_extract_shared<RecT, 2, R32, SPW> : fsk::k_sx_extract_shared<RecT, 2, false, SPW>)          \
-             : (small ? fsk::k_sx_extract_shared<RecT, 4, R32, SPW> : fsk::k_sx_extract_shared<RecT, 4, false, SPW>))
-        auto k_ex = four ? FSK_EXTRACT_SHARED(4) : FSK_EXTRACT_SHARED(1);
-#undef FSK_EXTRACT_SHARED
-        FSK_LAUNCH(k_ex, dim3(tps, four ? ((uint32_t)nb + 3u) / 4u : (uint32_t)nb), dim3(256), 0, stream, src, (const uint32_t*)S.d_group_of.p,
-                   (const RecT*)part, nfeat, tps, (uint32_t)nb, rec[0], S.d_blockhist.p, dmask, zeroed_stats);
+        src.c0 = c.sh.share;
+        sx_with_flags([&](auto w2, auto sm, auto f4) {
+            auto k = fsk::k_sx_extract_shared<RecT, w2 ? 2 : 4, sm && R32, f4 ? 4 : 1>;
+            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, (const uint32_t*)S.d_group_of.p, (const RecT*)S.d_part.p, nfeat, tps, nb, rec,
+                       S.d_blockhist.p, dmask, zeroed_stats);
+        }, ww == 2, small, four);
     } else if (ww) {
-        // (four slots per workgroup share the window loads when that still leaves a few thousand workgroups)
-        const bool four = e->tune.extract_slots ? e->tune.extract_slots == 4 : (u64)tps * (u64)nb >= 8192;
-#define FSK_EXTRACT_WIN(SPW)                                                                                          \
-    (ww == 2 ? (small ? fsk::k_sx_extract_win<RecT, 2, R32, SPW> : fsk::k_sx_extract_win<RecT, 2, false, SPW>)         \
-             : (small ? fsk::k_sx_extract_win<RecT, 4, R32, SPW> : fsk::k_sx_extract_win<RecT, 4, false, SPW>))
-        auto k_ex = four ? FSK_EXTRACT_WIN(4) : FSK_EXTRACT_WIN(1);
-#undef FSK_EXTRACT_WIN
-        FSK_LAUNCH(k_ex, dim3(tps, four ? ((uint32_t)nb + 3u) / 4u : (uint32_t)nb), dim3(256), 0, stream, src, nfeat, tps, (uint32_t)nb, rec[0],
-                   S.d_blockhist.p, dmask, zeroed_stats);
+        sx_with_flags([&](auto w2, auto sm, auto f4) {
+            auto k = fsk::k_sx_extract_win<RecT, w2 ? 2 : 4, sm && R32, f4 ? 4 : 1>;
+            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, nfeat, tps, nb, rec, S.d_blockhist.p, dmask, zeroed_stats);
+        }, ww == 2, small, four);
     } else {
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_sx_extract<RecT>), dim3(tps, nb), dim3(256), 0, stream, e->view(), e->d_featseq.p,
-                   e->d_fstart.p, nfeat, tps, e->k, e->sigma, sb, pos_tab, rec[0], S.d_blockhist.p, dmask, ids, zeroed_stats, by_id ? 1 : 0, e->sx_symbits);
+        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_sx_extract<RecT>), dim3(tps, nb), dim3(256), 0, c.stream, e->view(), e->d_featseq.p,
+                   e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S.d_blockhist.p, dmask, c.ids, zeroed_stats,
+                   c.by_id ? 1 : 0, e->sx_symbits);
     }
-    e->toc(&e->st.ms_extract, stream);
+    e->toc(&e->st.ms_extract, c.stream);
     e->st.launches += 1;
+    return FSK_OK;
+}
 
-    e->tic(stream);
-    int cur = 0;
-    {
-        const int rcs = sx_sort<RecT>(e, S, stream, rec, nfeat, tps, (uint32_t)nb, sb, keybits, &cur);
-        if (rcs) return rcs;
-    }
-    e->toc(&e->st.ms_sort, stream);
-    e->st.sort_records += nrec;
-    e->st.sort_passes = passes;
-
-    e->tic(stream);
-    const uint32_t maxprod = (1u << e->sx_pb) - 1u;
-    const uint32_t cmax = maxprod / std::max<uint32_t>(1u, e->maxW);  // multiplicities up to here: one word per pair
+// Segments: the entries of every tile counted and their bases scanned — by one workgroup over the tile records, or as chunk
+// totals, the same scan over the chunk records and the chunks with their carries. Opens ms_segment, which the update stage
+// closes once the batch's word count is known.
+template <typename RecT>
+int sx_segment(SxBatch& c) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    const uint32_t ntiles = c.ntiles;
+    const bool skipping = c.skipping;
+    e->tic(c.stream);
     {
         auto k_cnt = skipping ? fsk::k_sx_seg_count<RecT, true> : fsk::k_sx_seg_count<RecT, false>;
-        FSK_LAUNCH(k_cnt, dim3(tpg, nb), dim3(256), 0, stream, (const RecT*)rec[cur], nfeat, tpg, sb, S.d_tile_ent.p, S.d_tile_lrh.p, skip_from,
-                   skipping ? S.d_tile_lth.p : (int*)nullptr);
+        FSK_LAUNCH(k_cnt, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, S.d_tile_ent.p,
+                   S.d_tile_lrh.p, c.skip_from, skipping ? S.d_tile_lth.p : (int*)nullptr);
     }
-    {
-        const int* lth = skipping ? (const int*)S.d_tile_lth.p : (const int*)nullptr;
-        int* ts = skipping ? S.d_tile_ts.p : (int*)nullptr;
-        if (ntiles <= 4096u && !e->tune.seg_scan_chunked) {  // one workgroup walks the tile records
-            FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
-                       S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
-        } else {  // chunk totals, the same scan over the chunk records, the chunks with their carries
-            const uint32_t nch = (ntiles + 1023u) / 1024u;
-            FSK_HIP(S.d_segc.reserve((size_t)6 * (nch + 1)));
-            uint32_t* c_tot = S.d_segc.p;
-            int* c_lrh = reinterpret_cast<int*>(c_tot + (nch + 1));
-            int* c_lth = c_lrh + (nch + 1);
-            uint32_t* c_ex = reinterpret_cast<uint32_t*>(c_lth + (nch + 1));
-            int* c_h = reinterpret_cast<int*>(c_ex + (nch + 1));
-            int* c_t = c_h + (nch + 1);
-            FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
-                       (uint32_t*)nullptr, (int*)nullptr, lth, (int*)nullptr, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       c_tot, c_lrh, c_lth);
-            FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, stream, (const uint32_t*)c_tot, (const int*)c_lrh, nch, c_ex, c_h,
-                       skipping ? (const int*)c_lth : (const int*)nullptr, skipping ? c_t : (int*)nullptr, (const uint32_t*)nullptr,
-                       (const int*)nullptr, (const int*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
-            FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
-                       S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)c_ex, (const int*)c_h, (const int*)c_t, (uint32_t*)nullptr,
-                       (int*)nullptr, (int*)nullptr);
-            e->st.launches += 2;
-        }
-    }
-    // entries in the packed format (4 + 2 + 2 bytes) when sequence ids, multiplicities and ranks fit 16 bits
-    const bool packed = e->N < 65535 && e->maxW < 65536u && !e->tune.sparse_unpacked;
-    // descriptors: the entries' column array (what the partners are read from: 2 bytes when N < 32768, else 4)
-    // (col16 = bits of a sequence id << 1 | two-byte columns: what is left of the 16 or 32 bits holds the multiplicity)
-    const int colbits = std::max(1, sx_bits_below((u64)e->N));
-    const int col16 = (colbits << 1) | (e->N < 32768 && e->tune.sparse_desc_cols == 3 ? 1 : 0);
-    void* colp = nullptr;
-    if (desc && (e->tune.sparse_desc_cols >= 2 || (e->tune.sparse_desc_cols == 1 && !packed))) {
-        FSK_HIP(S.d_cols.reserve(((col16 & 1) ? (nrec + 1) / 2 : nrec) + 4));  // (+ 16 bytes: a lane's last load reads whole 16-byte pieces)
-        colp = (void*)S.d_cols.p;
-    }
-    if (blocks) {
-        // ---- the two-level form (fsk_sparse_blocks.inc): passes over disjoint row ranges, each sized exactly (a pass is
-        // milliseconds of work: the wait for its word count does not show). A range that does not fit one pass — more cells
-        // than 2^32 or than its bands cover, more words than 32-bit offsets address — is halved by cells.
-        const u64 pass_words = e->tune.blocks_pass_words > 0 ? (u64)e->tune.blocks_pass_words : ((u64)1 << 31);
-        const u64 total_cells = (u64)e->N * ((u64)e->N + 1) / 2;
-        stat_pin[0] = stat_pin[1] = 0;
-        e->toc(&e->st.ms_segment, stream);
-        e->tic(stream);
-        std::vector<std::pair<int64_t, int64_t>> todo;
-        todo.emplace_back(row0, row1);
-        u64 batch_pairs = 0;  // (the passes' += in all: what decides about descriptors for the batches that follow)
-        bool first_pass = true;
-        while (!todo.empty()) {
-            const int64_t ra = todo.back().first, rb = todo.back().second;
-            todo.pop_back();
-            if (rb <= ra) continue;
-            auto halve = [&]() {  // by cells: the row whose first cell is the middle one
-                const u64 ca = (u64)ra * ((u64)ra + 1) / 2, cb = (u64)rb * ((u64)rb + 1) / 2, mid = ca + (cb - ca) / 2;
-                int64_t lo = ra + 1, hi = rb - 1;
-                while (lo < hi) {
-                    const int64_t m = (lo + hi) / 2;
-                    if ((u64)m * ((u64)m + 1) / 2 < mid) lo = m + 1; else hi = m;
-                }
-                todo.emplace_back(lo, rb);  // (the lower rows first: the stack pops them next)
-                todo.emplace_back(ra, lo);
-            };
-            SxPass P;
-            // (what the range is expected to emit, by its share of the triangle: a range that would overflow a pass is not tried)
-            const u64 cells = (u64)rb * ((u64)rb + 1) / 2 - (u64)ra * ((u64)ra + 1) / 2;
-            const bool too_many = e->sx_wpr != 0 && rb - ra > 1 &&
-                                  (double)e->sx_words_of(nrec) * ((double)cells / (double)std::max<u64>(1, total_cells)) > 0.9 * (double)pass_words;
-            if (too_many || !blocks_plan_pass(e, ra, rb, &P)) {
-                if (rb - ra <= 1) return e->fail(FSK_EUNSUPPORTED, "sparse dataflow: row %lld does not fit one pass of the two-level form", (long long)ra);
-                halve();
-                continue;
-            }
-            const uint32_t Op = P.n_owners;
-            {   // (a pass of ONE row longer than blocks_max_bands bands cover has more bands than that — up to SX_MAX_OWNERS —: the
-                // count matrix and the offsets by this pass's own bands; found by tools/stress_parity.py's blocks cases as a
-                // memory fault at N = 6500 with seven bands of 2^9 cells a pass. The previous pass has been waited for.)
-                const size_t cols = (size_t)(desc ? 2u : 1u) * std::max(Op, O);
-                FSK_HIP(S.d_ucount.reserve(cols * ntiles));
-                FSK_HIP(S.d_uchunk.reserve(cols * nchunks));
-                FSK_HIP(S.d_utot.reserve(cols));
-                FSK_HIP(S.d_list_off.reserve(cols + 1));
-                FSK_HIP(S.d_part_base.reserve((size_t)std::max(Op, O) + 2));
-            }
-            FSK_HIP(e->d_blk_r0.reserve((size_t)fsk::SX_MAX_OWNERS + 1));
-            // (the previous pass has been waited for: nothing reads the table any more)
-            FSK_HIP(hipMemcpy(e->d_blk_r0.p, P.r0.data(), P.r0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            if (!first_pass) FSK_HIP(hipMemsetAsync(S.d_sxstat.p, 0, 3 * sizeof(u64), stream));  // (the first pass: zeroed by the extraction kernel)
-            first_pass = false;
-            const uint32_t maxprod_p = (1u << P.pb) - 1u, cmax_p = maxprod_p / std::max<uint32_t>(1u, e->maxW);
-            u64 pass_stat[2] = {0, 0};
-            // stat_pin is pinned host memory the device writes: this pass's totals land there, the batch's are summed below
-            u64* const pin = stat_pin;
-            pin[0] = pin[1] = 0;
-            if (packed) {
-                auto k_seg = desc ? (skipping ? fsk::k_sx_seg_write<RecT, true, false, true, true> : fsk::k_sx_seg_write<RecT, true, false, false, true>)
-                                  : (skipping ? fsk::k_sx_seg_write<RecT, true, false, true> : fsk::k_sx_seg_write<RecT, true, false, false>);
-                FSK_LAUNCH(k_seg, dim3(tpg, nb), dim3(256), 0, stream, (const RecT*)rec[cur], nfeat, tpg, sb, (const uint32_t*)S.d_ebase.p,
-                           (const int*)S.d_tile_rs.p, reinterpret_cast<uint32_t*>(S.d_E.p), reinterpret_cast<uint16_t*>(S.d_Pk.p), P.t, Op,
-                           S.d_ucount.p, (uint32_t)ra, (uint32_t)rb, e->maxW, maxprod_p, cmax_p, S.d_tile_stat.p, skip_from,
-                           skipping ? (const int*)S.d_tile_ts.p : (const int*)nullptr,
-                           skipping ? reinterpret_cast<uint16_t*>(S.d_Tk.p) : (uint16_t*)nullptr, P.own_base, short_max, desc, P.sub_shift, colp, col16);
-            } else {
-                auto k_seg = desc ? (skipping ? fsk::k_sx_seg_write<RecT, false, false, true, true> : fsk::k_sx_seg_write<RecT, false, false, false, true>)
-                                  : (skipping ? fsk::k_sx_seg_write<RecT, false, false, true> : fsk::k_sx_seg_write<RecT, false, false, false>);
-                FSK_LAUNCH(k_seg, dim3(tpg, nb), dim3(256), 0, stream, (const RecT*)rec[cur], nfeat, tpg, sb, (const uint32_t*)S.d_ebase.p,
-                           (const int*)S.d_tile_rs.p, S.d_E.p, S.d_Pk.p, P.t, Op, S.d_ucount.p, (uint32_t)ra, (uint32_t)rb, e->maxW, maxprod_p,
-                           cmax_p, S.d_tile_stat.p, skip_from, skipping ? (const int*)S.d_tile_ts.p : (const int*)nullptr,
-                           skipping ? S.d_Tk.p : (uint32_t*)nullptr, P.own_base, short_max, desc, P.sub_shift, colp, col16);
-            }
-            const uint32_t OCp = desc ? 2u * Op : Op, wcol = desc ? Op : 0u;  // (columns: descriptor streams first, then the words')
-            FSK_LAUNCH(fsk::k_sx_ucol_sum, dim3(nchunks), dim3(256), 0, stream, (const uint32_t*)S.d_ucount.p, ntiles, OCp, S.d_uchunk.p,
-                       (const u64*)S.d_tile_stat.p, S.d_sxstat.p, pin, uc);
-            FSK_LAUNCH(fsk::k_sx_ucol_scan, dim3(OCp), dim3(256), 0, stream, S.d_uchunk.p, nchunks, OCp, S.d_utot.p);
-            FSK_LAUNCH(fsk::k_sx_ucol_apply, dim3(nchunks), dim3(256), 0, stream, S.d_ucount.p, ntiles, OCp, (const uint32_t*)S.d_uchunk.p,
-                       (const uint32_t*)S.d_utot.p, S.d_list_off.p, uc);
-            e->st.launches += 4;
-            FSK_HIP(hipStreamSynchronize(stream));
-            pass_stat[0] = pin[0]; pass_stat[1] = pin[1];
-            const u64 words = pass_stat[1];
-            if (words >= pass_words && rb - ra > 1) {  // (does not fit 32-bit offsets with room to spare: the halves, each from its own count)
-                halve();
-                first_pass = false;
-                continue;
-            }
-            if (words >= ((u64)1 << 32))
-                return e->fail(FSK_EUNSUPPORTED, "sparse dataflow: row %lld alone emits %llu update words a batch", (long long)ra, (unsigned long long)words);
-            e->u_extra += pass_stat[0];
-            batch_pairs += pass_stat[0];
-            e->sx_passes += 1;
-            if (e->trace())
-                fprintf(stderr, "[fsk] sparse blocks: pass rows [%lld, %lld), %u bands of 2^%d cells, %u sub-bands a band, %d product bits, %llu words\n",
-                        (long long)ra, (long long)rb, Op, P.t, P.submax, P.pb, (unsigned long long)words);
-            if (words == 0) continue;
-            if ((size_t)words > S.d_ulist.cap) FSK_HIP(S.d_ulist.reserve((size_t)(words + words / 8)));
-            if ((size_t)words > S.d_ulist2.cap) FSK_HIP(S.d_ulist2.reserve((size_t)(words + words / 8)));
-            const size_t nsub = (size_t)Op * P.submax;
-            FSK_HIP(S.d_subcnt.reserve(nsub));
-            FSK_HIP(S.d_suboff.reserve(nsub));
-            FSK_HIP(S.d_subcur.reserve(nsub));
-            FSK_HIP(hipMemsetAsync(S.d_subcnt.p, 0, nsub * sizeof(uint32_t), stream));
-            if (k_wait) { FSK_HIP(hipStreamWaitEvent(stream, k_wait, 0)); k_wait = nullptr; }
-            if (packed) {
-                auto k_emit = desc ? (skipping ? fsk::k_sx_emit<false, true, true, true> : fsk::k_sx_emit<false, false, true, true>)
-                                   : (skipping ? fsk::k_sx_emit<false, true, true> : fsk::k_sx_emit<false, false, true>);
-                FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, reinterpret_cast<const uint32_t*>(S.d_E.p),
-                           reinterpret_cast<const uint16_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_blk_r0.p, P.t, Op,
-                           (const uint32_t*)S.d_list_off.p, (const uint32_t*)S.d_ucount.p, S.d_ulist.p, (uint32_t)ra, (uint32_t)rb, e->maxW,
-                           maxprod_p, cmax_p, P.pb, K, tpg, (u64)0,
-                           skipping ? reinterpret_cast<const uint16_t*>(S.d_Tk.p) : (const uint16_t*)nullptr, (const u64*)S.d_sxstat.p, ~(u64)0,
-                           ntiles, 0, P.own_base, short_max, desc, P.sub_shift);
-            } else {
-                auto k_emit = desc ? (skipping ? fsk::k_sx_emit<false, true, false, true> : fsk::k_sx_emit<false, false, false, true>)
-                                   : (skipping ? fsk::k_sx_emit<false, true, false> : fsk::k_sx_emit<false, false, false>);
-                FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, (const uint2*)S.d_E.p, (const uint32_t*)S.d_Pk.p,
-                           (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_blk_r0.p, P.t, Op, (const uint32_t*)S.d_list_off.p,
-                           (const uint32_t*)S.d_ucount.p, S.d_ulist.p, (uint32_t)ra, (uint32_t)rb, e->maxW, maxprod_p, cmax_p, P.pb, K, tpg, (u64)0,
-                           skipping ? (const uint32_t*)S.d_Tk.p : (const uint32_t*)nullptr, (const u64*)S.d_sxstat.p, ~(u64)0, ntiles, 0, P.own_base, short_max, desc, P.sub_shift);
-            }
-            // (persistent launches: two workgroups of 1024 threads a CU walk the tiles of the bands' streams in contiguous chunks)
-            const uint32_t n_tiles_max = Op + (uint32_t)((words + fsk::SXB_TILE - 1) / fsk::SXB_TILE);
-            const uint32_t n_split = std::min<uint32_t>(n_tiles_max, 2u * (uint32_t)std::max(1, e->n_cu));
-            const uint32_t* const w_off = (const uint32_t*)S.d_list_off.p + wcol;  // where the bands' word streams start
-            FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, stream, w_off, Op, (uint32_t)fsk::SXB_TILE, S.d_part_base.p,
-                       (const u64*)S.d_sxstat.p, ~(u64)0, 0u, (uint32_t*)nullptr, 0xffffffffu, 1u);
-            FSK_LAUNCH(fsk::k_sxb_count, dim3(n_split), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_ulist.p, w_off,
-                       (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcnt.p);
-            FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_subcnt.p, w_off, P.submax,
-                       S.d_suboff.p, S.d_subcur.p, 0);
-            if (desc) {  // the descriptor records by (band, sub-band): count, scan, scatter (into the head of the second buffer, as in the first)
-                FSK_HIP(S.d_dsubcnt.reserve(nsub));
-                FSK_HIP(S.d_dsuboff.reserve(nsub));
-                FSK_HIP(S.d_dsubcur.reserve(nsub));
-                FSK_HIP(hipMemsetAsync(S.d_dsubcnt.p, 0, nsub * sizeof(uint32_t), stream));
-                const dim3 dgrid((uint32_t)std::max(1, 4 * e->n_cu / (int)std::max(1u, Op)) + 1u, Op);
-                FSK_LAUNCH(fsk::k_sxb_drecords<false>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
-                           S.d_dsubcnt.p, (uint4*)nullptr);
-                FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_dsubcnt.p, (const uint32_t*)S.d_list_off.p,
-                           P.submax, S.d_dsuboff.p, S.d_dsubcur.p, 2);
-                FSK_LAUNCH(fsk::k_sxb_drecords<true>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
-                           S.d_dsubcur.p, reinterpret_cast<uint4*>(S.d_ulist2.p));
-                e->st.launches += 3;
-            }
-            {   // (workgroups of 256 threads, three a CU by their LDS; tuning blocks_scatter_threads: 512 / 1024 for the A/B)
-                const int nt = e->tune.blocks_scatter_threads ? (int)e->tune.blocks_scatter_threads : 256;
-                const uint32_t per_cu = nt == 1024 ? 2u : 3u;
-                const uint32_t grid = std::min<uint32_t>(n_tiles_max, per_cu * (uint32_t)std::max(1, e->n_cu));
-                auto k_sc = nt == 1024 ? fsk::k_sxb_scatter<1024> : nt == 512 ? fsk::k_sxb_scatter<512> : fsk::k_sxb_scatter<256>;
-                FSK_LAUNCH(k_sc, dim3(grid), dim3((uint32_t)nt), 0, stream, (const uint32_t*)S.d_ulist.p, w_off,
-                           (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcur.p, S.d_ulist2.p);
-            }
-            const size_t lds_sub = sizeof(uint32_t) << P.sub_shift;
-            {   // (a block of 2^13 cells and fewer: workgroups of 512 threads, four a CU)
-                auto k_cs = P.sub_shift <= 13 ? fsk::k_sxb_consume<512> : fsk::k_sxb_consume<1024>;
-                FSK_HIP(fsk_hw::allow_dynamic_lds(k_cs, lds_sub));
-                FSK_LAUNCH(k_cs, dim3(P.submax, Op), dim3(P.sub_shift <= 13 ? 512u : 1024u), lds_sub, stream, (const uint32_t*)S.d_ulist2.p,
-                           (const uint32_t*)S.d_suboff.p, (const uint32_t*)S.d_subcnt.p, (const uint32_t*)e->d_blk_r0.p, P.pb, P.sub_shift, P.submax, K,
-                           desc ? reinterpret_cast<const uint4*>(S.d_ulist2.p) : (const uint4*)nullptr, (const uint32_t*)S.d_dsuboff.p,
-                           (const uint32_t*)S.d_dsubcnt.p, (const void*)S.d_E.p, packed ? 1 : 0, (const void*)colp, col16);
-            }
-            e->st.launches += 6;
-            FSK_HIP(hipStreamSynchronize(stream));  // (the next pass overwrites the band table, the entries' unit marks and the streams)
-            e->sx_saw(words * std::max<u64>(1, total_cells / std::max<u64>(1, cells)), nrec);  // (words per record as if the whole triangle emitted at this rate)
-        }
-        if (k_wait) FSK_HIP(hipStreamWaitEvent(stream, k_wait, 0));
-        if (row1 > row0)
-            FSK_LAUNCH(fsk::k_sx_diag_windows, dim3((uint32_t)((row1 - row0 + 255) / 256), 1), dim3(256), 0, stream, (const uint32_t*)e->d_fstart.p,
-                       (uint32_t)row0, (uint32_t)row1, (uint32_t)nb, K, (u64)0, (const u64*)nullptr, ~(u64)0, 0, (uint32_t*)nullptr);
-        e->st.launches += 1;
-        if (k_done) FSK_HIP(hipEventRecord(k_done, stream));
-        e->toc(&e->st.ms_pairs, stream);
-        FSK_HIP(hipGetLastError());
-        stat_pin[0] = stat_pin[1] = 0;  // (every pass has been added to u_extra already)
-        e->sx_saw_pairs(batch_pairs, nrec);
-        return FSK_OK;
-    }
-    if (packed) {
-        auto k_seg = desc ? (skipping ? (pairs ? fsk::k_sx_seg_write<RecT, true, true, true, true> : fsk::k_sx_seg_write<RecT, true, false, true, true>)
-                                      : (pairs ? fsk::k_sx_seg_write<RecT, true, true, false, true> : fsk::k_sx_seg_write<RecT, true, false, false, true>))
-                          : (skipping ? (pairs ? fsk::k_sx_seg_write<RecT, true, true, true> : fsk::k_sx_seg_write<RecT, true, false, true>)
-                                      : (pairs ? fsk::k_sx_seg_write<RecT, true, true, false> : fsk::k_sx_seg_write<RecT, true, false, false>));
-        FSK_LAUNCH(k_seg, dim3(tpg, nb), dim3(256), 0, stream, (const RecT*)rec[cur], nfeat, tpg, sb, (const uint32_t*)S.d_ebase.p,
-                   (const int*)S.d_tile_rs.p, reinterpret_cast<uint32_t*>(S.d_E.p), reinterpret_cast<uint16_t*>(S.d_Pk.p), e->sx_own_shift, O,
-                   lists ? S.d_ucount.p : (uint32_t*)nullptr, (uint32_t)row0, (uint32_t)row1, e->maxW, maxprod, cmax, S.d_tile_stat.p,
-                   skip_from, skipping ? (const int*)S.d_tile_ts.p : (const int*)nullptr,
-                   skipping ? reinterpret_cast<uint16_t*>(S.d_Tk.p) : (uint16_t*)nullptr, 0u, short_max, desc, 0, colp, col16);
+    const int* lth = skipping ? (const int*)S.d_tile_lth.p : (const int*)nullptr;
+    int* ts = skipping ? S.d_tile_ts.p : (int*)nullptr;
+    if (ntiles <= 4096u && !e->tune.seg_scan_chunked) {
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
+                   S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                   (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
     } else {
-        auto k_seg = desc ? (skipping ? (pairs ? fsk::k_sx_seg_write<RecT, false, true, true, true> : fsk::k_sx_seg_write<RecT, false, false, true, true>)
-                                      : (pairs ? fsk::k_sx_seg_write<RecT, false, true, false, true> : fsk::k_sx_seg_write<RecT, false, false, false, true>))
-                          : (skipping ? (pairs ? fsk::k_sx_seg_write<RecT, false, true, true> : fsk::k_sx_seg_write<RecT, false, false, true>)
-                                      : (pairs ? fsk::k_sx_seg_write<RecT, false, true, false> : fsk::k_sx_seg_write<RecT, false, false, false>));
-        FSK_LAUNCH(k_seg, dim3(tpg, nb), dim3(256), 0, stream, (const RecT*)rec[cur], nfeat, tpg, sb, (const uint32_t*)S.d_ebase.p,
-                   (const int*)S.d_tile_rs.p, S.d_E.p, S.d_Pk.p, e->sx_own_shift, O,
-                   lists ? S.d_ucount.p : (uint32_t*)nullptr, (uint32_t)row0, (uint32_t)row1, e->maxW, maxprod, cmax, S.d_tile_stat.p,
-                   skip_from, skipping ? (const int*)S.d_tile_ts.p : (const int*)nullptr, skipping ? S.d_Tk.p : (uint32_t*)nullptr, 0u, short_max, desc, 0, colp, col16);
+        const uint32_t nch = (ntiles + 1023u) / 1024u;
+        FSK_HIP(S.d_segc.reserve((size_t)6 * (nch + 1)));
+        uint32_t* c_tot = S.d_segc.p;
+        int* c_lrh = reinterpret_cast<int*>(c_tot + (nch + 1));
+        int* c_lth = c_lrh + (nch + 1);
+        uint32_t* c_ex = reinterpret_cast<uint32_t*>(c_lth + (nch + 1));
+        int* c_h = reinterpret_cast<int*>(c_ex + (nch + 1));
+        int* c_t = c_h + (nch + 1);
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
+                   (uint32_t*)nullptr, (int*)nullptr, lth, (int*)nullptr, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                   c_tot, c_lrh, c_lth);
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)c_tot, (const int*)c_lrh, nch, c_ex, c_h,
+                   skipping ? (const int*)c_lth : (const int*)nullptr, skipping ? c_t : (int*)nullptr, (const uint32_t*)nullptr,
+                   (const int*)nullptr, (const int*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
+                   S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)c_ex, (const int*)c_h, (const int*)c_t, (uint32_t*)nullptr,
+                   (int*)nullptr, (int*)nullptr);
+        e->st.launches += 2;
     }
-    stat_pin[0] = stat_pin[1] = 0;
-    e->st.launches += 3;
-    u64 words = 0;
-    if (lists) {  // where every (tile, owner) share of the update streams starts (+ the batch's pair and word totals)
-        FSK_LAUNCH(fsk::k_sx_ucol_sum, dim3(nchunks), dim3(256), 0, stream, (const uint32_t*)S.d_ucount.p, ntiles, OC, S.d_uchunk.p,
-                   (const u64*)S.d_tile_stat.p, S.d_sxstat.p, stat_pin, uc);
-        FSK_LAUNCH(fsk::k_sx_ucol_scan, dim3(OC), dim3(256), 0, stream, S.d_uchunk.p, nchunks, OC, S.d_utot.p);
-        FSK_LAUNCH(fsk::k_sx_ucol_apply, dim3(nchunks), dim3(256), 0, stream, S.d_ucount.p, ntiles, OC, (const uint32_t*)S.d_uchunk.p,
-                   (const uint32_t*)S.d_utot.p, S.d_list_off.p, uc);
-        e->st.launches += 3;
-    } else {
-        FSK_LAUNCH(fsk::k_sx_stat_sum, dim3(32), dim3(256), 0, stream, (const u64*)S.d_tile_stat.p, ntiles, S.d_sxstat.p, stat_pin);
-        e->st.launches += 1;
+    // descriptors: the entries' column array, what their partners are read from (tuning sparse_desc_cols)
+    if (c.desc && (e->tune.sparse_desc_cols >= 2 || (e->tune.sparse_desc_cols == 1 && !c.packed))) {
+        FSK_HIP(S.d_cols.reserve(((c.col16 & 1) ? (c.nrec + 1) / 2 : c.nrec) + 4));  // (+ 16 bytes: a lane's last load reads whole 16-byte pieces)
+        c.colp = (void*)S.d_cols.p;
     }
-    const bool guarded = guard_cap != 0;
-    u64 cap_words = ~(u64)0;
-    if (guarded) {
-        words = lists ? std::max<u64>(1, std::min(e->sx_words_of(nrec), guard_cap)) : 0;  // (sizes the parts; the kernels read the true offsets)
-        cap_words = guard_cap;
-    } else {
-        FSK_HIP(hipStreamSynchronize(stream));  // the update streams are sized exactly
-        e->u_extra += stat_pin[0];
-        words = stat_pin[1];
-        e->sx_saw(words, nrec);
-        e->sx_saw_pairs(stat_pin[0], nrec);
-    }
-    e->toc(&e->st.ms_segment, stream);
+    return FSK_OK;
+}
 
-    e->tic(stream);
-    const bool use_lists = lists && words < e->sx_max_words();
-    if (slot_stride != 0 && !use_lists) return FSK_RETRY_UNGROUPED;  // (nothing of this batch has touched K yet)
-    if (use_lists) {
-        if (words > 0 || slot_stride != 0) {
-            if (!guarded && (size_t)words > S.d_ulist.cap)  // (grown with headroom: the batches of a pass differ by a few percent)
-                FSK_HIP(S.d_ulist.reserve((size_t)std::max<u64>(1, words + words / 4)));
-            // (function pointers: a template-id with a comma cannot pass through the launch macro)
-            if (packed) {
-                auto k_emit = desc ? (skipping ? fsk::k_sx_emit<false, true, true, true> : fsk::k_sx_emit<false, false, true, true>)
-                                   : (skipping ? fsk::k_sx_emit<false, true, true> : fsk::k_sx_emit<false, false, true>);
-                FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, reinterpret_cast<const uint32_t*>(S.d_E.p),
-                           reinterpret_cast<const uint16_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_owner_r0.p,
-                           e->sx_own_shift, O, (const uint32_t*)S.d_list_off.p, (const uint32_t*)S.d_ucount.p, S.d_ulist.p, (uint32_t)row0,
-                           (uint32_t)row1, e->maxW, maxprod, cmax, e->sx_pb, K, tpg, slot_stride,
-                           skipping ? reinterpret_cast<const uint16_t*>(S.d_Tk.p) : (const uint16_t*)nullptr, (const u64*)S.d_sxstat.p, cap_words, ntiles, pairs, 0u, short_max, desc, 0);
-            } else {
-                auto k_emit = desc ? (skipping ? fsk::k_sx_emit<false, true, false, true> : fsk::k_sx_emit<false, false, false, true>)
-                                   : (skipping ? fsk::k_sx_emit<false, true, false> : fsk::k_sx_emit<false, false, false>);
-                FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, (const uint2*)S.d_E.p, (const uint32_t*)S.d_Pk.p,
-                           (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_owner_r0.p, e->sx_own_shift, O, (const uint32_t*)S.d_list_off.p,
-                           (const uint32_t*)S.d_ucount.p, S.d_ulist.p, (uint32_t)row0, (uint32_t)row1, e->maxW, maxprod, cmax, e->sx_pb, K, tpg,
-                           slot_stride, skipping ? (const uint32_t*)S.d_Tk.p : (const uint32_t*)nullptr, (const u64*)S.d_sxstat.p, cap_words, ntiles, pairs, 0u, short_max, desc, 0);
-            }
-            const size_t lds = (size_t)e->sx_cap * sizeof(uint32_t), lds_slot = (size_t)e->sx_cap_slot * sizeof(uint32_t);
-            FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<false>, lds));
-            FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<true>, lds_slot));
-            // parts of about `target` words: ~1024 workgroups, and never so short that the flush of a
-            // part (up to sx_cap cells) outweighs the words it summed
-            // (tuning sparse_parts_target: tests cut small inputs into several parts a band)
-            const uint32_t target = e->tune.sparse_parts_target > 0 ? (uint32_t)e->tune.sparse_parts_target
-                                                                    : (uint32_t)std::max<u64>((u64)4 * e->sx_cap, (words + 1023) / 1024);
-            // (with descriptors k_sx_parts sets the target itself: about sparse_desc_parts parts, at most one more a band)
-            const uint32_t desc_parts = (uint32_t)std::max<int64_t>(1, e->tune.sparse_desc_parts);
-            const uint32_t max_parts = desc ? O + desc_parts + 9u : O + (uint32_t)(((guarded ? guard_cap : words) + target - 1) / target);
-            const void* const Ep = (const void*)S.d_E.p;
-            if (slot_stride == 0) FSK_HIP(S.d_part_base.reserve((size_t)O + 8 + (size_t)4 * max_parts));  // (bases, total, target, then 16 bytes a part)
-            if (k_wait) FSK_HIP(hipStreamWaitEvent(stream, k_wait, 0));
-            if (slot_stride != 0) {  // one triangle per slot: a slot's words of a stream are one contiguous piece
-                if (slot16) {
-                    auto k_cs16 = fsk::k_sx_consume<true, true>;
-                    FSK_HIP(fsk_hw::allow_dynamic_lds(k_cs16, lds_slot));
-                    FSK_LAUNCH(k_cs16, dim3(O, e->sx_rounds_slot, nb), dim3(fsk::CS_THREADS), lds_slot, stream, (const uint32_t*)S.d_ulist.p,
-                               (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)nullptr, O, target,
-                               e->sx_cap_slot, e->sx_pb, K, (const uint32_t*)S.d_ucount.p, tpg, slot_stride, (const u64*)S.d_sxstat.p, cap_words,
-                               e->sx_ovf_now, pairs, desc, Ep, packed ? 1 : 0, (const void*)colp, col16);
-                } else {
-                    FSK_LAUNCH(fsk::k_sx_consume<true>, dim3(O, e->sx_rounds_slot, nb), dim3(fsk::CS_THREADS), lds_slot, stream, (const uint32_t*)S.d_ulist.p,
-                               (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)nullptr, O, target,
-                               e->sx_cap_slot, e->sx_pb, K, (const uint32_t*)S.d_ucount.p, tpg, slot_stride, (const u64*)S.d_sxstat.p, cap_words,
-                               (uint32_t*)nullptr, pairs, desc, Ep, packed ? 1 : 0, (const void*)colp, col16);
-                }
-            } else {
-                FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, stream, (const uint32_t*)S.d_list_off.p, O, target, S.d_part_base.p,
-                           (const u64*)S.d_sxstat.p, cap_words, desc, S.d_part_base.p + ((O + 2 + 3) & ~3u), max_parts, desc_parts);
-                FSK_LAUNCH(fsk::k_sx_consume<false>, dim3(max_parts, e->sx_rounds), dim3(fsk::CS_THREADS), lds, stream, (const uint32_t*)S.d_ulist.p,
-                           (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)S.d_part_base.p, O, target,
-                           e->sx_cap, e->sx_pb, K, (const uint32_t*)nullptr, tpg, (u64)0, (const u64*)S.d_sxstat.p, cap_words, (uint32_t*)nullptr, pairs,
-                           desc, Ep, packed ? 1 : 0, (const void*)colp, col16);
-                e->st.launches += 1;
-            }
-            e->st.launches += 2;
-        }
+// The bands the update words are binned by: the owner bands of K, or the bands of one pass of the two-level form.
+struct SxBands {
+    const uint32_t* r0;      // on the device: the first row of every band
+    int shift;               // a band: the rows whose first cell, counted from own_base, lies in [o << shift, (o + 1) << shift)
+    uint32_t n, row0, row1;  // bands; the rows the words are for
+    uint32_t maxprod, cmax;
+    int pb;                  // product bits of a word
+    uint32_t own_base;       // blocks: the pass's first cell (mod 2^32)
+    int sub_shift;           // blocks: sub-bands of 2^sub_shift cells
+};
+SxBands sx_owner_bands(const SxBatch& c) {
+    return SxBands{(const uint32_t*)c.e->d_owner_r0.p, c.e->sx_own_shift, c.O, (uint32_t)c.row0, (uint32_t)c.row1, c.maxprod, c.cmax, c.e->sx_pb, 0u, 0};
+}
+
+// k_sx_seg_write: the entries of the sorted records and, by band, the words they will emit (the count matrix; none for the
+// 64-bit atomics)
+template <typename RecT>
+void sx_seg_write(const SxBatch& c, const SxBands& b) {
+    const fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    uint32_t* const ucount = c.form == 1 ? nullptr : S.d_ucount.p;
+    sx_with_flags([&](auto packed, auto pairs, auto skip, auto desc) {
+        using X = fsk::SxEnt<packed>;
+        auto k = fsk::k_sx_seg_write<RecT, packed, pairs, skip, desc>;
+        FSK_LAUNCH(k, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, (const uint32_t*)S.d_ebase.p,
+                   (const int*)S.d_tile_rs.p, reinterpret_cast<typename X::ent_t*>(S.d_E.p), reinterpret_cast<typename X::rank_t*>(S.d_Pk.p),
+                   b.shift, b.n, ucount, b.row0, b.row1, e->maxW, b.maxprod, b.cmax, S.d_tile_stat.p, c.skip_from,
+                   skip ? (const int*)S.d_tile_ts.p : (const int*)nullptr, skip ? reinterpret_cast<typename X::rank_t*>(S.d_Tk.p) : nullptr,
+                   b.own_base, c.short_max, c.desc, b.sub_shift, c.colp, c.col16);
+    }, c.packed, c.pairs != 0, c.skipping, c.desc != 0);
+}
+
+// k_sx_ucol_*: where every (tile, column) share of the update streams starts, and the batch's pair and word totals (into
+// stat_pin)
+void sx_stream_offsets(const SxBatch& c, uint32_t cols) {
+    SxScratch& S = *c.S;
+    FSK_LAUNCH(fsk::k_sx_ucol_sum, dim3(c.nchunks), dim3(256), 0, c.stream, (const uint32_t*)S.d_ucount.p, c.ntiles, cols, S.d_uchunk.p,
+               (const u64*)S.d_tile_stat.p, S.d_sxstat.p, c.stat_pin, c.uc);
+    FSK_LAUNCH(fsk::k_sx_ucol_scan, dim3(cols), dim3(256), 0, c.stream, S.d_uchunk.p, c.nchunks, cols, S.d_utot.p);
+    FSK_LAUNCH(fsk::k_sx_ucol_apply, dim3(c.nchunks), dim3(256), 0, c.stream, S.d_ucount.p, c.ntiles, cols, (const uint32_t*)S.d_uchunk.p,
+               (const uint32_t*)S.d_utot.p, S.d_list_off.p, c.uc);
+}
+
+// k_sx_emit: the update words of the entries, binned by band into the streams — or, `direct`, each one 64-bit atomic into
+// K (no streams, no descriptors)
+void sx_emit(const SxBatch& c, const SxBands& b, bool direct, u64 cap_words) {
+    const fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    sx_with_flags([&](auto dir, auto skip, auto packed, auto desc) {
+        using X = fsk::SxEnt<packed>;
+        auto k = fsk::k_sx_emit<dir, skip, packed, desc && !dir>;
+        FSK_LAUNCH(k, dim3(fsk::xcd_grid(c.ntiles)), dim3(fsk::EM_THREADS), 0, c.stream, reinterpret_cast<const typename X::ent_t*>(S.d_E.p),
+                   reinterpret_cast<const typename X::rank_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, b.r0, b.shift, b.n,
+                   dir ? nullptr : (const uint32_t*)S.d_list_off.p, dir ? nullptr : (const uint32_t*)S.d_ucount.p, dir ? nullptr : S.d_ulist.p,
+                   b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.pb, c.K, c.tpg, c.slot_stride,
+                   skip ? reinterpret_cast<const typename X::rank_t*>(S.d_Tk.p) : nullptr, dir ? nullptr : (const u64*)S.d_sxstat.p, cap_words,
+                   c.ntiles, dir ? 0 : c.pairs, b.own_base, dir ? fsk::SX_SHORT : c.short_max, dir ? 0u : c.desc, b.sub_shift);
+    }, direct, c.skipping, c.packed, c.desc != 0);
+}
+
+// k_sx_consume: the owner bands' streams summed in LDS and added into K — by parts of about `target` words (k_sx_parts cuts
+// them), or (variance mode) by slot, into the slots' own triangles. After k_wait.
+int sx_consume(const SxBatch& c, u64 words, u64 cap_words) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    const uint32_t O = c.O;
+    const size_t lds = (size_t)e->sx_cap * sizeof(uint32_t), lds_slot = (size_t)e->sx_cap_slot * sizeof(uint32_t);
+    FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<false>, lds));
+    FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<true>, lds_slot));
+    // parts of about `target` words: ~1024 workgroups, and never so short that the flush of a
+    // part (up to sx_cap cells) outweighs the words it summed
+    // (tuning sparse_parts_target: tests cut small inputs into several parts a band)
+    const uint32_t target = e->tune.sparse_parts_target > 0 ? (uint32_t)e->tune.sparse_parts_target
+                                                            : (uint32_t)std::max<u64>((u64)4 * e->sx_cap, (words + 1023) / 1024);
+    // (with descriptors k_sx_parts sets the target itself: about sparse_desc_parts parts, at most one more a band)
+    const uint32_t desc_parts = (uint32_t)std::max<int64_t>(1, e->tune.sparse_desc_parts);
+    const uint32_t max_parts = c.desc ? O + desc_parts + 9u : O + (uint32_t)(((c.guard_cap ? c.guard_cap : words) + target - 1) / target);
+    const void* const Ep = (const void*)S.d_E.p;
+    if (c.slot_stride == 0) FSK_HIP(S.d_part_base.reserve((size_t)O + 8 + (size_t)4 * max_parts));  // (bases, total, target, then 16 bytes a part)
+    if (c.k_wait) FSK_HIP(hipStreamWaitEvent(c.stream, c.k_wait, 0));
+    if (c.slot_stride != 0) {  // one triangle per slot: a slot's words of a stream are one contiguous piece
+        if (c.slot16) FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<true, true>, lds_slot));
+        auto k_cs = c.slot16 ? fsk::k_sx_consume<true, true> : fsk::k_sx_consume<true>;
+        FSK_LAUNCH(k_cs, dim3(O, e->sx_rounds_slot, c.nb), dim3(fsk::CS_THREADS), lds_slot, c.stream, (const uint32_t*)S.d_ulist.p,
+                   (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)nullptr, O, target, e->sx_cap_slot,
+                   e->sx_pb, c.K, (const uint32_t*)S.d_ucount.p, c.tpg, c.slot_stride, (const u64*)S.d_sxstat.p, cap_words,
+                   c.slot16 ? e->sx_ovf_now : (uint32_t*)nullptr, c.pairs, c.desc, Ep, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
     } else {
-        if (k_wait) FSK_HIP(hipStreamWaitEvent(stream, k_wait, 0));
-        if (packed) {
-            auto k_emit = skipping ? fsk::k_sx_emit<true, true, true> : fsk::k_sx_emit<true, false, true>;
-            FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, reinterpret_cast<const uint32_t*>(S.d_E.p),
-                       reinterpret_cast<const uint16_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_owner_r0.p, e->sx_own_shift,
-                       O, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)row0, (uint32_t)row1, e->maxW, maxprod,
-                       cmax, e->sx_pb, K, tpg, slot_stride, skipping ? reinterpret_cast<const uint16_t*>(S.d_Tk.p) : (const uint16_t*)nullptr,
-                       (const u64*)nullptr, ~(u64)0, ntiles, 0, 0u, fsk::SX_SHORT, 0u, 0);
-        } else {
-            auto k_emit = skipping ? fsk::k_sx_emit<true, true, false> : fsk::k_sx_emit<true, false, false>;
-            FSK_LAUNCH(k_emit, dim3(fsk::xcd_grid(ntiles)), dim3(fsk::EM_THREADS), 0, stream, (const uint2*)S.d_E.p, (const uint32_t*)S.d_Pk.p,
-                       (const uint32_t*)S.d_ebase.p, (const uint32_t*)e->d_owner_r0.p, e->sx_own_shift, O, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)row0, (uint32_t)row1, e->maxW, maxprod, cmax, e->sx_pb, K, tpg,
-                       slot_stride, skipping ? (const uint32_t*)S.d_Tk.p : (const uint32_t*)nullptr, (const u64*)nullptr, ~(u64)0, ntiles, 0, 0u, fsk::SX_SHORT, 0u, 0);
-        }
+        FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, c.stream, (const uint32_t*)S.d_list_off.p, O, target, S.d_part_base.p,
+                   (const u64*)S.d_sxstat.p, cap_words, c.desc, S.d_part_base.p + ((O + 2 + 3) & ~3u), max_parts, desc_parts);
+        FSK_LAUNCH(fsk::k_sx_consume<false>, dim3(max_parts, e->sx_rounds), dim3(fsk::CS_THREADS), lds, c.stream, (const uint32_t*)S.d_ulist.p,
+                   (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)S.d_part_base.p, O, target, e->sx_cap,
+                   e->sx_pb, c.K, (const uint32_t*)nullptr, c.tpg, (u64)0, (const u64*)S.d_sxstat.p, cap_words, (uint32_t*)nullptr, c.pairs,
+                   c.desc, Ep, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
         e->st.launches += 1;
     }
-    // the diagonal's combo-independent part (the streams and the atomics above carry the rest)
-    if (k_wait && use_lists && !(words > 0 || slot_stride != 0)) FSK_HIP(hipStreamWaitEvent(stream, k_wait, 0));
-    if (row1 > row0)
-        FSK_LAUNCH(fsk::k_sx_diag_windows, dim3((uint32_t)((row1 - row0 + 255) / 256), slot_stride ? nb : 1), dim3(256), 0, stream,
-                   (const uint32_t*)e->d_fstart.p, (uint32_t)row0, (uint32_t)row1, (uint32_t)nb, K, slot_stride,
-                   use_lists ? (const u64*)S.d_sxstat.p : (const u64*)nullptr, cap_words, slot16 ? 1 : 0, slot16 ? e->sx_ovf_now : (uint32_t*)nullptr);
+    return FSK_OK;
+}
+
+// The end of every form: the diagonal's combo-independent part (the streams and the atomics carry the rest), then the
+// batch is done with K.
+int sx_finish(const SxBatch& c, const u64* batch_stat, u64 cap_words) {
+    fsk_engine* e = c.e;
+    if (c.row1 > c.row0)
+        FSK_LAUNCH(fsk::k_sx_diag_windows, dim3((uint32_t)((c.row1 - c.row0 + 255) / 256), c.slot_stride ? c.nb : 1), dim3(256), 0, c.stream,
+                   (const uint32_t*)e->d_fstart.p, (uint32_t)c.row0, (uint32_t)c.row1, (uint32_t)c.nb, c.K, c.slot_stride, batch_stat, cap_words,
+                   c.slot16 ? 1 : 0, c.slot16 ? e->sx_ovf_now : (uint32_t*)nullptr);
     e->st.launches += 1;
-    if (k_done) FSK_HIP(hipEventRecord(k_done, stream));
-    e->toc(&e->st.ms_pairs, stream);
+    if (c.k_done) FSK_HIP(hipEventRecord(c.k_done, c.stream));
+    e->toc(&e->st.ms_pairs, c.stream);
     FSK_HIP(hipGetLastError());
     return FSK_OK;
+}
+
+// The batch's pair and word totals: waited for, the streams then sized exactly — or, under a guard, the words that size the
+// parts while the kernels read the true count. Closes ms_segment and opens ms_pairs.
+int sx_word_count(const SxBatch& c, u64* words, u64* cap_words) {
+    fsk_engine* e = c.e;
+    *words = 0;
+    *cap_words = ~(u64)0;
+    if (c.guard_cap != 0) {
+        *words = c.form == 0 ? std::max<u64>(1, std::min(e->sx_words_of(c.nrec), c.guard_cap)) : 0;  // (sizes the parts; the kernels read the true offsets)
+        *cap_words = c.guard_cap;
+    } else {
+        FSK_HIP(hipStreamSynchronize(c.stream));  // the update streams are sized exactly
+        e->u_extra += c.stat_pin[0];
+        *words = c.stat_pin[1];
+        e->sx_saw(*words, c.nrec);
+        e->sx_saw_pairs(c.stat_pin[0], c.nrec);
+    }
+    e->toc(&e->st.ms_segment, c.stream);
+    e->tic(c.stream);
+    return FSK_OK;
+}
+
+// The 64-bit atomics: k_sx_emit adds every word into K itself.
+int sx_emit_atomics(const SxBatch& c, u64 cap_words) {
+    fsk_engine* e = c.e;
+    if (c.k_wait) FSK_HIP(hipStreamWaitEvent(c.stream, c.k_wait, 0));
+    sx_emit(c, sx_owner_bands(c), true, ~(u64)0);
+    e->st.launches += 1;
+    return sx_finish(c, nullptr, cap_words);
+}
+
+// Form 1, the 64-bit atomics: the entries, the batch's totals (k_sx_stat_sum), the direct emit.
+template <typename RecT>
+int sx_update_atomics(const SxBatch& c) {
+    fsk_engine* e = c.e;
+    sx_seg_write<RecT>(c, sx_owner_bands(c));
+    c.stat_pin[0] = c.stat_pin[1] = 0;
+    e->st.launches += 3;
+    FSK_LAUNCH(fsk::k_sx_stat_sum, dim3(32), dim3(256), 0, c.stream, (const u64*)c.S->d_tile_stat.p, c.ntiles, c.S->d_sxstat.p, c.stat_pin);
+    e->st.launches += 1;
+    u64 words = 0, cap_words = 0;
+    const int rc = sx_word_count(c, &words, &cap_words);
+    if (rc) return rc;
+    if (c.slot_stride != 0) return FSK_RETRY_UNGROUPED;  // (nothing of this batch has touched K yet)
+    return sx_emit_atomics(c, cap_words);
+}
+
+// Form 0, the owner bands: the entries, the stream offsets, the word count; then k_sx_emit into the bands' streams and
+// k_sx_consume — or, for a batch of more words than one stream addresses, the 64-bit atomics.
+template <typename RecT>
+int sx_update_bands(const SxBatch& c) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    sx_seg_write<RecT>(c, sx_owner_bands(c));
+    c.stat_pin[0] = c.stat_pin[1] = 0;
+    e->st.launches += 3;
+    sx_stream_offsets(c, c.OC);
+    e->st.launches += 3;
+    u64 words = 0, cap_words = 0;
+    int rc = sx_word_count(c, &words, &cap_words);
+    if (rc) return rc;
+    if (words >= e->sx_max_words()) {
+        if (c.slot_stride != 0) return FSK_RETRY_UNGROUPED;  // (nothing of this batch has touched K yet)
+        return sx_emit_atomics(c, cap_words);
+    }
+    if (words > 0 || c.slot_stride != 0) {
+        if (!c.guard_cap && (size_t)words > S.d_ulist.cap)  // (grown with headroom: the batches of a pass differ by a few percent)
+            FSK_HIP(S.d_ulist.reserve((size_t)std::max<u64>(1, words + words / 4)));
+        sx_emit(c, sx_owner_bands(c), false, cap_words);
+        rc = sx_consume(c, words, cap_words);
+        if (rc) return rc;
+        e->st.launches += 2;
+    } else if (c.k_wait) {
+        FSK_HIP(hipStreamWaitEvent(c.stream, c.k_wait, 0));
+    }
+    return sx_finish(c, S.d_sxstat.p, cap_words);
+}
+
+// One pass of the two-level form, its word count known: k_sx_emit by band, the bands' streams cut into tiles (k_sx_parts),
+// split by sub-band (k_sxb_count / _scan / _scatter; the descriptor records likewise) and summed in LDS (k_sxb_consume).
+int sx_blocks_pass(SxBatch& c, const SxPass& P, const SxBands& bands, u64 words) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    hipStream_t stream = c.stream;
+    const uint32_t Op = P.n_owners;
+    if ((size_t)words > S.d_ulist.cap) FSK_HIP(S.d_ulist.reserve((size_t)(words + words / 8)));
+    if ((size_t)words > S.d_ulist2.cap) FSK_HIP(S.d_ulist2.reserve((size_t)(words + words / 8)));
+    const size_t nsub = (size_t)Op * P.submax;
+    FSK_HIP(S.d_subcnt.reserve(nsub));
+    FSK_HIP(S.d_suboff.reserve(nsub));
+    FSK_HIP(S.d_subcur.reserve(nsub));
+    FSK_HIP(hipMemsetAsync(S.d_subcnt.p, 0, nsub * sizeof(uint32_t), stream));
+    if (c.k_wait) { FSK_HIP(hipStreamWaitEvent(stream, c.k_wait, 0)); c.k_wait = nullptr; }
+    sx_emit(c, bands, false, ~(u64)0);
+    // (persistent launches: two workgroups of 1024 threads a CU walk the tiles of the bands' streams in contiguous chunks)
+    const uint32_t n_tiles_max = Op + (uint32_t)((words + fsk::SXB_TILE - 1) / fsk::SXB_TILE);
+    const uint32_t n_split = std::min<uint32_t>(n_tiles_max, 2u * (uint32_t)std::max(1, e->n_cu));
+    const uint32_t* const w_off = (const uint32_t*)S.d_list_off.p + (c.desc ? Op : 0u);  // where the bands' word streams start (behind the descriptors')
+    FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, stream, w_off, Op, (uint32_t)fsk::SXB_TILE, S.d_part_base.p,
+               (const u64*)S.d_sxstat.p, ~(u64)0, 0u, (uint32_t*)nullptr, 0xffffffffu, 1u);
+    FSK_LAUNCH(fsk::k_sxb_count, dim3(n_split), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_ulist.p, w_off,
+               (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcnt.p);
+    FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_subcnt.p, w_off, P.submax,
+               S.d_suboff.p, S.d_subcur.p, 0);
+    if (c.desc) {  // the descriptor records by (band, sub-band): count, scan, scatter (into the head of the second buffer, as in the first)
+        FSK_HIP(S.d_dsubcnt.reserve(nsub));
+        FSK_HIP(S.d_dsuboff.reserve(nsub));
+        FSK_HIP(S.d_dsubcur.reserve(nsub));
+        FSK_HIP(hipMemsetAsync(S.d_dsubcnt.p, 0, nsub * sizeof(uint32_t), stream));
+        const dim3 dgrid((uint32_t)std::max(1, 4 * e->n_cu / (int)std::max(1u, Op)) + 1u, Op);
+        FSK_LAUNCH(fsk::k_sxb_drecords<false>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
+                   S.d_dsubcnt.p, (uint4*)nullptr);
+        FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_dsubcnt.p, (const uint32_t*)S.d_list_off.p,
+                   P.submax, S.d_dsuboff.p, S.d_dsubcur.p, 2);
+        FSK_LAUNCH(fsk::k_sxb_drecords<true>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
+                   S.d_dsubcur.p, reinterpret_cast<uint4*>(S.d_ulist2.p));
+        e->st.launches += 3;
+    }
+    // (workgroups of 256 threads, three a CU by their LDS)
+    FSK_LAUNCH(fsk::k_sxb_scatter<256>, dim3(std::min<uint32_t>(n_tiles_max, 3u * (uint32_t)std::max(1, e->n_cu))), dim3(256), 0, stream,
+               (const uint32_t*)S.d_ulist.p, w_off, (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcur.p, S.d_ulist2.p);
+    // (a block of 2^13 cells and fewer: workgroups of 512 threads, four a CU)
+    const size_t lds_sub = sizeof(uint32_t) << P.sub_shift;
+    auto k_cs = P.sub_shift <= 13 ? fsk::k_sxb_consume<512> : fsk::k_sxb_consume<1024>;
+    FSK_HIP(fsk_hw::allow_dynamic_lds(k_cs, lds_sub));
+    FSK_LAUNCH(k_cs, dim3(P.submax, Op), dim3(P.sub_shift <= 13 ? 512u : 1024u), lds_sub, stream, (const uint32_t*)S.d_ulist2.p,
+               (const uint32_t*)S.d_suboff.p, (const uint32_t*)S.d_subcnt.p, (const uint32_t*)e->d_blk_r0.p, P.pb, P.sub_shift, P.submax, c.K,
+               c.desc ? reinterpret_cast<const uint4*>(S.d_ulist2.p) : (const uint4*)nullptr, (const uint32_t*)S.d_dsuboff.p,
+               (const uint32_t*)S.d_dsubcnt.p, (const void*)S.d_E.p, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
+    e->st.launches += 6;
+    FSK_HIP(hipStreamSynchronize(stream));  // (the next pass overwrites the band table, the entries' unit marks and the streams)
+    return FSK_OK;
+}
+
+// Form 2, the two-level blocks (fsk_sparse_blocks.inc): passes over disjoint row ranges, each sized exactly (a pass is
+// milliseconds of work: the wait for its word count does not show). A range that does not fit one pass — more cells than
+// 2^32 or than its bands cover, more words than 32-bit offsets address — is halved by cells.
+template <typename RecT>
+int sx_update_blocks(SxBatch& c) {
+    fsk_engine* e = c.e;
+    SxScratch& S = *c.S;
+    hipStream_t stream = c.stream;
+    const u64 pass_words = e->tune.blocks_pass_words > 0 ? (u64)e->tune.blocks_pass_words : ((u64)1 << 31);
+    const u64 total_cells = (u64)e->N * ((u64)e->N + 1) / 2;
+    u64* const pin = c.stat_pin;  // (pinned host memory the device writes: a pass's totals land there, the batch's are summed here)
+    pin[0] = pin[1] = 0;
+    e->toc(&e->st.ms_segment, stream);
+    e->tic(stream);
+    std::vector<std::pair<int64_t, int64_t>> todo;
+    todo.emplace_back(c.row0, c.row1);
+    u64 batch_pairs = 0;  // (the passes' += in all: what decides about descriptors for the batches that follow)
+    bool first_pass = true;
+    while (!todo.empty()) {
+        const int64_t ra = todo.back().first, rb = todo.back().second;
+        todo.pop_back();
+        if (rb <= ra) continue;
+        auto halve = [&]() {  // by cells: the row whose first cell is the middle one
+            const u64 ca = (u64)ra * ((u64)ra + 1) / 2, cb = (u64)rb * ((u64)rb + 1) / 2, mid = ca + (cb - ca) / 2;
+            int64_t lo = ra + 1, hi = rb - 1;
+            while (lo < hi) {
+                const int64_t m = (lo + hi) / 2;
+                if ((u64)m * ((u64)m + 1) / 2 < mid) lo = m + 1; else hi = m;
+            }
+            todo.emplace_back(lo, rb);  // (the lower rows first: the stack pops them next)
+            todo.emplace_back(ra, lo);
+        };
+        SxPass P;
+        // (what the range is expected to emit, by its share of the triangle: a range that would overflow a pass is not tried)
+        const u64 cells = (u64)rb * ((u64)rb + 1) / 2 - (u64)ra * ((u64)ra + 1) / 2;
+        const bool too_many = e->sx_wpr != 0 && rb - ra > 1 &&
+                              (double)e->sx_words_of(c.nrec) * ((double)cells / (double)std::max<u64>(1, total_cells)) > 0.9 * (double)pass_words;
+        if (too_many || !blocks_plan_pass(e, ra, rb, &P)) {
+            if (rb - ra <= 1) return e->fail(FSK_EUNSUPPORTED, "sparse dataflow: row %lld does not fit one pass of the two-level form", (long long)ra);
+            halve();
+            continue;
+        }
+        const uint32_t Op = P.n_owners;
+        {   // (a pass of ONE row longer than blocks_max_bands bands cover has more bands than that — up to SX_MAX_OWNERS —: the
+            // count matrix and the offsets by this pass's own bands; found by tools/stress_parity.py's blocks cases as a
+            // memory fault at N = 6500 with seven bands of 2^9 cells a pass. The previous pass has been waited for.)
+            const size_t cols = (size_t)(c.desc ? 2u : 1u) * std::max(Op, c.O);
+            FSK_HIP(S.d_ucount.reserve(cols * c.ntiles));
+            FSK_HIP(S.d_uchunk.reserve(cols * c.nchunks));
+            FSK_HIP(S.d_utot.reserve(cols));
+            FSK_HIP(S.d_list_off.reserve(cols + 1));
+            FSK_HIP(S.d_part_base.reserve((size_t)std::max(Op, c.O) + 2));
+        }
+        FSK_HIP(e->d_blk_r0.reserve((size_t)fsk::SX_MAX_OWNERS + 1));
+        // (the previous pass has been waited for: nothing reads the table any more)
+        FSK_HIP(hipMemcpy(e->d_blk_r0.p, P.r0.data(), P.r0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (!first_pass) FSK_HIP(hipMemsetAsync(S.d_sxstat.p, 0, 3 * sizeof(u64), stream));  // (the first pass: zeroed by the extraction kernel)
+        first_pass = false;
+        const uint32_t maxprod = (1u << P.pb) - 1u;
+        const SxBands bands{(const uint32_t*)e->d_blk_r0.p, P.t, Op, (uint32_t)ra, (uint32_t)rb, maxprod, maxprod / std::max<uint32_t>(1u, e->maxW),
+                            P.pb, P.own_base, P.sub_shift};
+        pin[0] = pin[1] = 0;
+        sx_seg_write<RecT>(c, bands);
+        sx_stream_offsets(c, c.desc ? 2u * Op : Op);  // (columns: descriptor streams first, then the words')
+        e->st.launches += 4;
+        FSK_HIP(hipStreamSynchronize(stream));
+        const u64 pairs = pin[0], words = pin[1];
+        if (words >= pass_words && rb - ra > 1) {  // (does not fit 32-bit offsets with room to spare: the halves, each from its own count)
+            halve();
+            continue;
+        }
+        if (words >= ((u64)1 << 32))
+            return e->fail(FSK_EUNSUPPORTED, "sparse dataflow: row %lld alone emits %llu update words a batch", (long long)ra, (unsigned long long)words);
+        e->u_extra += pairs;
+        batch_pairs += pairs;
+        e->sx_passes += 1;
+        if (e->trace())
+            fprintf(stderr, "[fsk] sparse blocks: pass rows [%lld, %lld), %u bands of 2^%d cells, %u sub-bands a band, %d product bits, %llu words\n",
+                    (long long)ra, (long long)rb, Op, P.t, P.submax, P.pb, (unsigned long long)words);
+        if (words == 0) continue;
+        const int rc = sx_blocks_pass(c, P, bands, words);
+        if (rc) return rc;
+        e->sx_saw(words * std::max<u64>(1, total_cells / std::max<u64>(1, cells)), c.nrec);  // (words per record as if the whole triangle emitted at this rate)
+    }
+    if (c.k_wait) FSK_HIP(hipStreamWaitEvent(stream, c.k_wait, 0));
+    const int rc = sx_finish(c, nullptr, ~(u64)0);
+    if (rc) return rc;
+    pin[0] = pin[1] = 0;  // (every pass has been added to u_extra already)
+    e->sx_saw_pairs(batch_pairs, c.nrec);
+    return FSK_OK;
+}
+
+// One batch of combos: extract, sort, segments, then the update stage of the batch's form (the arguments: SxBatch).
+template <typename RecT>
+int sparse_batch(fsk_engine* e, const int32_t* combos, int nb, u64* K, int64_t row0, int64_t row1, u64 slot_stride,
+                 unsigned char* pos_pin, u64* stat_pin, u64 guard_cap, int lane, size_t pos_off = 0, hipEvent_t k_wait = nullptr,
+                 hipEvent_t k_done = nullptr) {
+    SxBatch c{e, &e->sxs[lane], lane ? e->lane_stream : e->stream, combos, nb, K, row0, row1, slot_stride, pos_pin, stat_pin, guard_cap,
+              pos_off, k_wait, k_done};
+    int rc = sx_batch_begin<RecT>(c);
+    if (rc || c.nrec == 0) return rc;
+    rc = sx_extract<RecT>(c);
+    if (rc) return rc;
+    e->tic(c.stream);
+    RecT* rec[2] = {(RecT*)c.S->d_keys[0].p, (RecT*)c.S->d_keys[1].p};
+    int cur = 0;
+    rc = sx_sort<RecT>(e, *c.S, c.stream, rec, c.nfeat, c.tps, (uint32_t)nb, e->sx_sb, c.keybits, &cur);
+    if (rc) return rc;
+    e->toc(&e->st.ms_sort, c.stream);
+    e->st.sort_records += c.nrec;
+    e->st.sort_passes = (c.keybits + 7) / 8;
+    c.sorted = rec[cur];
+    rc = sx_segment<RecT>(c);
+    if (rc) return rc;
+    switch (c.form) {
+        case 0: return sx_update_bands<RecT>(c);
+        case 2: return sx_update_blocks<RecT>(c);
+        default: return sx_update_atomics<RecT>(c);
+    }
 }
 
 int ensure_featseq(fsk_engine* e) {
@@ -910,9 +981,9 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
                    hipEvent_t k_done = nullptr) {
         // (slot triangles are u32 arrays, slot_stride cells apart)
         u64* Kb = slot_stride ? reinterpret_cast<u64*>(reinterpret_cast<uint32_t*>(K) + (u64)s * slot_stride) : K;
-        return recbits <= 32   ? sparse_batch<uint32_t>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done)
-               : recbits <= 64 ? sparse_batch<u64>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done)
-                               : sparse_batch<u128>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done);
+        if (recbits <= 32) return sparse_batch<uint32_t>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done);
+        if (recbits <= 64) return sparse_batch<u64>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done);
+        return sparse_batch<u128>(e, combos + s, nb, Kb, row0, row1, slot_stride, pos_pin, stat_pin, guard, ln, pos_off, k_wait, k_done);
     };
     e->sx_slot16_used = false;
     if (defer >= 0) {
