@@ -75,7 +75,8 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_combo_positions", "fsk_stream_wait_engine", "fsk_engine_wait_stream", "fsk_read_fasta", "fsk_sequential_sum",
            "fsk_run_chains", "fsk_get_kernel_sum_device", "fsk_set_kernel_sum_device", "fsk_create_multi", "fsk_get_multi_info",
            "fsk_counts_digest", "fsk_alloc_block_device", "fsk_free_device", "fsk_set_skip_test_block",
-           "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order"]
+           "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
+           "fsk_set_complement"]
 
 
 _hip_shared = False
@@ -207,6 +208,7 @@ class Library:
             "fsk_get_tuning": ([vp, C.c_char_p, C.POINTER(i64)], C.c_int),
             "fsk_tuning_keys": ([], C.c_char_p),
             "fsk_seed_order": ([C.c_uint64, i64, vp], C.c_int),
+            "fsk_set_complement": ([vp, vp, vp, i32], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -257,6 +259,32 @@ def library():
     return _default
 
 
+def complement_arrays(mapping):
+    """``{token_id: token_id}`` -> (tokens int32, complements int32) for ``fsk_set_complement``, checked as the engine
+    checks it (an involution on its domain; self-pairs allowed): ``ValueError`` otherwise. ``None`` / ``False`` / an empty
+    mapping: two empty arrays, i.e. the mode off."""
+    if mapping is None or mapping is False:
+        mapping = {}
+    if not hasattr(mapping, "items"):
+        raise ValueError("revcomp must be None, False or a mapping {token_id: token_id}")
+    pairs = []
+    for k, v in mapping.items():
+        if isinstance(k, bool) or isinstance(v, bool) or int(k) != k or int(v) != v:
+            raise ValueError("revcomp: token ids must be integers, got %r -> %r" % (k, v))
+        if not (-2 ** 31 <= int(k) < 2 ** 31 and -2 ** 31 <= int(v) < 2 ** 31):
+            raise ValueError("revcomp: token ids must fit 32 bits")
+        pairs.append((int(k), int(v)))
+    as_map = dict(pairs)
+    if len(as_map) != len(pairs):
+        raise ValueError("revcomp: a token is listed twice")
+    for k, v in pairs:
+        if v not in as_map:
+            raise ValueError("revcomp: token %d maps to %d, which is not listed" % (k, v))
+        if as_map[v] != k:
+            raise ValueError("revcomp is not an involution: %d -> %d -> %d" % (k, v, as_map[v]))
+    return (np.array([k for k, _ in pairs], dtype=np.int32), np.array([v for _, v in pairs], dtype=np.int32))
+
+
 def flatten(X):
     """Nested int sequences (or a 2-D array) -> (tokens int32, offsets int64)."""
     if isinstance(X, np.ndarray) and X.ndim == 2:
@@ -277,7 +305,7 @@ class Engine:
 
     def __init__(self, g, m, t=-1, approx=False, delta=0.025, max_iters=-1, skip_variance=False, device=0,
                  path=PATH_AUTO, profile=False, lib=None, skip_test_block=False, devices=None, collective=COLL_AUTO,
-                 bands=0, deadline_ms=0, tuning=None):
+                 bands=0, deadline_ms=0, tuning=None, revcomp=None):
         self.lib = lib or library()
         if devices is not None:
             devices = [int(d) for d in devices]
@@ -301,8 +329,15 @@ class Engine:
         self.g, self.m = g, m
         self.device = device
         self._keep = None
+        self.revcomp = False
         for key, value in (tuning or {}).items():
             self.set_tuning(key, value)
+        if revcomp is not None and revcomp is not False:
+            try:
+                self.set_complement(revcomp)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -342,6 +377,22 @@ class Engine:
 
     def set_seed(self, seed):
         self._ck(self.lib.L.fsk_set_seed(self.h, seed))
+
+    def set_complement(self, mapping):
+        """Reverse-complement mode from the next ``load_sequences`` / ``compute`` on: ``mapping`` is the involution
+        ``{token_id: token_id}`` (``FastaUtility.complement()``); ``None``, ``False`` or ``{}`` switch it off. A mapping
+        that is not one raises ``ValueError``; the engine's own check (``FSK_EINVAL``) is the same."""
+        tokens, comps = complement_arrays(mapping)
+        self.set_complement_arrays(tokens, comps)
+
+    def set_complement_arrays(self, tokens, complements):
+        """``fsk_set_complement`` as it is: two int32 arrays, checked by the engine alone."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        complements = np.ascontiguousarray(complements, dtype=np.int32)
+        if tokens.shape != complements.shape or tokens.ndim != 1:
+            raise ValueError("tokens and complements must be 1-D and of equal length")
+        self._ck(self.lib.L.fsk_set_complement(self.h, tokens.ctypes.data, complements.ctypes.data, len(tokens)))
+        self.revcomp = len(tokens) > 0
 
     # ---- staged path
     def bind_counts(self, device_ptr, n_cells, keepalive=None):
@@ -501,4 +552,6 @@ class Engine:
     def stats(self):
         s = Stats()
         self._ck(self.lib.L.fsk_get_stats(self.h, C.byref(s)))
-        return s.as_dict()
+        d = s.as_dict()
+        d["revcomp"] = self.revcomp  # (as set: in force from the next load on)
+        return d

@@ -7,7 +7,7 @@
 //   - errors raise ValueError / RuntimeError instead of printf + exit(1) (fastsk.cpp:53-58);
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
 //     NotImplementedError (they are unusable from Python in the reference as well);
-//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block), numpy and
+//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
 //   - skip_test_block (default False: compute_kernel computes the whole N x N triangle, as fastsk.cpp:30-118 does).
@@ -25,6 +25,9 @@
 #include <string>
 #include <vector>
 
+//   - revcomp (default None: off): the complement mapping {token_id: token_id} of reverse-complement mode
+//     (fsk_set_complement; FastaUtility.complement() returns it for DNA) — a k-mer is counted together with its reverse
+//     complement, as gkm-SVM / LS-GKM do; the reference has no such mode.
 #include "../../include/fastsk_amd.h"
 
 namespace py = pybind11;
@@ -119,6 +122,7 @@ class FastSK {
     int device0_ = 0;
     // skip_test_block="lazy" / None: the test x test block is left out of compute_kernel and computed only if asked for
     bool lazy_test_block_ = false, test_block_missing_ = false;
+    bool revcomp_ = false;
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
 
@@ -228,7 +232,7 @@ class FastSK {
 public:
     FastSK(int g, int m, int t, bool approx, double delta, int max_iters, bool skip_variance, int device,
            const std::string& path, py::object seed, py::object skip_test_block, py::object devices,
-           const std::string& collective, int deadline_ms) {
+           const std::string& collective, int deadline_ms, py::object revcomp) {
         fsk_config c{};
         if (skip_test_block.is_none()) lazy_test_block_ = true;
         else if (py::isinstance<py::str>(skip_test_block)) {
@@ -255,7 +259,32 @@ public:
             if (rc == FSK_EINVAL) throw py::value_error(msg);
             throw std::runtime_error(msg);
         }
-        if (!seed.is_none()) check(fsk_set_seed(h_, seed.cast<uint64_t>()));
+        try {
+            if (!seed.is_none()) check(fsk_set_seed(h_, seed.cast<uint64_t>()));
+            set_revcomp(revcomp);
+        } catch (...) {
+            fsk_destroy(h_);
+            h_ = nullptr;
+            throw;
+        }
+    }
+    // None / False: off; else a mapping {token_id: token_id} that fsk_set_complement checks (ValueError)
+    void set_revcomp(const py::object& revcomp) {
+        std::vector<int32_t> tokens, comps;
+        if (!revcomp.is_none() && !(py::isinstance<py::bool_>(revcomp) && !revcomp.cast<bool>())) {
+            if (!py::isinstance<py::dict>(revcomp)) throw py::value_error("revcomp must be None, False or a mapping {token_id: token_id}");
+            for (auto kv : revcomp.cast<py::dict>()) {
+                if (!py::isinstance<py::int_>(kv.first) || !py::isinstance<py::int_>(kv.second) || py::isinstance<py::bool_>(kv.first) ||
+                    py::isinstance<py::bool_>(kv.second))
+                    throw py::value_error("revcomp: token ids must be integers");
+                const long long a = kv.first.cast<long long>(), b = kv.second.cast<long long>();
+                if (a < INT32_MIN || a > INT32_MAX || b < INT32_MIN || b > INT32_MAX) throw py::value_error("revcomp: token ids must fit 32 bits");
+                tokens.push_back((int32_t)a);
+                comps.push_back((int32_t)b);
+            }
+        }
+        check(fsk_set_complement(h_, tokens.data(), comps.data(), (int32_t)tokens.size()));
+        revcomp_ = !tokens.empty();
     }
     ~FastSK() { fsk_destroy(h_); }
     FastSK(const FastSK&) = delete;
@@ -381,6 +410,7 @@ public:
         d["n_combos_total"] = s.n_combos_total; d["combos_done"] = s.combos_done;
         d["cell_updates"] = s.cell_updates; d["launches"] = s.launches;
         d["test_block_computed"] = computed_ && !test_block_missing_;
+        d["revcomp"] = revcomp_;
         fsk_multi_info mi;
         check(fsk_get_multi_info(h_, &mi));
         py::list devs;
@@ -409,11 +439,12 @@ PYBIND11_MODULE(_fastsk, m) {
     m.doc() = "MI355X-native gapped-k-mer kernel engine behind the FastSK Python surface";
     py::class_<FastSK>(m, "FastSK")
         .def(py::init<int, int, int, bool, double, int, bool, int, const std::string&, py::object, py::object, py::object,
-                      const std::string&, int>(),
+                      const std::string&, int, py::object>(),
              py::arg("g"), py::arg("m"), py::arg("t") = -1, py::arg("approx") = false, py::arg("delta") = 0.025,
              py::arg("max_iters") = -1, py::arg("skip_variance") = false, py::arg("device") = 0,
              py::arg("path") = "auto", py::arg("seed") = py::none(), py::arg("skip_test_block") = false,
-             py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0)
+             py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0,
+             py::arg("revcomp") = py::none())
         .def("compute_kernel", &FastSK::compute_kernel, py::arg("Xtrain"), py::arg("Xtest"))
         .def("compute_kernel_flat", &FastSK::compute_kernel_flat, py::arg("tokens").noconvert(), py::arg("offsets").noconvert(),
              py::arg("n_train"))

@@ -181,11 +181,13 @@ bool dense_is_cheaper(const fsk_engine* e) {
     // per window for every further sweep when the window keys are cached in LDS — as
     // accumulate_dense arranges when they fit — and 8e-12 s when they are recomputed; 7e-13 s per
     // (sequence, key) for zeroing and reading out the histograms)
-    DensePlan plan = dense_plan(e->maxW, e->cfg.g, e->Vq);
+    // (reverse-complement mode: nfeat and maxW count both strands; the kernel stages one strand's maxW1 windows at a time
+    // and runs without the window-key cache)
+    DensePlan plan = dense_plan(e->maxW1, e->cfg.g, e->Vq);
     double sweep_cost = 8e-12;
-    if (plan.Vcq && plan.Vcq < e->Vq && plan.CH >= e->maxW) {
-        const DensePlan p2 = dense_plan(e->maxW, e->cfg.g, e->Vq, (size_t)e->maxW * fsk::PANEL * sizeof(uint16_t));
-        if (p2.CH >= e->maxW && p2.Vcq >= 64) { plan = p2; sweep_cost = 2.6e-12; }
+    if (plan.Vcq && plan.Vcq < e->Vq && plan.CH >= e->maxW1 && !e->revcomp) {
+        const DensePlan p2 = dense_plan(e->maxW1, e->cfg.g, e->Vq, (size_t)e->maxW1 * fsk::PANEL * sizeof(uint16_t));
+        if (p2.CH >= e->maxW1 && p2.Vcq >= 64) { plan = p2; sweep_cost = 2.6e-12; }
     }
     const double sweeps = plan.Vcq ? std::ceil((double)e->Vq / plan.Vcq) : 1.0;
     // (tile kernel: 3.0e14 count-MAC/s with thousands of tiles, ~2.4e14 with few)
@@ -220,7 +222,7 @@ bool dense_is_cheaper(const fsk_engine* e) {
 }
 
 int choose_path(fsk_engine* e) {
-    bool dense_ok = e->V <= DENSE_MAX_KEYS && e->bits <= 8 && e->k <= 16 && e->Lmax < 65536 && dense_plan(e->maxW, e->cfg.g, e->Vq).CH > 0;
+    bool dense_ok = e->V <= DENSE_MAX_KEYS && e->bits <= 8 && e->k <= 16 && e->Lmax < 65536 && e->maxW < 65536 && dense_plan(e->maxW1, e->cfg.g, e->Vq).CH > 0;
     if (e->cfg.path == FSK_PATH_DENSE) {
         if (!dense_ok)
             return e->fail(FSK_EUNSUPPORTED, "dense path needs alphabet^k <= %llu and the panel histogram to fit in LDS",
@@ -466,7 +468,7 @@ void fsk_detail::one_destroy(fsk_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
     if (e->chain_stream) (void)hipStreamSynchronize(e->chain_stream);  // (variance mode may leave a dropped batch's sums running)
-    e->d_words.release(); e->d_wstart.release(); e->d_len.release(); e->d_fstart.release(); e->d_featseq.release(); e->d_win.release();
+    e->d_words.release(); e->d_wstart.release(); e->d_len.release(); e->d_fstart.release(); e->d_featseq.release(); e->d_win.release(); e->d_comp.release();
     e->d_pos.release(); e->d_allpos.release(); e->d_bsum.release(); e->d_seqblk.release(); e->K_store.release(); e->d_Kf64.release(); e->d_Khat.release(); e->d_prod.release();
     e->d_diag.release(); e->d_stage.release(); e->d_stage_u64.release(); e->d_Kslots.release(); e->d_cell_idx.release(); e->d_C4.release(); e->d_C4H.release(); e->d_rowmask.release(); e->d_flag.release(); e->d_tiletab.release(); e->d_rare.release(); e->d_rare_n.release(); e->d_common.release(); e->d_keybits.release(); e->d_lut.release(); e->d_vc.release();
     if (e->lane_stream) { (void)hipStreamSynchronize(e->lane_stream); (void)hipStreamDestroy(e->lane_stream); }
@@ -513,7 +515,34 @@ int fsk_detail::one_set_combo_order(fsk_engine* e, const int32_t* order, int32_t
     return FSK_OK;
 }
 
+// fsk_set_complement: the map is checked here and kept sorted by token; the next load packs with it
+int fsk_detail::one_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n) {
+    if (n < 0 || (n > 0 && (!tokens || !complements))) return e->fail(FSK_EINVAL, "complement map: null arrays or a negative length");
+    std::vector<std::pair<int32_t, int32_t>> map((size_t)n);
+    for (int32_t i = 0; i < n; ++i) map[(size_t)i] = {tokens[i], complements[i]};
+    std::sort(map.begin(), map.end());
+    for (size_t i = 1; i < map.size(); ++i)
+        if (map[i].first == map[i - 1].first) return e->fail(FSK_EINVAL, "complement map: token %d is listed twice", map[i].first);
+    auto find = [&](int32_t t) { return std::lower_bound(map.begin(), map.end(), std::make_pair(t, INT32_MIN)); };
+    for (const auto& tc : map) {
+        const auto back = find(tc.second);
+        if (back == map.end() || back->first != tc.second)
+            return e->fail(FSK_EINVAL, "complement map: token %d maps to %d, which is not listed", tc.first, tc.second);
+        if (back->second != tc.first)
+            return e->fail(FSK_EINVAL, "complement map is not an involution: %d -> %d -> %d", tc.first, tc.second, back->second);
+    }
+    e->rc_tokens.resize(map.size());
+    e->rc_comps.resize(map.size());
+    for (size_t i = 0; i < map.size(); ++i) { e->rc_tokens[i] = map[i].first; e->rc_comps[i] = map[i].second; }
+    return FSK_OK;
+}
+
 extern "C" {
+
+int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n) {
+    if (!e) return FSK_EINVAL;
+    return e->group ? group_set_complement(e, tokens, complements, n) : one_set_complement(e, tokens, complements, n);
+}
 
 int fsk_set_seed(fsk_engine* e, uint64_t seed) {
     if (!e) return FSK_EINVAL;
@@ -549,6 +578,9 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     tokens = tokens ? tokens + offsets[0] : tokens;
     const int64_t off0 = offsets[0];
     // ---- lengths (fastsk.cpp:32-58)
+    // reverse-complement mode: every sequence owns the windows of both its strands
+    const bool rc_on = !e->rc_tokens.empty();
+    const int64_t strands = rc_on ? 2 : 1;
     int64_t shortest_train = INT64_MAX, shortest_test = INT64_MAX, longest = 0, nfeat = 0;
     for (int64_t i = 0; i < N; ++i) {
         const int64_t len = offsets[i + 1] - offsets[i];
@@ -556,7 +588,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         if (i < n_train) shortest_train = std::min(shortest_train, len);
         else shortest_test = std::min(shortest_test, len);
         longest = std::max(longest, len);
-        nfeat += len >= g ? len - g + 1 : 0;
+        nfeat += len >= g ? strands * (len - g + 1) : 0;
     }
     if (g > shortest_train)
         return e->fail(FSK_ESHORT, "g cannot be longer than the shortest sequence in a dataset. g = %d, but shortest train sequence has length %lld", g, (long long)shortest_train);
@@ -584,10 +616,36 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             const int64_t len = offsets[i + 1] - offsets[i];
             len32[i] = (uint32_t)len;
             fstart[i] = fcount;
-            fcount += (uint32_t)(len - g + 1);
+            fcount += (uint32_t)(strands * (len - g + 1));
         }
         fstart[N] = fcount;
     }
+    // reverse-complement mode: `distinct` (the tokens present, ascending) becomes its closure under the map — data without
+    // a single 'g' still produce 'g' on their second strand —; a token the map does not list fails the load, named (the
+    // first one in the data: protein given to a DNA map must not be self-complemented silently)
+    auto rc_comp_of = [&](int32_t t, int32_t* out) {
+        const auto it = std::lower_bound(e->rc_tokens.begin(), e->rc_tokens.end(), t);
+        if (it == e->rc_tokens.end() || *it != t) return false;
+        *out = e->rc_comps[(size_t)(it - e->rc_tokens.begin())];
+        return true;
+    };
+    auto rc_close = [&]() -> int {
+        if (!rc_on) return FSK_OK;
+        const size_t present = distinct.size();
+        for (size_t q = 0; q < present; ++q) {
+            int32_t c = 0;
+            if (!rc_comp_of(distinct[q], &c)) {
+                int32_t first = distinct[q];
+                for (int64_t i = 0; i < total; ++i)
+                    if (!rc_comp_of(tokens[i], &c)) { first = tokens[i]; break; }
+                return e->fail(FSK_EINVAL, "token %d occurs in the sequences but not in the complement map", first);
+            }
+            distinct.push_back(c);
+        }
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        return FSK_OK;
+    };
     // sigma, bits, V from `distinct`; where every sequence's words start
     auto plan_words = [&](uint32_t* wstart, uint64_t* nwords_out) -> int {
         // (cntsrtna's radix is the dictionary size, whatever it is — shared.cpp:156-191 — and its keys are tuples, never a
@@ -658,11 +716,17 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             [&] {
                 for (int t = 0; t < nt; ++t) all_small = all_small && small[(size_t)t];
                 if (!all_small) return;
+                int64_t cnt[256];
                 for (int v = 0; v < 256; ++v) {
-                    int64_t c = 0;
-                    for (int t = 0; t < nt; ++t) c += hist[(size_t)t][(size_t)v];
-                    if (c) { lut[v] = (uint8_t)distinct.size(); sym_freq[distinct.size()] = c; distinct.push_back(v); }
+                    cnt[v] = 0;
+                    for (int t = 0; t < nt; ++t) cnt[v] += hist[(size_t)t][(size_t)v];
+                    if (cnt[v]) distinct.push_back(v);
                 }
+                rc_mid = rc_close();
+                if (rc_mid) return;
+                if (distinct.size() > 256) { all_small = false; distinct.clear(); return; }  // (complements beyond the byte table: the general path)
+                for (size_t r = 0; r < distinct.size(); ++r)
+                    if (distinct[r] >= 0 && distinct[r] < 256) { lut[distinct[r]] = (uint8_t)r; sym_freq[r] = cnt[distinct[r]]; }
                 // staging: [words + 4][wstart N][len N][fstart N + 1]
                 std::vector<uint32_t> ws((size_t)N);
                 uint64_t nwords = 0;
@@ -718,6 +782,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             std::sort(distinct.begin(), distinct.end());
             distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
         }
+        { const int rc_cl = rc_close(); if (rc_cl) return rc_cl; }
         if (distinct.size() > sym_freq.size()) sym_freq.assign(distinct.size(), 0);
         wstart_v.resize((size_t)N);
         uint64_t nwords = 0;
@@ -746,6 +811,20 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         p_wstart = wstart_v.data();
         n_words_alloc = words_v.size();
     }
+    // the complement of every rank; a symbol's frequency over both strands is its own plus its complement's
+    std::vector<uint16_t> comp_rank;
+    if (rc_on) {
+        comp_rank.resize(distinct.size());
+        for (size_t r = 0; r < distinct.size(); ++r) {
+            int32_t c = 0;
+            (void)rc_comp_of(distinct[r], &c);
+            comp_rank[r] = (uint16_t)(std::lower_bound(distinct.begin(), distinct.end(), c) - distinct.begin());
+        }
+        std::vector<int64_t> both(sym_freq);
+        for (size_t r = 0; r < distinct.size(); ++r) both[r] = sym_freq[r] + sym_freq[comp_rank[r]];
+        sym_freq.swap(both);
+    }
+    const int64_t total_sym = strands * total;  // symbols counted, both strands
     tl_pack = tl_ms(tl0);
     // ---- commit
     // (the dense dataflow's tile table depends on the number of sequences and the train / test split alone: a set of the same
@@ -755,7 +834,9 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     e->pairs = N * (N + 1) / 2;
     e->sigma = sigma; e->bits = bits; e->V = V; e->Vq = (uint32_t)((V + 3) / 4);
     e->Lmax = (uint32_t)longest; e->Lmin = (uint32_t)std::min(shortest_train, n_test > 0 ? shortest_test : shortest_train);
-    e->maxW = (uint32_t)(longest - g + 1);
+    e->maxW1 = (uint32_t)(longest - g + 1);
+    e->maxW = (uint32_t)strands * e->maxW1;
+    e->revcomp = rc_on;
     e->n_panels = (uint32_t)((N + fsk::PANEL - 1) / fsk::PANEL);
     e->h_len = len32; e->h_fstart = fstart; e->featseq_ready = false;
     e->prep_valid = false; e->vc_sum = 0; e->vc_n = 0;
@@ -790,7 +871,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         // space is then empty and need not be multiplied
         int64_t rarest = INT64_MAX;
         for (uint32_t r = 0; r < sigma; ++r) rarest = std::min(rarest, sym_freq[r]);
-        e->compact = sigma >= 3 && V >= 64 && V <= 4096 && rarest * 50 < total;
+        e->compact = sigma >= 3 && V >= 64 && V <= 4096 && rarest * 50 < total_sym;
         if (e->tune.compact >= 0) e->compact = e->tune.compact != 0 && V <= 4096;
         // ... and the keys that occur follow from the places of the rare symbols when those are few (g windows per place
         // and combo are marked instead of every window) and every key of common symbols can be taken as present (16
@@ -799,7 +880,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         int64_t places = 0;
         uint32_t common = 0;
         for (uint32_t r = 0; r < sigma && r < 32u; ++r) {
-            if (sym_freq[r] * 50 < total) { e->rare_mask |= 1u << r; places += sym_freq[r]; }
+            if (sym_freq[r] * 50 < total_sym) { e->rare_mask |= 1u << r; places += sym_freq[r]; }
             else ++common;
         }
         double common_keys = 1;
@@ -807,12 +888,19 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         e->compact_rare = e->compact && sigma <= 32 && common >= 1 && places > 0 && places < ((int64_t)1 << 24) &&
                           places * (int64_t)g * 8 < std::max<int64_t>(1, nfeat) && (double)nfeat >= 16.0 * common_keys;
         if (e->tune.compact_rare >= 0) e->compact_rare = e->compact && e->tune.compact_rare != 0 && sigma <= 32 && places < ((int64_t)1 << 24);
+        // (reverse-complement mode: the rare symbols' places are listed on one strand only — the marking pass over every
+        // window of both strands, k_dense_count<true, ., true>, instead)
+        if (rc_on) e->compact_rare = false;
         e->rare_places = (uint32_t)places;
     }
     FSK_HIP(e->d_words.reserve(n_words_alloc));
     FSK_HIP(e->d_wstart.reserve((size_t)N));
     FSK_HIP(e->d_len.reserve((size_t)N));
     FSK_HIP(e->d_fstart.reserve((size_t)N + 1));
+    if (rc_on) {
+        FSK_HIP(e->d_comp.reserve(comp_rank.size()));
+        FSK_HIP(hipMemcpy(e->d_comp.p, comp_rank.data(), comp_rank.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
     if (staged) {  // everything sits in pinned memory: four copies on the stream, nothing to wait for
         FSK_HIP(hipMemcpyAsync(e->d_words.p, p_words, n_words_alloc * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         FSK_HIP(hipMemcpyAsync(e->d_wstart.p, p_wstart, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));

@@ -122,33 +122,50 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     const u64 n_tiles = e->tab_n;
     const bool compact = e->compact;
     const uint32_t Vkeys = (uint32_t)e->V, Vw = (Vkeys + 31u) / 32u;
-    DensePlan plan = dense_plan(e->maxW, e->cfg.g, e->Vq, compact ? (size_t)Vkeys * 2 : 0);  // may be re-planned below
+    // (reverse-complement mode: the count kernel stages and counts one strand at a time — maxW1 windows —; maxW, which bounds
+    // a cell, counts both)
+    const uint32_t maxW1 = e->maxW1;
+    size_t extra = compact ? (size_t)Vkeys * 2 : 0;
+    DensePlan plan = dense_plan(maxW1, e->cfg.g, e->Vq, extra);  // may be re-planned below
     if (plan.CH == 0) return e->fail(FSK_EUNSUPPORTED, "dense path: LDS plan does not fit");
+    // ... and when a strand is staged in one pass, the second strand gets a staging buffer of its own behind the table, so
+    // that both are unpacked once per workgroup like the single strand is (else every sweep stages strand by strand)
+    uint32_t rc_rows = 0;
+    if (e->revcomp && plan.CH >= maxW1 && !e->tune.dense_chunk) {
+        const size_t second = (size_t)(maxW1 + e->cfg.g - 1) * fsk::PANEL;
+        const DensePlan p2 = dense_plan(maxW1, e->cfg.g, e->Vq, extra + second);
+        if (p2.CH >= maxW1) {
+            plan = p2;
+            extra += second;
+            rc_rows = maxW1 + (uint32_t)e->cfg.g - 1u;
+        }
+    }
     uint32_t CH = plan.CH;
     if (e->tune.dense_chunk) CH = std::max(1u, std::min(CH, (uint32_t)e->tune.dense_chunk));
-    size_t lds = (size_t)(CH + e->cfg.g - 1) * fsk::PANEL + (size_t)plan.Vcq * 512 + (compact ? (size_t)Vkeys * 2 : 0);
+    size_t lds = (size_t)(CH + e->cfg.g - 1) * fsk::PANEL + (size_t)plan.Vcq * 512 + extra;
     // several histogram sweeps over one staging pass: cache the window keys in LDS (u16 each) when
     // they fit next to everything else, so that only the first sweep computes them
     uint32_t kc_rows = 0;
-    if (plan.Vcq < e->Vq && CH >= e->maxW && !e->tune.dense_chunk) {
+    // (never in reverse-complement mode: the cache holds one strand's keys)
+    if (plan.Vcq < e->Vq && CH >= maxW1 && !e->tune.dense_chunk && !e->revcomp) {
         // re-plan with the cache carved out first
-        const size_t cache = (size_t)e->maxW * fsk::PANEL * sizeof(uint16_t);
-        DensePlan p2 = dense_plan(e->maxW, e->cfg.g, e->Vq, (compact ? (size_t)Vkeys * 2 : 0) + cache);
-        if (p2.CH >= e->maxW && p2.Vcq >= 64) {
+        const size_t cache = (size_t)maxW1 * fsk::PANEL * sizeof(uint16_t);
+        DensePlan p2 = dense_plan(maxW1, e->cfg.g, e->Vq, extra + cache);
+        if (p2.CH >= maxW1 && p2.Vcq >= 64) {
             plan = p2;
             CH = plan.CH;
-            kc_rows = e->maxW;
+            kc_rows = maxW1;
             lds = plan.lds;
         }
     }
-    {
-        auto k0 = fsk::k_dense_count<false, false>;
-        auto k1 = fsk::k_dense_count<false, true>;
-        auto k2 = fsk::k_dense_count<true, false>;
-        FSK_HIP(fsk_hw::allow_dynamic_lds(k0, lds));
-        FSK_HIP(fsk_hw::allow_dynamic_lds(k1, lds));
-        FSK_HIP(fsk_hw::allow_dynamic_lds(k2, lds));
-    }
+    // (function pointers: a template-id with a comma cannot pass through the launch macro)
+    auto k_count = e->revcomp ? fsk::k_dense_count<false, false, true> : fsk::k_dense_count<false, false, false>;
+    auto k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true> : fsk::k_dense_count<false, true, false>;
+    auto k_mark = e->revcomp ? fsk::k_dense_count<true, false, true> : fsk::k_dense_count<true, false, false>;
+    const uint16_t* const comp = e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr;
+    FSK_HIP(fsk_hw::allow_dynamic_lds(k_count, lds));
+    FSK_HIP(fsk_hw::allow_dynamic_lds(k_count_lut, lds));
+    FSK_HIP(fsk_hw::allow_dynamic_lds(k_mark, lds));
     if (compact) {
         FSK_HIP(e->d_keybits.reserve((size_t)chunk * Vw));
         FSK_HIP(e->d_lut.reserve((size_t)chunk * Vkeys));
@@ -194,10 +211,6 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             const int n_chunks = (nb + slots_per_chunk - 1) / slots_per_chunk;
             e->tic();
             const dim3 cgrid(panels_pad, n_chunks);
-            // (function pointers: a template-id with a comma cannot pass through the launch macro)
-            auto k_mark = fsk::k_dense_count<true, false>;
-            auto k_count_lut = fsk::k_dense_count<false, true>;
-            auto k_count = fsk::k_dense_count<false, false>;
             if (compact) {  // which keys occur per combo -> rank tables -> compacted panels
                 if (e->compact_rare) {  // from the places of the rare symbols (listed once per set of sequences)
                     const uint32_t cap = std::max(1u, e->rare_places);
@@ -221,13 +234,13 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                 } else {
                     FSK_HIP(hipMemsetAsync(e->d_keybits.p, 0, (size_t)nb * Vw * sizeof(uint32_t), e->stream));
                     FSK_LAUNCH(k_mark, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
-                               e->k, e->sigma, e->Vq, plan.Vcq, e->maxW, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows);
+                               e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
+                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows, comp, rc_rows);
                 }
                 FSK_LAUNCH(fsk::k_dense_keylut, dim3(nb), dim3(256), 0, e->stream, e->d_keybits.p, Vkeys, e->d_lut.p, e->d_vc.p);
                 FSK_LAUNCH(k_count_lut, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
-                           e->k, e->sigma, e->Vq, plan.Vcq, e->maxW, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows);
+                           e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows, comp, rc_rows);
                 h_vc.resize((size_t)nb);
                 FSK_HIP(hipMemcpyAsync(h_vc.data(), e->d_vc.p, (size_t)nb * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
                 FSK_HIP(hipStreamSynchronize(e->stream));
@@ -241,8 +254,8 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                 }
             } else {
                 FSK_LAUNCH(k_count, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
-                           e->k, e->sigma, e->Vq, plan.Vcq, e->maxW, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows);
+                           e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows, comp, rc_rows);
             }
             e->toc(&e->st.ms_count);
             e->st.count_launches += 1;

@@ -205,6 +205,13 @@ struct fsk_engine {
     int win_words = 0;
     std::vector<uint32_t> h_len, h_fstart;
     bool featseq_ready = false;
+    // reverse-complement mode (fsk_set_complement): the map as it was set, sorted by token (empty: off); what the LOADED
+    // sequences were packed with — revcomp, the complement of every rank (d_comp, beside the packed sequences, which hold
+    // one strand only) — and the windows of ONE strand of the longest sequence. maxW, nfeat, fstart count both strands.
+    std::vector<int32_t> rc_tokens, rc_comps;
+    bool revcomp = false;
+    uint32_t maxW1 = 0;
+    DevBuf<uint16_t> d_comp;
 
     // combos
     std::vector<uint8_t> all_pos;  // [ncomb][k]
@@ -457,6 +464,7 @@ int one_accumulate_rows(fsk_engine* e, const int32_t* combos, int32_t n, int64_t
 int one_synchronize(fsk_engine* e);
 int one_finalize(fsk_engine* e);
 int one_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
+int one_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 int one_get_stats(fsk_engine* e, fsk_stats* out);
 void one_destroy(fsk_engine* e);
 // the combos the approx modes accumulate as plain integer sums (skip_variance): fastsk_kernel.cpp:148,275
@@ -472,6 +480,7 @@ int group_finalize(fsk_engine* e);
 int group_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test);
 int group_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
 int group_set_seed(fsk_engine* e, uint64_t seed);
+int group_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 int group_get_stats(fsk_engine* e, fsk_stats* out);
 int group_set_skip_test_block(fsk_engine* e, int32_t skip);
 int group_set_tuning(fsk_engine* e, const char* key, int64_t value, std::string& err);

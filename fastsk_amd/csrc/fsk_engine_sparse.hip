@@ -419,9 +419,10 @@ int sx_extract(const SxBatch& c) {
             FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, nfeat, tps, nb, rec, S.d_blockhist.p, dmask, zeroed_stats);
         }, ww == 2, small, four);
     } else {
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_sx_extract<RecT>), dim3(tps, nb), dim3(256), 0, c.stream, e->view(), e->d_featseq.p,
-                   e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S.d_blockhist.p, dmask, c.ids, zeroed_stats,
-                   c.by_id ? 1 : 0, e->sx_symbits);
+        auto k = e->revcomp ? fsk::k_sx_extract<RecT, true> : fsk::k_sx_extract<RecT, false>;
+        FSK_LAUNCH(k, dim3(tps, nb), dim3(256), 0, c.stream, e->view(), (const uint32_t*)e->d_featseq.p,
+                   (const uint32_t*)e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S.d_blockhist.p, dmask, c.ids, zeroed_stats,
+                   c.by_id ? 1 : 0, e->sx_symbits, e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr, e->cfg.g);
     }
     e->toc(&e->st.ms_extract, c.stream);
     e->st.launches += 1;
@@ -859,12 +860,11 @@ int ensure_featseq(fsk_engine* e) {
     if (e->win_words && e->nfeat > 0) {
         FSK_HIP(e->d_win.reserve((size_t)e->nfeat * e->win_words));
         const dim3 grid((uint32_t)((e->nfeat + 255) / 256));
-        if (e->win_words == 2)
-            FSK_LAUNCH(fsk::k_sx_windows<2>, grid, dim3(256), 0, e->stream, e->view(), (const uint32_t*)e->d_featseq.p,
-                       (const uint32_t*)e->d_fstart.p, (uint32_t)e->nfeat, e->cfg.g, e->d_win.p);
-        else
-            FSK_LAUNCH(fsk::k_sx_windows<4>, grid, dim3(256), 0, e->stream, e->view(), (const uint32_t*)e->d_featseq.p,
-                       (const uint32_t*)e->d_fstart.p, (uint32_t)e->nfeat, e->cfg.g, e->d_win.p);
+        // (reverse-complement mode: the second half of a sequence's windows are its other strand's)
+        auto k = e->win_words == 2 ? (e->revcomp ? fsk::k_sx_windows<2, true> : fsk::k_sx_windows<2, false>)
+                                   : (e->revcomp ? fsk::k_sx_windows<4, true> : fsk::k_sx_windows<4, false>);
+        FSK_LAUNCH(k, grid, dim3(256), 0, e->stream, e->view(), (const uint32_t*)e->d_featseq.p, (const uint32_t*)e->d_fstart.p,
+                   (uint32_t)e->nfeat, e->cfg.g, e->d_win.p, e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr);
     }
     FSK_HIP(hipStreamSynchronize(e->stream));  // (every lane's kernels read both arrays)
     e->featseq_ready = true;

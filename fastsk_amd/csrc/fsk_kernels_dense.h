@@ -145,13 +145,19 @@ __device__ __forceinline__ void pack_count_row(const uint16_t* hist16, uint32_t 
 // MARK = true only records, per combo, which of the sigma^k keys occur anywhere (keybits);
 // k_dense_keylut turns that into a rank table, and the counting launch (LUT = true) maps every
 // key through it, so panels and the tile kernel only carry the keys that exist (vc[slot] of them).
-template <bool MARK, bool LUT>
+//
+// RC (reverse-complement mode): a strand loop around the staging chunks. The second strand is staged as
+// comp[x[len - 1 - p]] and counted into the SAME histogram with the same kept positions, so panels, rowmask, the hi plane
+// and the overflow flag carry two-strand counts and nothing after this kernel knows. rc_rows != 0: the second strand has
+// sym_rows = rc_rows rows of its own behind the table (CH >= max_win: both strands are unpacked once per workgroup);
+// rc_rows == 0: the one buffer is re-staged strand by strand. No window-key cache in this mode (kc_rows = 0).
+template <bool MARK, bool LUT, bool RC>
 __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, uint32_t sigma, uint32_t Vq,
                                                      uint32_t Vcq, uint32_t max_win, uint32_t CH, const uint8_t* combo_pos,
                                                      int n_slots, int slots_per_chunk, uint32_t* C4, uint32_t* C4H,
                                                      uint32_t* rowmask, uint32_t nst, uint32_t* overflow_flag, uint32_t V,
                                                      const uint16_t* lut_g, const uint16_t* vc, uint32_t* keybits,
-                                                     uint32_t kc_rows) {
+                                                     uint32_t kc_rows, const uint16_t* comp, uint32_t rc_rows) {
     // Counts leave as two 4-bit planes, count = lo + 16 * hi (8 keys per dword): C4 holds lo and
     // is all the tile kernel multiplies for almost every key; C4H holds hi, zero unless a k-mer
     // occurs more than 15 times in one sequence (poly-A, runs of 'n'); rowmask[panel][slot][..]
@@ -170,6 +176,8 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
     uint16_t* lut = reinterpret_cast<uint16_t*>(smem + (size_t)sym_rows * PANEL + (size_t)Vcq * 512);
     // window-key cache [kc_rows][64] u16 behind the table (kc_rows = max_win when the host enabled it)
     uint16_t* kcache = lut + (LUT ? V : 0u);
+    uint8_t* symT2 = RC && rc_rows != 0u ? reinterpret_cast<uint8_t*>(kcache) : symT;  // (RC: the place of the cache is the second strand's)
+    constexpr int STRANDS = RC ? 2 : 1;
     const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
     const uint32_t panel = blockIdx.x;
     const uint32_t seq = panel * PANEL + r;
@@ -206,17 +214,27 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
             const uint32_t hist_dwords = MARK ? Vw : 4u * Vcq * 32u;
             __syncthreads();  // previous read-out finished
             for (uint32_t i = tid; i < hist_dwords; i += 256) hist[i] = 0u;
-            for (uint32_t cb = 0; cb < max_win; cb += CH) {
-                if (!single || (slot == slot0 && kc0 == 0)) {
-                    __syncthreads();  // everyone is done with the previous chunk's symbols
-                    for (uint32_t p = w; p < sym_rows; p += 4)
-                        symT[p * PANEL + r] = cb + p < len ? (uint8_t)fetch_sym(S.words, wbase, cb + p, S.bits) : (uint8_t)0;
+            for (int strand = 0; strand < STRANDS; ++strand) {
+                uint8_t* const sy = RC && strand ? symT2 : symT;
+                const bool kept = !RC || rc_rows != 0u;  // a strand's staged symbols outlive the other strand's pass
+                for (uint32_t cb = 0; cb < max_win; cb += CH) {
+                    if (!single || !kept || (slot == slot0 && kc0 == 0)) {
+                        __syncthreads();  // everyone is done with the previous chunk's symbols
+                        for (uint32_t p = w; p < sym_rows; p += 4) {
+                            uint32_t sym = 0u;
+                            if (cb + p < len) {
+                                if (RC && strand) sym = comp[fetch_sym(S.words, wbase, len - 1u - (cb + p), S.bits)];
+                                else sym = fetch_sym(S.words, wbase, cb + p, S.bits);
+                            }
+                            sy[p * PANEL + r] = (uint8_t)sym;
+                        }
+                    }
+                    __syncthreads();  // symbols staged, histogram zeroed, table loaded
+                    const uint32_t hi = cb + CH < max_win ? cb + CH : max_win;
+                    const int kmode = (MARK || kc_rows == 0u) ? 0 : (kc0 == 0u ? 1 : 2);
+                    count_windows_k<MARK, LUT>(sy, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half, key_lo, key_n,
+                                               kcache, kmode);
                 }
-                __syncthreads();  // symbols staged, histogram zeroed, table loaded
-                const uint32_t hi = cb + CH < max_win ? cb + CH : max_win;
-                const int kmode = (MARK || kc_rows == 0u) ? 0 : (kc0 == 0u ? 1 : 2);
-                count_windows_k<MARK, LUT>(symT, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half, key_lo, key_n,
-                                           kcache, kmode);
             }
             __syncthreads();
             if (MARK) {  // merge this panel's key bitmap into the combo's

@@ -760,6 +760,17 @@ int group_set_seed(fsk_engine* lead, uint64_t seed) {
     return FSK_OK;
 }
 
+int group_set_complement(fsk_engine* lead, const int32_t* tokens, const int32_t* complements, int32_t n) {
+    for (fsk_engine* e : lead->group->member) {
+        const int rc = one_set_complement(e, tokens, complements, n);
+        if (rc) {
+            if (e != lead) lead->err = e->err;
+            return rc;
+        }
+    }
+    return FSK_OK;
+}
+
 int group_set_skip_test_block(fsk_engine* lead, int32_t skip) {
     for (fsk_engine* e : lead->group->member) {
         e->cfg.skip_test_block = skip ? 1 : 0;

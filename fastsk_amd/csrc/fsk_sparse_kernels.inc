@@ -149,12 +149,14 @@ __device__ __forceinline__ int block_excl_maxscan_256(int v, int* tmp, int* tota
 // The kept positions of slot s: combo_pos[s][k] (uploaded per batch) — or, for a batch of at most 16
 // combos (variance mode), row ids.id[s] of the resident table of all combos (by_id): the
 // batch then needs no copy command at all; this kernel also zeroes the batch's counters (batch_stats).
+// RC (reverse-complement mode): a sequence owns 2 (len - g + 1) features; feature j of its second half is window
+// j - (len - g + 1) of rc(x), whose symbol c is comp[x[len - 1 - (j - (len - g + 1)) - c]].
 struct SxIds { int32_t id[16]; };
-template <typename RecT>
+template <typename RecT, bool RC>
 __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* feat_seq, const uint32_t* fstart, uint32_t nfeat, uint32_t tps,
                                                     int k, uint32_t sigma, int sb, const uint8_t* combo_pos, RecT* rec,
                                                     uint32_t* blockhist, uint32_t dmask, SxIds ids, u64* batch_stats, int by_id,
-                                                    int symbits) {
+                                                    int symbits, const uint16_t* comp, int g) {
     // (symbits != 0: a k-mer space beyond 2^62 — the key is the symbols' bit fields side by side, which a 128-bit record holds)
     typedef typename std::conditional<sizeof(RecT) == 16, RecT, u64>::type key_t;
     __shared__ uint32_t h[256];
@@ -174,6 +176,7 @@ __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* f
     static_assert(SX_ITEMS % EX_B == 0, "records per thread");
     for (int it0 = 0; it0 < SX_ITEMS; it0 += EX_B) {
         uint32_t seq[EX_B], j[EX_B], wbase[EX_B];
+        bool back[EX_B];  // (RC) the feature is a window of the second strand; j is then the place of its FIRST symbol's source
 #pragma unroll
         for (int u = 0; u < EX_B; ++u) {
             const uint32_t f = base + (uint32_t)(it0 + u) * 256u + tid;
@@ -184,6 +187,11 @@ __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* f
             const uint32_t f = base + (uint32_t)(it0 + u) * 256u + tid;
             j[u] = f - fstart[seq[u]];
             wbase[u] = S.wstart[seq[u]];
+            back[u] = false;
+            if (RC && f < nfeat) {
+                const uint32_t len = S.len[seq[u]], nwin = len - (uint32_t)g + 1u;
+                if (j[u] >= nwin) { back[u] = true; j[u] = len - 1u - (j[u] - nwin); }
+            }
         }
         key_t key[EX_B];
 #pragma unroll
@@ -193,7 +201,9 @@ __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* f
 #pragma unroll
             for (int u = 0; u < EX_B; ++u) {
                 const uint32_t f = base + (uint32_t)(it0 + u) * 256u + tid;
-                const uint32_t sym = f < nfeat ? fetch_sym(S.words, wbase[u], j[u] + pc, S.bits) : 0u;
+                uint32_t sym = 0u;
+                if (RC && back[u]) sym = comp[fetch_sym(S.words, wbase[u], j[u] - pc, S.bits)];
+                else if (f < nfeat) sym = fetch_sym(S.words, wbase[u], j[u] + pc, S.bits);
                 key[u] = symbits ? (key_t)((key[u] << symbits) | (key_t)sym) : (key_t)(key[u] * sigma + sym);
             }
         }
@@ -223,19 +233,31 @@ __global__ __launch_bounds__(256) void k_sx_featseq(const uint32_t* fstart, uint
 // coalesced load of 8 or 16 bytes — not three dependent gathers (sequence of the g-mer, where it starts, its
 // words) and a load per kept symbol, for every slot of every batch — and the array, read by every slot, stays in
 // L2 / MALL (16 bytes x features).
-template <int WW>
+// RC (reverse-complement mode): the second half of a sequence's features are the windows of rc(x), written reversed and
+// complemented (see k_sx_extract) — everything that reads the window array then sees twice the features and no strands.
+template <int WW, bool RC>
 __global__ __launch_bounds__(256) void k_sx_windows(SeqView S, const uint32_t* feat_seq, const uint32_t* fstart, uint32_t nfeat, int g,
-                                                    uint32_t* win) {
+                                                    uint32_t* win, const uint16_t* comp) {
     const uint32_t f = blockIdx.x * 256u + threadIdx.x;
     if (f >= nfeat) return;
-    const uint32_t seq = feat_seq[f], j = f - fstart[seq], wbase = S.wstart[seq];
+    const uint32_t seq = feat_seq[f], wbase = S.wstart[seq];
+    uint32_t j = f - fstart[seq];
+    bool back = false;
+    if (RC) {
+        const uint32_t len = S.len[seq], nwin = len - (uint32_t)g + 1u;
+        if (j >= nwin) { back = true; j = len - 1u - (j - nwin); }
+    }
     const int per = 32 / S.bits;  // symbols per word
 #pragma unroll
     for (int ww = 0; ww < WW; ++ww) {
         uint32_t acc = 0u;
         for (int q = 0; q < per; ++q) {
             const int c = ww * per + q;
-            if (c < g) acc |= fetch_sym(S.words, wbase, j + (uint32_t)c, S.bits) << (q * S.bits);
+            if (c < g) {
+                const uint32_t sym = RC && back ? (uint32_t)comp[fetch_sym(S.words, wbase, j - (uint32_t)c, S.bits)]
+                                                : fetch_sym(S.words, wbase, j + (uint32_t)c, S.bits);
+                acc |= sym << (q * S.bits);
+            }
         }
         win[(size_t)f * WW + ww] = acc;
     }

@@ -155,6 +155,21 @@ class FastaUtility:
         X = [flat[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
         return X, Y
 
+    def complement(self):
+        """The DNA complement as a mapping of this reader's token ids — a<->t, c<->g, n<->n, for the symbols seen so far (a
+        partner not seen yet gets its id now, so that the mapping is closed) —: what ``FastSK(..., revcomp=...)`` takes.
+        ``ValueError`` naming the symbol when the vocabulary holds anything else (protein read through this object)."""
+        pairs = {"a": "t", "t": "a", "c": "g", "g": "c", "n": "n"}
+        seen = [tok for tok in self._vocab._token2idx if tok != 0]
+        for tok in seen:
+            if tok not in pairs:
+                raise ValueError("symbol %r of the vocabulary has no DNA complement (a, c, g, t, n do)" % (tok,))
+        out = {}
+        for tok in seen:
+            a, b = self._vocab.add(tok), self._vocab.add(pairs[tok])
+            out[a], out[b] = b, a
+        return out
+
     def shortest_seq(self, data_file):
         _, offsets, _ = self.read_packed(data_file)
         return int(np.diff(offsets).min())

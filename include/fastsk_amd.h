@@ -32,7 +32,8 @@ extern "C" {
                               3: fsk_get_triangle_device / fsk_alloc_triangle_device, fsk_config.deadline_ms;
                               4: fsk_set_tuning / fsk_get_tuning / fsk_tuning_keys (one FSK_TUNING variable instead of
                                  two dozen FSK_* switches);
-                              5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order */
+                              5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
+                                 (added since, no layout changed: fsk_set_complement) */
 
 enum {
     FSK_OK = 0,
@@ -132,7 +133,7 @@ typedef struct fsk_stats {
                                 remainder products of the rows with counts above 15 included (profile = 1)  */
     uint64_t panel_bytes;    /* bytes of count panels written (= read at least once)            */
     double u4_tile_launches; /* launches of the 4-bit tile kernel (v_dot8_u32_u4)                */
-    double max_windows;      /* max over sequences of (length - g + 1): bounds a cell per combo  */
+    double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo */
     double count_launches;   /* launches of the segment-count kernel (panel cache misses)        */
     double compact_keys_avg; /* key compaction on: mean keys per combo that really occur (else 0) */
     double batches_redone;   /* sparse: batches enqueued ahead of their word count that did not fit */
@@ -209,6 +210,19 @@ int fsk_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
  * restated in the engine (fsk_seed_order returns it). So FastSK(approx=True, seed=S) samples the
  * combos the reference sampled in the second S. */
 int fsk_set_seed(fsk_engine* e, uint64_t seed);
+
+/* Reverse-complement mode (DNA: a regulatory element reads the same from either strand; what gkm-SVM and LS-GKM
+ * count by default, and the reference cannot). `tokens[i]` <-> `complements[i]`, i < n, is an involution on token ids
+ * (a<->t, c<->g, n<->n ...); rc(x) is x reversed with every token complemented. With the mode on the feature multiset
+ * of a sequence is that of x plus that of rc(x), multiplicities kept, so that per combination
+ *     Krc(x, y) = K(x, y) + K(x, rc y) + K(rc x, y) + K(rc x, rc y),
+ * and everything else (sum over combinations, approx modes, normalisation) is the reference's algorithm on these
+ * counts. n = 0 switches the mode off (the default). Takes effect from the next fsk_load_sequences / fsk_compute; a
+ * group handle sets it on every engine. FSK_EINVAL here when a token is listed twice or the map is not an involution
+ * on its domain (every complement listed, comp(comp(t)) == t; self-pairs allowed); FSK_EINVAL at load, naming the
+ * token, when the data hold a token the map does not list (nothing is self-complemented silently). The alphabet of
+ * a load is the closure under the map of the tokens present. */
+int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 
 /* ---- staged path (multi-GPU sharding, benchmarking with inputs resident in HBM) ------------ */
 /* lengths check + dictionary + packing + H2D: fastsk.cpp:32-88 (extractFeatures is replaced by
