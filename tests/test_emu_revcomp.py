@@ -16,6 +16,9 @@ import pytest
 from conftest import GOLD, ROOT, load_golden, tri_to_square
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import revcomp_cases as cases  # noqa: E402
 
 DNA = {1: 4, 4: 1, 2: 3, 3: 2, 5: 5}   # a = 1, c = 2, g = 3, t = 4, n = 5
 
@@ -414,3 +417,267 @@ def test_golden_from_the_compiled_reference(emu_lib, port, path):
     assert np.array_equal(e.get_counts(), counts)
     assert np.array_equal(e.get_triangle(), tri)
     e.close()
+
+
+# ---- 11: the edges of this mode's kernels -----------------------------------------------------------------------------------
+# The cases of tests/revcomp_cases.py, each checked by ONE function that both suites call: here on the emulator at a reduced
+# scale (fewer ordinary sequences; the lengths that define an edge are kept), in tests/test_gpu_revcomp.py on the device at
+# scale 1. The emulator switches a workgroup's threads only at barriers and wave collectives, so a case that passes here and
+# fails there points at a race or at something only the larger size reaches — not at the logic of the edge.
+# ``make(g, m, **kw)`` creates an engine with the DNA map set. Every comparison is bit-exact against folded_oracle.
+EMU_SCALE = 0.2
+_FOLDS = {}
+
+
+def fold_once(port, key, case, with_updates=False):
+    """The fold (and, asked for, its update count) of a case, computed once per session and shared: treat as read-only."""
+    if key not in _FOLDS:
+        want = folded_oracle(port, case["seqs"], cases.DNA, case["g"], case["m"], case["combos"], threads=cases.THREADS)
+        want.setflags(write=False)
+        _FOLDS[key] = [want, None]
+    if with_updates and _FOLDS[key][1] is None:
+        _FOLDS[key][1] = cases.fold_updates(port, case["seqs"], cases.DNA, case["g"], case["m"], case["combos"])
+    return _FOLDS[key]
+
+
+def accumulate_case(make, case, path, tuning=None, how="whole", n_train=None, **kw):
+    from fastsk_amd import _native
+    tok, off = _native.flatten(case["seqs"])
+    n = len(case["seqs"])
+    e = make(case["g"], case["m"], path=path, tuning=dict(tuning or {}), **kw)
+    e.load_sequences(tok, off, n if n_train is None else n_train, 0 if n_train is None else n - n_train)
+    combos = case["combos"]
+    if how == "whole":
+        e.accumulate(combos)
+    elif how == "three calls":
+        for part in np.array_split(combos, 3):
+            e.accumulate(part)
+    else:
+        for lo, hi in case["bands"]:
+            e.accumulate_rows(combos, lo, hi)
+    e.finalize()
+    return e
+
+
+def assert_kept_cells(got, want, n, n_train):
+    """skip_test_block: every cell whose column is a train sequence or that lies on the diagonal equals the oracle's; the
+    rest is zero in the engine and is not all zero in the oracle; at least half the cells are of the first kind."""
+    a, b = np.tril_indices(n)
+    keep = (b < n_train) | (a == b)
+    assert keep.mean() >= 0.5
+    assert np.array_equal(got[keep], want[keep]) and not got[~keep].any() and want[~keep].any()
+
+
+def check_dense_regime(make, port, lmax, m, rare_n, planned, planned_whole, scale):
+    """k_dense_count<., ., RC>'s strand loop in each staging regime accumulate_dense can put it in (revcomp_cases.dense_regime
+    names them). The arithmetic — fsk_engine_dense.hip:dense_plan with PANEL = 64 bytes a staged row, at most 64 KiB = 1024
+    rows of symbols, LDS_BUDGET = 150 KiB = 153,600 bytes, 512 bytes of histogram a key quad — for DNA at g = 12, where a
+    strand of L symbols stages L rows = 64 L bytes:
+        one pass per strand   <=> 64 L <= 65,536                        <=> L <= 1024        (beyond: C, 1013 windows a chunk)
+        second buffer fits    <=> 64 L + 64 L + table + 1024 <= 153,600 <=> L <= 1192 - table / 128
+        key quads a sweep      =  (153,600 - 128 L - table) / 512, rounded down to even
+      m = 8: 256 keys = 64 key quads, no table.
+        L = 300: A, one sweep (64 quads fit up to L = 944).   L = 1000: A, (153,600 - 128,000) / 512 = 50 quads: two sweeps, the
+        second without staging.   L = 1025, 2500: C, two and three chunks a strand, every chunk of every strand restaged.
+      m = 5: 16,384 keys = 4096 key quads. L = 1000: A, 50 quads: 82 sweeps, 81 of them on the kept buffers.
+      m = 7 with a few n: 3125 keys = 782 key quads, key compaction on, a table of 6250 bytes. L = 1000: A,
+        (153,600 - 128,000 - 6250) / 512 = 37 -> 36 quads: up to 22 sweeps (fewer for a combo whose compacted keys are
+        fewer), keys through the rank table.
+    B (a strand fits in one pass, the second buffer does not) cannot come out of this plan: with L <= 1024 the second buffer
+    fails only for a table above 153,600 - 1024 - 131,072 = 21,504 bytes = 10,752 keys, and the engine compacts keys up to
+    4096 only (fsk_engine.hip: compact = ... && V <= 4096; compact=1 at 16,384 keys leaves compaction off). What does reach it
+    is the tuning key dense_chunk at or above the strand's windows: CH stays max_win, rc_rows stays 0. Every case that
+    fits one pass is run once more that way (dense_chunk=2^20): L = 1000 at m = 5 is then B with (153,600 - 64,000) / 512 =
+    175 -> 174 quads, 24 sweeps, each restaging strand by strand.
+    The load is ragged (the second strand reads len - 1 - p per lane); dense_chunk=7 is regime C with 7 windows a chunk;
+    path=2 is the sparse dataflow on the same sequences, whose backward half crosses many 256-feature blocks of
+    k_sx_windows. No stat names the regime and none is added for this: the restated plan is what is asserted."""
+    case = cases.dense_regime_case(port, lmax, m, rare_n, scale)
+    g, keys, compact = case["g"], case["keys"], case["compact"]
+    assert cases.dense_regime(lmax, g, keys, compact) == planned
+    assert cases.dense_regime(lmax, g, keys, compact, cases.WHOLE_STRAND) == planned_whole
+    assert cases.dense_regime(lmax, g, keys, compact, case["tiny_chunk"])[0] == "C"
+    lens = [len(s) for s in case["seqs"]]
+    assert max(lens) == lmax and min(lens) == g and len(set(lens)) > len(lens) // 4
+    want, _ = fold_once(port, ("dense", lmax, m, scale), case)
+    for path, tun in ((1, {}), (1, {"dense_chunk": cases.WHOLE_STRAND}), (1, {"dense_chunk": case["tiny_chunk"]}), (2, {})):
+        e = accumulate_case(make, case, path, tun)
+        st = e.stats()
+        assert st["path_used"] == path and st["revcomp"] and st["max_windows"] == case["max_windows"], (path, tun)
+        assert st["key_space"] == keys and (path != 1 or (st["compact_keys_avg"] > 0) == compact), (path, tun)
+        assert np.array_equal(e.get_counts(), want), (planned, path, tun)
+        e.close()
+
+
+def check_planes(make, port, name, path, scale):
+    """Counts that pass 15 (the hi plane of the count panels) or 255 (the hand-over to the sparse dataflow) only because both
+    strands land in one counter: revcomp_cases.plane_case."""
+    from fastsk_amd import _native
+    case = cases.plane_case(name, scale)
+    n = len(case["seqs"])
+    want, _ = fold_once(port, ("planes", name, scale), case)
+    tok, off = _native.flatten(case["seqs"])
+    e = make(case["g"], case["m"], path=path)
+    e.compute(tok, off, n, 0)
+    st = e.stats()
+    assert np.array_equal(e.get_counts(), want), (name, path)
+    assert np.array_equal(e.get_triangle(), port.normalise(want.astype(np.float64), n))
+    if path == 1:   # the hand-over ran exactly when a count passed 255
+        assert (st["sort_records"] > 0) == (name == "overflow")
+    e.close()
+
+
+def check_long_sequence(make, port, windows, skip, sparse_global, scale):
+    """The packed / unpacked entry formats on either side of max_windows = 65,536 (revcomp_cases.long_sequence_case), update
+    streams and 64-bit atomics, with and without skip_test_block."""
+    case = cases.long_sequence_case(windows, scale)
+    n, ntr = len(case["seqs"]), case["n_train"]
+    want, U = fold_once(port, ("long", windows, scale), case, with_updates=True)
+    e = accumulate_case(make, case, 2, {"sparse_global": sparse_global}, n_train=ntr, skip_test_block=skip)
+    st = e.stats()
+    assert st["path_used"] == 2 and st["max_windows"] == case["max_windows"] == 2 * windows
+    got = e.get_counts()
+    if skip:
+        assert_kept_cells(got, want, n, ntr)
+        assert st["cell_updates"] < U
+    else:
+        assert np.array_equal(got, want)
+        assert st["cell_updates"] == U
+    e.close()
+
+
+def check_products(make, port, sparse_global, scale):
+    """Products beyond the product field of one 32-bit update word, in a cell that is zero without this mode
+    (revcomp_cases.products_case); update streams and 64-bit atomics."""
+    case = cases.products_case(scale)
+    want, U = fold_once(port, ("products", scale), case, with_updates=True)
+    ia, it = case["poly_a"], case["poly_t"]
+    assert want[it * (it + 1) // 2 + ia] == len(case["combos"]) * 2 * 1491 * 1391   # (they pair through this mode only)
+    e = accumulate_case(make, case, 2, {"sparse_global": sparse_global})
+    assert np.array_equal(e.get_counts(), want)
+    assert e.stats()["cell_updates"] == U
+    e.close()
+
+
+def check_wide_windows(make, port, path, scale):
+    """g x bits a symbol > 128: revcomp_cases.wide_window_case, the combos in two calls."""
+    from fastsk_amd import _native
+    case = cases.wide_window_case(port, scale)
+    want, _ = fold_once(port, ("wide", scale), case)
+    tok, off = _native.flatten(case["seqs"])
+    e = make(case["g"], case["m"], path=path)
+    e.load_sequences(tok, off, len(case["seqs"]), 0)
+    assert e.stats()["bits_per_symbol"] == 4
+    e.accumulate(case["combos"][:2])
+    e.accumulate(case["combos"][2:])
+    e.finalize()
+    assert e.stats()["path_used"] == path and np.array_equal(e.get_counts(), want)
+    e.close()
+
+
+def check_update_stages(make, port, scale):
+    """Every form of the sparse update stage (revcomp_cases.SPARSE_FORMS and the two-level blocks forced small) on ragged
+    low-complexity sequences: in one call, in three calls, in row bands at multiples of 128 — whole triangle and U."""
+    case = cases.low_complexity_case(scale)
+    want, U = fold_once(port, ("stages", scale), case, with_updates=True)
+    digests = set()
+    for name, tun, form in cases.SPARSE_FORMS + [cases.SMALL_BLOCKS]:
+        for how in ("whole", "three calls", "row bands"):
+            e = accumulate_case(make, case, 2, tun, how)
+            st = e.stats()
+            assert st["path_used"] == 2 and (form is None or st["sparse_form"] == form), (name, how)
+            assert np.array_equal(e.get_counts(), want), (name, how)
+            assert st["cell_updates"] == U, (name, how)
+            digests.add(e.counts_digest())
+            e.close()
+    assert len(digests) == 1
+
+
+def check_narrowing(make, port, windows, narrow, scale):
+    """fsk_multi.hip narrows the exchange of a group to int32 when combos x max_windows^2 < 2^31, max_windows counting both
+    strands (revcomp_cases.narrowing_case: the cell that needs it)."""
+    from fastsk_amd import _native
+    case = cases.narrowing_case(windows, scale)
+    n, ntr, at = len(case["seqs"]), case["n_train"], case["long_at"]
+    assert (15 * (2 * windows) ** 2 < 2 ** 31) == narrow and (narrow or 15 * windows ** 2 < 2 ** 31 <= case["diagonal"])
+    want, _ = fold_once(port, ("narrow", windows, scale), case)
+    diag = at * (at + 1) // 2 + at
+    assert want[diag] == case["diagonal"]
+    tok, off = _native.flatten(case["seqs"])
+    one = make(case["g"], case["m"])
+    one.compute(tok, off, ntr, n - ntr)
+    e = make(case["g"], case["m"], devices=[0, 0], collective=_native.COLL_P2P)
+    e.compute(tok, off, ntr, n - ntr)
+    info = e.multi_info()
+    assert info["ndev"] == 2 and info["collective"] == "p2p" and info["narrow"] == narrow
+    got = e.get_counts()
+    assert got[diag] == case["diagonal"]
+    assert np.array_equal(got, want)
+    assert np.array_equal(e.get_triangle(), port.normalise(want.astype(np.float64), n))
+    assert e.counts_digest() == one.counts_digest()
+    one.close(); e.close()
+
+
+@pytest.fixture(scope="module")
+def make_emu(emu_lib):
+    return lambda g, m, **kw: engine(emu_lib, g, m, cases.DNA, **kw)
+
+
+def test_fold_updates_is_the_oracles_count_on_one_strand(port):
+    """revcomp_cases.fold_updates with the second strand left out is ``port.raw_counts``' U: what makes it a yardstick."""
+    from fastsk_amd import _native
+    case = cases.low_complexity_case(0.1)
+    tok, off = _native.flatten(case["seqs"])
+    _, _, U = port.raw_counts(tok, off, case["g"], case["m"], case["combos"])
+    assert cases.fold_updates(port, case["seqs"], None, case["g"], case["m"], case["combos"]) == U
+    seqs = ragged_dna()
+    tok, off = _native.flatten(seqs)
+    _, _, U = port.raw_counts(tok, off, 8, 3, np.arange(56, dtype=np.int32))
+    assert cases.fold_updates(port, seqs, None, 8, 3, np.arange(56)) == U
+
+
+def test_plane_cases_cross_their_planes_only_with_both_strands(port):
+    """revcomp_cases.plane_case at both scales, from the definition: 'hi_plane' at most 15 a strand, more than 15 and at most
+    255 together; 'overflow' at most 255 a strand, more together. At scale 1 its rows sit in three panels and two tiles."""
+    for scale in (1.0, EMU_SCALE):
+        for name, plane in (("hi_plane", 15), ("overflow", 255)):
+            case = cases.plane_case(name, scale)
+            one, both = cases.strand_maxima(port, case["seqs"], cases.DNA, case["g"], case["m"], case["combos"])
+            assert one <= plane < both and (name == "overflow" or both <= 255), (name, scale, one, both)
+            rows = case["flagged"]
+            assert len({r // 64 for r in rows}) >= 2 and (scale < 1.0 or (len({r // 64 for r in rows}) == 3 and len({r // 128 for r in rows}) == 2))
+
+
+@pytest.mark.parametrize("lmax,m,rare_n,planned,planned_whole", cases.DENSE_REGIMES)
+def test_edges_dense_staging_regimes(make_emu, port, lmax, m, rare_n, planned, planned_whole):
+    check_dense_regime(make_emu, port, lmax, m, rare_n, planned, planned_whole, EMU_SCALE)
+
+
+@pytest.mark.parametrize("path", [0, 1, 2])
+@pytest.mark.parametrize("name", ["hi_plane", "overflow"])
+def test_edges_counts_crossing_a_plane(make_emu, port, name, path):
+    check_planes(make_emu, port, name, path, EMU_SCALE)
+
+
+@pytest.mark.parametrize("windows,skip,sparse_global", [(32767, False, 0), (32767, True, 1), (32768, True, 0), (32768, False, 1)])
+def test_edges_sparse_entry_formats(make_emu, port, windows, skip, sparse_global):
+    check_long_sequence(make_emu, port, windows, skip, sparse_global, EMU_SCALE)
+
+
+@pytest.mark.parametrize("sparse_global", [0, 1])
+def test_edges_sparse_products_beyond_one_update_word(make_emu, port, sparse_global):
+    check_products(make_emu, port, sparse_global, EMU_SCALE)
+
+
+@pytest.mark.parametrize("path", [1, 2])
+def test_edges_windows_wider_than_128_bits(make_emu, port, path):
+    check_wide_windows(make_emu, port, path, EMU_SCALE)
+
+
+def test_edges_sparse_update_stages(make_emu, port):
+    check_update_stages(make_emu, port, EMU_SCALE / 2)
+
+
+@pytest.mark.parametrize("windows,narrow", [(10000, False), (4000, True)])
+def test_edges_group_narrowing(make_emu, port, windows, narrow):
+    check_narrowing(make_emu, port, windows, narrow, EMU_SCALE)

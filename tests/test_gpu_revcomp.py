@@ -10,6 +10,10 @@ from conftest import ROOT, load_tokens, reference_fasta, synthetic_dna, tri_to_s
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import revcomp_cases as cases  # noqa: E402
+from test_emu_revcomp import (check_dense_regime, check_long_sequence, check_narrowing, check_planes, check_products,  # noqa: E402
+                              check_update_stages, check_wide_windows)
+
 pytestmark = pytest.mark.gpu
 
 ACGT = {1: 4, 4: 1, 2: 3, 3: 2}   # synthetic_dna: tokens 1..4
@@ -82,12 +86,7 @@ def test_golden_from_the_compiled_reference(native, path):
 
 
 # ---- 12 -----------------------------------------------------------------------------------------------------------------
-SPARSE_FORMS = [("owner bands", {"sparse_form": 1, "sparse_desc": -1}, 0),
-                ("owner bands, descriptors", {"sparse_form": 1, "sparse_desc": 1, "sparse_desc_min": 5}, 0),
-                ("two-level blocks", {"sparse_form": 2, "sparse_desc": -1}, 2),
-                ("two-level blocks, descriptors", {"sparse_form": 2, "sparse_desc": 1, "sparse_desc_min": 5}, 2),
-                ("unpacked entries", {"sparse_unpacked": 1}, None),
-                ("direct atomics", {"sparse_form": 3}, 1)]
+SPARSE_FORMS = cases.SPARSE_FORMS
 
 
 def test_sparse_forms_forced_on_dna_k8(native, port):
@@ -213,3 +212,50 @@ def test_variance_mode_on_ep300(native, port, path):
     assert np.array_equal(e.get_stdevs(), sds)
     assert np.array_equal(e.get_triangle(), want)
     e.close()
+
+
+# ---- 15: the edges of this mode's kernels ----------------------------------------------------------------------------------
+# tests/revcomp_cases.py at scale 1, through the checks of tests/test_emu_revcomp.py (section 11 there runs the same cases on
+# the emulator, scaled down): what the emulator cannot show — races between the four waves of k_dense_count on the histogram
+# and on the second strand's buffer, a missing barrier between staging a strand and counting it — and the sizes it cannot
+# afford. Every comparison is bit-exact against folded_oracle.
+@pytest.fixture(scope="module")
+def make(native):
+    return lambda g, m, **kw: native.Engine(g, m, revcomp=cases.DNA, **kw)
+
+
+@pytest.mark.parametrize("lmax,m,rare_n,planned,planned_whole", cases.DENSE_REGIMES)
+def test_dense_staging_regimes_on_ragged_dna(make, port, lmax, m, rare_n, planned, planned_whole):
+    check_dense_regime(make, port, lmax, m, rare_n, planned, planned_whole, 1.0)
+
+
+@pytest.mark.parametrize("path", [0, 1, 2])
+@pytest.mark.parametrize("name", ["hi_plane", "overflow"])
+def test_counts_crossing_a_plane_with_both_strands(make, port, name, path):
+    check_planes(make, port, name, path, 1.0)
+
+
+@pytest.mark.parametrize("sparse_global", [0, 1])
+@pytest.mark.parametrize("skip", [False, True])
+@pytest.mark.parametrize("windows", [32767, 32768])
+def test_sparse_entry_formats_at_the_doubled_feature_count(make, port, windows, skip, sparse_global):
+    check_long_sequence(make, port, windows, skip, sparse_global, 1.0)
+
+
+@pytest.mark.parametrize("sparse_global", [0, 1])
+def test_sparse_products_beyond_one_update_word(make, port, sparse_global):
+    check_products(make, port, sparse_global, 1.0)
+
+
+@pytest.mark.parametrize("path", [1, 2])
+def test_windows_wider_than_128_bits(make, port, path):
+    check_wide_windows(make, port, path, 1.0)
+
+
+def test_sparse_update_stages_on_ragged_low_complexity_dna(make, port):
+    check_update_stages(make, port, 1.0)
+
+
+@pytest.mark.parametrize("windows,narrow", [(10000, False), (4000, True)])
+def test_group_narrowing_sees_both_strands(make, port, windows, narrow):
+    check_narrowing(make, port, windows, narrow, 1.0)
