@@ -239,7 +239,7 @@ struct SxBatch {
     SxShare sh;
     int keybits = 0, form = 0, pairs = 0, col16 = 0;
     bool slot16 = false, skipping = false, packed = false, by_id = false;
-    uint32_t O = 0, OC = 0, desc = 0, short_max = 0, skip_from = 0, uc = 0, nchunks = 0, maxprod = 0, cmax = 0;
+    uint32_t O = 0, OC = 0, desc = 0, short_max = 0, skip_from = 0, uc = 0, nchunks = 0, maxprod = 0, cmax = 0, cwide = 0;
     fsk::SxIds ids{};
     const uint8_t* pos_tab = nullptr;  // the kept positions of the batch's combos, on the device
     const void* sorted = nullptr;      // the sort: the buffer that holds the sorted records
@@ -295,6 +295,9 @@ int sx_batch_begin(SxBatch& c) {
     c.col16 = (std::max(1, sx_bits_below((u64)e->N)) << 1) | (e->N < 32768 && e->tune.sparse_desc_cols == 3 ? 1 : 0);
     c.maxprod = (1u << e->sx_pb) - 1u;
     c.cmax = c.maxprod / std::max<uint32_t>(1u, e->maxW);  // multiplicities up to here: one word per pair
+    // multiplicities up to here: the sum of a batch's products fits a u32 cell of the consume kernels; an entry beyond adds
+    // its products into K itself (fsk_sparse_kernels.inc:sx_wide_entry — none while maxW < 65,536; never into slot triangles)
+    c.cwide = c.slot_stride != 0 ? 0xffffffffu : 0xffffffffu / std::max<uint32_t>(1u, e->maxW);
 
     // (the presort's records, 4 or 8 bytes a window and group, go through the same two buffers first)
     const size_t pre_bytes = sh.share ? (size_t)sh.groups * nfeat * (sh.pre64 ? 8 : 4) : 0;
@@ -483,13 +486,13 @@ struct SxBands {
     const uint32_t* r0;      // on the device: the first row of every band
     int shift;               // a band: the rows whose first cell, counted from own_base, lies in [o << shift, (o + 1) << shift)
     uint32_t n, row0, row1;  // bands; the rows the words are for
-    uint32_t maxprod, cmax;
+    uint32_t maxprod, cmax, cwide;
     int pb;                  // product bits of a word
     uint32_t own_base;       // blocks: the pass's first cell (mod 2^32)
     int sub_shift;           // blocks: sub-bands of 2^sub_shift cells
 };
 SxBands sx_owner_bands(const SxBatch& c) {
-    return SxBands{(const uint32_t*)c.e->d_owner_r0.p, c.e->sx_own_shift, c.O, (uint32_t)c.row0, (uint32_t)c.row1, c.maxprod, c.cmax, c.e->sx_pb, 0u, 0};
+    return SxBands{(const uint32_t*)c.e->d_owner_r0.p, c.e->sx_own_shift, c.O, (uint32_t)c.row0, (uint32_t)c.row1, c.maxprod, c.cmax, c.cwide, c.e->sx_pb, 0u, 0};
 }
 
 // k_sx_seg_write: the entries of the sorted records and, by band, the words they will emit (the count matrix; none for the
@@ -504,7 +507,7 @@ void sx_seg_write(const SxBatch& c, const SxBands& b) {
         auto k = fsk::k_sx_seg_write<RecT, packed, pairs, skip, desc>;
         FSK_LAUNCH(k, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, (const uint32_t*)S.d_ebase.p,
                    (const int*)S.d_tile_rs.p, reinterpret_cast<typename X::ent_t*>(S.d_E.p), reinterpret_cast<typename X::rank_t*>(S.d_Pk.p),
-                   b.shift, b.n, ucount, b.row0, b.row1, e->maxW, b.maxprod, b.cmax, S.d_tile_stat.p, c.skip_from,
+                   b.shift, b.n, ucount, b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.cwide, S.d_tile_stat.p, c.skip_from,
                    skip ? (const int*)S.d_tile_ts.p : (const int*)nullptr, skip ? reinterpret_cast<typename X::rank_t*>(S.d_Tk.p) : nullptr,
                    b.own_base, c.short_max, c.desc, b.sub_shift, c.colp, c.col16);
     }, c.packed, c.pairs != 0, c.skipping, c.desc != 0);
@@ -532,7 +535,7 @@ void sx_emit(const SxBatch& c, const SxBands& b, bool direct, u64 cap_words) {
         FSK_LAUNCH(k, dim3(fsk::xcd_grid(c.ntiles)), dim3(fsk::EM_THREADS), 0, c.stream, reinterpret_cast<const typename X::ent_t*>(S.d_E.p),
                    reinterpret_cast<const typename X::rank_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, b.r0, b.shift, b.n,
                    dir ? nullptr : (const uint32_t*)S.d_list_off.p, dir ? nullptr : (const uint32_t*)S.d_ucount.p, dir ? nullptr : S.d_ulist.p,
-                   b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.pb, c.K, c.tpg, c.slot_stride,
+                   b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.cwide, b.pb, c.K, c.tpg, c.slot_stride,
                    skip ? reinterpret_cast<const typename X::rank_t*>(S.d_Tk.p) : nullptr, dir ? nullptr : (const u64*)S.d_sxstat.p, cap_words,
                    c.ntiles, dir ? 0 : c.pairs, b.own_base, dir ? fsk::SX_SHORT : c.short_max, dir ? 0u : c.desc, b.sub_shift);
     }, direct, c.skipping, c.packed, c.desc != 0);
@@ -785,7 +788,7 @@ int sx_update_blocks(SxBatch& c) {
         first_pass = false;
         const uint32_t maxprod = (1u << P.pb) - 1u;
         const SxBands bands{(const uint32_t*)e->d_blk_r0.p, P.t, Op, (uint32_t)ra, (uint32_t)rb, maxprod, maxprod / std::max<uint32_t>(1u, e->maxW),
-                            P.pb, P.own_base, P.sub_shift};
+                            c.cwide, P.pb, P.own_base, P.sub_shift};
         pin[0] = pin[1] = 0;
         sx_seg_write<RecT>(c, bands);
         sx_stream_offsets(c, c.desc ? 2u * Op : Op);  // (columns: descriptor streams first, then the words')
@@ -951,8 +954,10 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
     if (rc) return rc;
     sx_choose_form(e);
     const bool blocks_form = e->sx_form == 2 && slot_stride == 0;
-    // Batch so that (i) the record count stays below the cap, (ii) the owner bands can sum a batch in u32 LDS cells
-    // (per cell and combo <= maxW^2), (iii) a batch's update words stay well inside what one stream addresses
+    // Batch so that (i) the record count stays below the cap, (ii) the owner bands and the blocks can sum a batch in u32 LDS
+    // cells (per cell and combo <= maxW^2; where one combo alone passes 2^32 — maxW >= 65,536, by_cells = 1 — the entries
+    // that could make it do so add into K themselves: fsk_sparse_kernels.inc:sx_wide_entry), (iii) a batch's update words
+    // stay well inside what one stream addresses
     // (2^31: beyond it the pairs go to K with atomics, an order of magnitude slower) — judged by the most words per
     // record seen so far on these sequences; while none has been seen, a first batch of at most 2^25 records.
     const size_t nfeat = (size_t)std::max<int64_t>(1, e->nfeat);
@@ -1014,7 +1019,10 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
         nb_steady = (int)std::max<u64>(1, std::min<u64>({(u64)(recs / nfeat), (u64)n, by_cells, (u64)65535}));
     }
     const bool many = (n + nb_steady - 1) / nb_steady >= 6;
-    const bool two = (e->tune.sparse_exact_lanes >= 2 || (e->tune.sparse_exact_lanes == 0 && many)) && !e->profile_sync() && !e->sx_exactly() && slot_stride == 0 && nb0 < n && !blocks_form;
+    // (never with a sequence of 65,536 windows or more: k_sx_emit then adds the products of wide entries into K itself —
+    // sx_wide_entry —, and the lanes order only their consume passes)
+    const bool wide = (u64)e->maxW * e->maxW > 0xffffffffull;
+    const bool two = (e->tune.sparse_exact_lanes >= 2 || (e->tune.sparse_exact_lanes == 0 && many)) && !e->profile_sync() && !e->sx_exactly() && slot_stride == 0 && nb0 < n && !blocks_form && !wide;
     if (two) {
         if (!e->lane_stream) FSK_HIP(hipStreamCreateWithFlags(&e->lane_stream, hipStreamNonBlocking));
         for (auto& ev : e->ev_lane)

@@ -56,8 +56,9 @@ constexpr uint32_t SX_DESC_MULT_BITS = 20;  // a descriptor's multiplicity field
 // of the piece, cell of column 0 of the row inside the band, multiplicity | sub-band << 20} — reserved by the most a row of
 // that length can take, (row >> sub_shift) + 2, the rest left as empty records (T = 0); the entry's own cell (multiplicity
 // above 1) travels as an ordinary update word. May an entry of multiplicity c that is not binned be a descriptor?
-__device__ __forceinline__ bool sx_desc_entry(uint32_t desc, uint32_t c, uint32_t cmax) {
-    return desc != 0u && c < (1u << SX_DESC_MULT_BITS) && (desc == 1u || c <= cmax);
+// (cwide: see sx_wide_entry — an entry beyond it is no descriptor either)
+__device__ __forceinline__ bool sx_desc_entry(uint32_t desc, uint32_t c, uint32_t cmax, uint32_t cwide) {
+    return desc != 0u && c < (1u << SX_DESC_MULT_BITS) && c <= cwide && (desc == 1u || c <= cmax);
 }
 __device__ __forceinline__ uint32_t sx_desc_records(uint32_t desc, uint32_t row, int sub_shift) { return desc == 2u ? (row >> sub_shift) + 2u : 1u; }
 #ifndef FSK_SX_SHORT
@@ -882,6 +883,17 @@ __device__ __forceinline__ uint32_t sx_words_per_pair(uint32_t count, uint32_t c
     return (uint32_t)(((u64)count * max_win + maxprod - 1) / maxprod);
 }
 
+// WIDE entries. The consume kernels (k_sx_consume, k_sxb_consume) sum a batch's contributions to a cell in u32 LDS cells. A
+// cell (i, j) takes sum_v c_i(v) c_j(v) a combination, the entries of row i sending the products: while every c_i(v) stays at
+// or below cwide = (2^32 - 1) / max_windows that sum is at most cwide * sum_v c_j(v) <= cwide * max_windows < 2^32. The host
+// keeps a batch to (2^32 - 1) / max_windows^2 combinations, which makes cwide >= max_windows — no entry is wide — until
+// max_windows reaches 65,536; from there on a batch is ONE combination and an entry of multiplicity above cwide (a
+// homopolymer's) adds its products into K itself, one 64-bit atomic each (k_sx_emit, as its DIRECT form does for every entry):
+// it is neither binned nor a descriptor, and so that every count of words, every stream offset and every "no words, no launch"
+// on the host stays what it is, it sends ONE word of product 0 to the first cell of its row. (By-slot batches — variance
+// mode, u32 triangles by design — pass cwide = 2^32 - 1: never.)
+__device__ __forceinline__ bool sx_wide_entry(uint32_t c, uint32_t cwide) { return c > cwide; }
+
 // Entries of one tile: E (sequence, multiplicity), Pk (rank in run), and — unless `ucount` is null —
 // the number of update words the tile will emit per owner band, ucount[tile][owner].
 // stats[0] += pairs (the reference's `+=` count U), stats[1] += update words.
@@ -899,7 +911,7 @@ __global__ __launch_bounds__(256) void k_sx_seg_write(const RecT* rec, uint32_t 
                                                       const int* tile_rs, typename SxEnt<PACKED>::ent_t* E,
                                                       typename SxEnt<PACKED>::rank_t* Pk, int own_shift, uint32_t n_owners,
                                                       uint32_t* ucount, uint32_t row0, uint32_t row1, uint32_t max_win,
-                                                      uint32_t maxprod, uint32_t cmax, u64* tile_stat, uint32_t skip_from,
+                                                      uint32_t maxprod, uint32_t cmax, uint32_t cwide, u64* tile_stat, uint32_t skip_from,
                                                       const int* tile_ts, typename SxEnt<PACKED>::rank_t* Tk, uint32_t own_base,
                                                       uint32_t short_max_in, uint32_t desc_in, int desc_sub_shift, void* cols_in, int col16) {
     // (DESC: a template parameter — this kernel is bound by the instructions it issues, and the instantiation without
@@ -1066,7 +1078,7 @@ __global__ __launch_bounds__(256) void k_sx_seg_write(const RecT* rec, uint32_t 
             const uint32_t np = T + (c > 1u ? 1u : 0u);
             const bool in_band = seq >= row0 && seq < row1;
             const bool is_short = np != 0u && np <= short_max && c <= cmax;  // (k_sx_emit's class 1: binned in LDS)
-            const bool is_desc = np != 0u && !is_short && sx_desc_entry(desc, c, cmax);  // (k_sx_emit's class 5: descriptors)
+            const bool is_desc = np != 0u && !is_short && sx_desc_entry(desc, c, cmax, cwide);  // (k_sx_emit's class 5: descriptors)
             const bool unit = clean && in_band && is_short;
             E_t[e] = SxEnt<PACKED>::pack(seq, unit ? 0u : c);
             if (cols) {
@@ -1088,6 +1100,9 @@ __global__ __launch_bounds__(256) void k_sx_seg_write(const RecT* rec, uint32_t 
                         atomicAdd(&s_cntd[sx_owner_of(seq, own_shift, own_base)], dw);
                         if (own) atomicAdd(&s_cnt[sx_owner_of(seq, own_shift, own_base)], 1u);
                     }
+                } else if (np != 0u && sx_wide_entry(c, cwide)) {  // (its products go to K as 64-bit atomics: one word of product 0)
+                    words_t += 1u;
+                    w = 1u;
                 } else if (c > cmax) {  // (rare)
                     const u64 wm = (u64)np * sx_words_per_pair(c, cmax, max_win, maxprod);
                     words_multi += wm;
@@ -1346,7 +1361,7 @@ __global__ __launch_bounds__(EM_THREADS, FSK_EM_MIN_WAVES) void k_sx_emit(const 
                                                         const uint32_t* owner_r0, int own_shift, uint32_t n_owners,
                                                         const uint32_t* list_off, const uint32_t* tile_off, uint32_t* list,
                                                         uint32_t row0, uint32_t row1, uint32_t max_win, uint32_t maxprod,
-                                                        uint32_t cmax, int pb, u64* K, uint32_t tpg, u64 slot_stride,
+                                                        uint32_t cmax, uint32_t cwide, int pb, u64* K, uint32_t tpg, u64 slot_stride,
                                                         const typename SxEnt<PACKED>::rank_t* Tk, const u64* batch_stat, u64 cap_words,
                                                         uint32_t n_tiles, int pairs, uint32_t own_base, uint32_t short_max_in,
                                                         uint32_t desc_in, int desc_sub_shift) {
@@ -1456,7 +1471,7 @@ __global__ __launch_bounds__(EM_THREADS, FSK_EM_MIN_WAVES) void k_sx_emit(const 
                     // (class 4: a UNIT entry — multiplicity field 0, k_sx_seg_write's mark: always short, every product 1)
                     // (class 5, descriptors: every entry that is not binned leaves as one descriptor)
                     my_cls[q] = (my_np[q] <= short_max && one_word) ? ((!DIRECT && ue.y == 0u) ? 4u : 1u)
-                                : (!DIRECT && sx_desc_entry(desc, sx_mult(ue.y), cmax)) ? 5u
+                                : (!DIRECT && sx_desc_entry(desc, sx_mult(ue.y), cmax, cwide)) ? 5u
                                 : (!DIRECT && !SKIP && one_word && my_np[q] <= 32u) ? 3u : 2u;
                 }
             }
@@ -1808,7 +1823,8 @@ __global__ __launch_bounds__(EM_THREADS, FSK_EM_MIN_WAVES) void k_sx_emit(const 
             const uint32_t e = s_long[q];
             const uint2 a = SX_ENT(e);
             const uint32_t o = sx_owner_of(a.x, own_shift, own_base);
-            const uint32_t at = atomicAdd(&s_cur[o], SX_NPART(e) * sx_words_per_pair(a.y, cmax, max_win, maxprod));
+            // (a wide entry — sx_wide_entry — takes one word)
+            const uint32_t at = atomicAdd(&s_cur[o], sx_wide_entry(a.y, cwide) ? 1u : SX_NPART(e) * sx_words_per_pair(a.y, cmax, max_win, maxprod));
             long_hdr[q] = make_uint2(at, sx_tri32(a.x) - s_segc0[o].y);
         }
         __syncthreads();
@@ -1904,6 +1920,15 @@ __global__ __launch_bounds__(EM_THREADS, FSK_EM_MIN_WAVES) void k_sx_emit(const 
         const uint2 a = n_a, hdr = n_hdr;
         if (q + EM_WAVES < nlong) SX_FETCH_LONG(q + EM_WAVES)
         if (DIRECT) {
+            u64* row = K + tri_index((u64)a.x, 0);
+            for (uint32_t b = lane; b < P; b += 64) {
+                const uint2 pq = SX_PARTNER_OF(e, b);
+                atomicAdd(&row[pq.x], (u64)a.y * (pq.y - (SX_IS_SELF(e, b) ? 1u : 0u)));
+            }
+        } else if (sx_wide_entry(a.y, cwide)) {
+            // (sx_wide_entry: the products as 64-bit atomics — the u32 cells of the consume kernels could not hold their sum —
+            // and the one word of product 0 that k_sx_seg_write counted for the entry)
+            if (lane == 0u) list[hdr.x] = hdr.y << pb;
             u64* row = K + tri_index((u64)a.x, 0);
             for (uint32_t b = lane; b < P; b += 64) {
                 const uint2 pq = SX_PARTNER_OF(e, b);

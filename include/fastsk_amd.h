@@ -289,7 +289,13 @@ int fsk_get_triangle(fsk_engine* e, double* out);   /* double[N(N+1)/2], the ref
  * (*device_out; release with fsk_free_device). One streaming pass: 16 bytes per cell. */
 int fsk_get_triangle_device(fsk_engine* e, double* device_out);
 int fsk_alloc_triangle_device(fsk_engine* e, double** device_out);
-int fsk_get_counts(fsk_engine* e, uint64_t* out);   /* raw integer triangle (exact/skip-var)   */
+/* The raw integer triangle of the exact and skip-variance modes: the EXACT 64-bit sum over the combinations accumulated, for
+ * every form either dataflow takes and every tuning key. Where a kernel sums in 32 bits first, the host keeps what one launch
+ * or batch can put into a cell below 2^32 (combinations per dense tile launch and per sparse batch: (2^32 - 1) / max_windows^2),
+ * and where one combination alone can pass it (a sequence of 65,536 windows or more) the sparse dataflow adds the entries that
+ * could make it do so into the 64-bit triangle directly. (Variance mode's per-combination triangles are 32 bits wide by
+ * design, like the reference's `unsigned int Ks`; they are not what this returns.) */
+int fsk_get_counts(fsk_engine* e, uint64_t* out);
 int fsk_get_counts_block(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint64_t* out);
 /* raw integer cells (rows[q], cols[q]), q < n, of the symmetric matrix: scattered spot checks of a
  * triangle too large to copy out (tri_access of arbitrary pairs, shared.cpp:97-117) */
