@@ -2,7 +2,7 @@
 ``FastSK(g, m, ...).compute_kernel(Xtrain, Xtest)`` path)."""
 from .utils import FastaUtility, Vocabulary  # noqa: F401
 
-__all__ = ["FastSK", "FastaUtility", "Vocabulary"]
+__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels"]
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
         share_hip_runtime_with_torch()  # before the extension pulls in libamdhip64
         from ._fastsk import FastSK
         return FastSK
+    if name == "mismatch_levels":  # (host only, but it lives in the HIP library)
+        from ._native import mismatch_levels
+        return mismatch_levels
     raise AttributeError(name)

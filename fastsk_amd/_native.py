@@ -76,7 +76,7 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_run_chains", "fsk_get_kernel_sum_device", "fsk_set_kernel_sum_device", "fsk_create_multi", "fsk_get_multi_info",
            "fsk_counts_digest", "fsk_alloc_block_device", "fsk_free_device", "fsk_set_skip_test_block",
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
-           "fsk_set_complement"]
+           "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels"]
 
 
 _hip_shared = False
@@ -209,6 +209,10 @@ class Library:
             "fsk_tuning_keys": ([], C.c_char_p),
             "fsk_seed_order": ([C.c_uint64, i64, vp], C.c_int),
             "fsk_set_complement": ([vp, vp, vp, i32], C.c_int),
+            "fsk_set_mismatch_weights": ([vp, vp, i32], C.c_int),
+            "fsk_get_mismatch_info": ([vp, C.POINTER(i32), vp, vp, i32], C.c_int),
+            "fsk_get_mismatch_times": ([vp, vp, vp, i32], C.c_int),
+            "fsk_mismatch_levels": ([i32, vp, i32, vp, C.POINTER(i32)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -236,6 +240,16 @@ class Library:
 
     def device_count(self):
         return int(self.L.fsk_device_count())
+
+    def mismatch_levels(self, g, weights):
+        """``fsk_mismatch_levels``: the level coefficients a_0..a_d of the mismatch weights c_0..c_{n-1} at window length g."""
+        c = np.ascontiguousarray([int(w) for w in weights], dtype=np.uint64)
+        a = np.zeros(max(len(c), 1), dtype=np.int64)
+        n = C.c_int32(0)
+        rc = self.L.fsk_mismatch_levels(g, c.ctypes.data, len(c), a.ctypes.data, C.byref(n))
+        if rc:
+            raise FskError(rc, (self.L.fsk_last_error(None) or b"").decode())
+        return [int(v) for v in a[:n.value]]
 
     def tuning_keys(self):
         """{key: (default, lowest, highest, what it does)} — every knob fsk_set_tuning / FSK_TUNING takes."""
@@ -285,6 +299,58 @@ def complement_arrays(mapping):
     return (np.array([k for k, _ in pairs], dtype=np.int32), np.array([v for _, v in pairs], dtype=np.int32))
 
 
+def mismatch_levels(g, weights, lib=None):
+    """The level coefficients ``a_0..a_d`` of mismatch weights ``c_0..c_m`` at window length ``g`` (``fsk_mismatch_levels``, host
+    only): ``sum_h c_h N_h == sum_j a_j S_j`` with ``S_j`` the raw kernel of ``(g, m=j)``. ``d`` is the last ``h`` with
+    ``c_h != 0``."""
+    return (lib or library()).mismatch_levels(g, weights)
+
+
+def solve_mismatch_levels(g, weights):
+    """The same recurrence in Python integers (no library): a_d = c_d, a_h = c_h - sum_{j>h} a_j C(g-h, j-h)."""
+    from math import comb
+    c = [int(w) for w in weights]
+    d = max(h for h, w in enumerate(c) if w) if any(c) else 0
+    a = [0] * (d + 1)
+    for h in range(d, -1, -1):
+        a[h] = c[h] - sum(a[j] * comb(g - h, j - h) for j in range(h + 1, d + 1))
+    return a
+
+
+def mismatch_weights(g, m, weights=None, max_mismatches=None):
+    """The ``weights=`` / ``max_mismatches=`` keywords checked and brought to one form: ``None`` (mode off) or the list
+    ``c_0..c_m`` of Python ints. ``max_mismatches=d`` is the gapped k-mer kernel truncated at d mismatches,
+    ``[C(g-h, m-h) if h <= d else 0 for h <= m]``. ``ValueError`` for anything the engine would refuse."""
+    from math import comb
+    if weights is not None and max_mismatches is not None:
+        raise ValueError("give weights= or max_mismatches=, not both")
+    if max_mismatches is not None:
+        if isinstance(max_mismatches, bool) or not isinstance(max_mismatches, (int, np.integer)):
+            raise ValueError("max_mismatches must be an int")
+        if not 0 <= int(max_mismatches) <= m:
+            raise ValueError("max_mismatches must lie in 0..m = %d, got %d" % (m, int(max_mismatches)))
+        weights = [comb(g - h, m - h) if h <= int(max_mismatches) else 0 for h in range(m + 1)]
+    if weights is None:
+        return None
+    if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__"):
+        raise ValueError("weights must be a sequence of m + 1 non-negative ints")
+    out = []
+    for w in weights:
+        if isinstance(w, bool) or not isinstance(w, (int, np.integer)):
+            raise ValueError("weights must be non-negative ints, got %r" % (w,))
+        if not 0 <= int(w) < 2 ** 64:
+            raise ValueError("weights must lie in 0 .. 2^64 - 1, got %r" % (w,))
+        out.append(int(w))
+    if len(out) != m + 1:
+        raise ValueError("weights must hold m + 1 = %d values, got %d" % (m + 1, len(out)))
+    if out[0] < 1:
+        raise ValueError("weights[0] must be at least 1: it keeps every diagonal positive")
+    for j, a in enumerate(solve_mismatch_levels(g, out)):
+        if not -2 ** 63 <= a < 2 ** 63:
+            raise ValueError("weights: the coefficient of level %d, %d, does not fit 64 bits" % (j, a))
+    return out
+
+
 def flatten(X):
     """Nested int sequences (or a 2-D array) -> (tokens int32, offsets int64)."""
     if isinstance(X, np.ndarray) and X.ndim == 2:
@@ -305,7 +371,13 @@ class Engine:
 
     def __init__(self, g, m, t=-1, approx=False, delta=0.025, max_iters=-1, skip_variance=False, device=0,
                  path=PATH_AUTO, profile=False, lib=None, skip_test_block=False, devices=None, collective=COLL_AUTO,
-                 bands=0, deadline_ms=0, tuning=None, revcomp=None):
+                 bands=0, deadline_ms=0, tuning=None, revcomp=None, weights=None, max_mismatches=None):
+        weights = mismatch_weights(g, m, weights, max_mismatches)
+        if weights is not None and approx:
+            raise ValueError("weights= / max_mismatches= with approx=True: a sample of combinations under signed level "
+                             "coefficients estimates nothing")
+        if weights is not None and devices is not None:
+            raise ValueError("weights= / max_mismatches= with devices=[...]: a group of engines does not run the levels")
         self.lib = lib or library()
         if devices is not None:
             devices = [int(d) for d in devices]
@@ -332,12 +404,15 @@ class Engine:
         self.revcomp = False
         for key, value in (tuning or {}).items():
             self.set_tuning(key, value)
-        if revcomp is not None and revcomp is not False:
-            try:
+        self.weights = None
+        try:
+            if revcomp is not None and revcomp is not False:
                 self.set_complement(revcomp)
-            except Exception:
-                self.close()
-                raise
+            if weights is not None:
+                self.set_mismatch_weights(weights)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -393,6 +468,35 @@ class Engine:
             raise ValueError("tokens and complements must be 1-D and of equal length")
         self._ck(self.lib.L.fsk_set_complement(self.h, tokens.ctypes.data, complements.ctypes.data, len(tokens)))
         self.revcomp = len(tokens) > 0
+
+    def set_mismatch_weights(self, weights):
+        """Mismatch-weighted mode from the next ``compute`` on: ``weights`` are ``c_0..c_m`` (``W = sum_h c_h N_h``, N_h the
+        pairs of g-windows at exactly h mismatches); ``None`` or ``[]`` switch it off. Checked here (``ValueError``) as the
+        engine checks it."""
+        if weights is None or len(weights) == 0:
+            self._ck(self.lib.L.fsk_set_mismatch_weights(self.h, None, 0))
+            self.weights = None
+            return
+        weights = mismatch_weights(self.g, self.m, weights)
+        c = np.array(weights, dtype=np.uint64)
+        self._ck(self.lib.L.fsk_set_mismatch_weights(self.h, c.ctypes.data, len(c)))
+        self.weights = weights
+
+    def mismatch_info(self):
+        """What the last ``compute`` did in mismatch-weighted mode: ``{"n_levels": d + 1, "a": [a_0..a_d], "levels":
+        [{"m": j, "k": g - j, "a": a_j, "path": 1 | 2, "ms": host time, "fold_ms": fold time}, ... the levels that ran]}``;
+        ``n_levels == 0`` with the mode off."""
+        n = C.c_int32(0)
+        cap = self.m + 1
+        a = np.zeros(cap, dtype=np.int64)
+        paths = np.zeros(cap, dtype=np.int32)
+        ms = np.zeros(cap, dtype=np.float64)
+        fold = np.zeros(cap, dtype=np.float64)
+        self._ck(self.lib.L.fsk_get_mismatch_info(self.h, C.byref(n), a.ctypes.data, paths.ctypes.data, cap))
+        self._ck(self.lib.L.fsk_get_mismatch_times(self.h, ms.ctypes.data, fold.ctypes.data, cap))
+        levels = [{"m": j, "k": self.g - j, "a": int(a[j]), "path": int(paths[j]), "ms": float(ms[j]), "fold_ms": float(fold[j])}
+                  for j in range(n.value) if a[j] != 0]
+        return {"n_levels": n.value, "a": [int(v) for v in a[:n.value]], "levels": levels}
 
     # ---- staged path
     def bind_counts(self, device_ptr, n_cells, keepalive=None):
@@ -554,4 +658,5 @@ class Engine:
         self._ck(self.lib.L.fsk_get_stats(self.h, C.byref(s)))
         d = s.as_dict()
         d["revcomp"] = self.revcomp  # (as set: in force from the next load on)
+        d["weights"] = None if self.weights is None else list(self.weights)  # (mismatch-weighted mode, as set)
         return d

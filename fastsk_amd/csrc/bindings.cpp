@@ -7,7 +7,7 @@
 //   - errors raise ValueError / RuntimeError instead of printf + exit(1) (fastsk.cpp:53-58);
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
 //     NotImplementedError (they are unusable from Python in the reference as well);
-//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp), numpy and
+//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
 //   - skip_test_block (default False: compute_kernel computes the whole N x N triangle, as fastsk.cpp:30-118 does).
@@ -28,6 +28,10 @@
 //   - revcomp (default None: off): the complement mapping {token_id: token_id} of reverse-complement mode
 //     (fsk_set_complement; FastaUtility.complement() returns it for DNA) — a k-mer is counted together with its reverse
 //     complement, as gkm-SVM / LS-GKM do; the reference has no such mode.
+//   - weights / max_mismatches (default None: off): the mismatch-weighted kernels of fsk_set_mismatch_weights —
+//     weights = c_0..c_m, W = sum_h c_h N_h over the pairs of g-windows at exactly h mismatches; max_mismatches = d is
+//     shorthand for the gapped k-mer kernel truncated at d mismatches, c_h = C(g-h, m-h) for h <= d and 0 beyond (LS-GKM's
+//     "-l g -k g-m -d d"). Checked before any device call (ValueError); not with approx=True or devices=[...].
 #include "../../include/fastsk_amd.h"
 
 namespace py = pybind11;
@@ -123,6 +127,7 @@ class FastSK {
     // skip_test_block="lazy" / None: the test x test block is left out of compute_kernel and computed only if asked for
     bool lazy_test_block_ = false, test_block_missing_ = false;
     bool revcomp_ = false;
+    std::vector<uint64_t> weights_;      // mismatch-weighted mode: c_0..c_m (empty: off)
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
 
@@ -232,8 +237,13 @@ class FastSK {
 public:
     FastSK(int g, int m, int t, bool approx, double delta, int max_iters, bool skip_variance, int device,
            const std::string& path, py::object seed, py::object skip_test_block, py::object devices,
-           const std::string& collective, int deadline_ms, py::object revcomp) {
+           const std::string& collective, int deadline_ms, py::object revcomp, py::object weights, py::object max_mismatches) {
         fsk_config c{};
+        parse_weights(g, m, weights, max_mismatches);  // (host only: ValueError before any device call)
+        if (!weights_.empty() && approx)
+            throw py::value_error("weights= / max_mismatches= with approx=True: a sample of combinations under signed level coefficients estimates nothing");
+        if (!weights_.empty() && !devices.is_none())
+            throw py::value_error("weights= / max_mismatches= with devices=[...]: a group of engines does not run the levels");
         if (skip_test_block.is_none()) lazy_test_block_ = true;
         else if (py::isinstance<py::str>(skip_test_block)) {
             if (skip_test_block.cast<std::string>() != "lazy") throw py::value_error("skip_test_block must be False, True or \"lazy\"");
@@ -262,10 +272,45 @@ public:
         try {
             if (!seed.is_none()) check(fsk_set_seed(h_, seed.cast<uint64_t>()));
             set_revcomp(revcomp);
+            if (!weights_.empty()) check(fsk_set_mismatch_weights(h_, weights_.data(), (int32_t)weights_.size()));
         } catch (...) {
             fsk_destroy(h_);
             h_ = nullptr;
             throw;
+        }
+    }
+    // weights= / max_mismatches= -> weights_ (empty: off), checked as fsk_set_mismatch_weights checks them
+    void parse_weights(int g, int m, const py::object& weights, const py::object& max_mismatches) {
+        weights_.clear();
+        if (weights.is_none() && max_mismatches.is_none()) return;
+        if (!weights.is_none() && !max_mismatches.is_none()) throw py::value_error("give weights= or max_mismatches=, not both");
+        if (g <= 0 || m < 0 || m >= g) throw py::value_error("need 0 <= m < g");
+        if (!max_mismatches.is_none()) {
+            if (!py::isinstance<py::int_>(max_mismatches) || py::isinstance<py::bool_>(max_mismatches)) throw py::value_error("max_mismatches must be an int");
+            const long long d = max_mismatches.cast<long long>();
+            if (d < 0 || d > m) throw py::value_error("max_mismatches must lie in 0..m");
+            for (int h = 0; h <= m; ++h) {
+                const int64_t b = fsk_num_combos(g - h, m - h);
+                if (b >= INT64_MAX / 2) throw py::value_error("max_mismatches: C(g-h, m-h) does not fit 64 bits");
+                weights_.push_back(h <= d ? (uint64_t)b : 0);
+            }
+        } else {
+            if (py::isinstance<py::str>(weights) || py::isinstance<py::bytes>(weights) || !py::isinstance<py::sequence>(weights))
+                throw py::value_error("weights must be a sequence of m + 1 non-negative ints");
+            for (auto w : weights.cast<py::sequence>()) {
+                if (!py::isinstance<py::int_>(w) || py::isinstance<py::bool_>(w)) throw py::value_error("weights must be non-negative ints");
+                const unsigned long long v = PyLong_AsUnsignedLongLong(w.ptr());
+                if (v == (unsigned long long)-1 && PyErr_Occurred()) { PyErr_Clear(); throw py::value_error("weights must lie in 0 .. 2^64 - 1"); }
+                weights_.push_back((uint64_t)v);
+            }
+            if ((int)weights_.size() != m + 1) { weights_.clear(); throw py::value_error("weights must hold m + 1 values"); }
+        }
+        if (weights_[0] < 1) { weights_.clear(); throw py::value_error("weights[0] must be at least 1: it keeps every diagonal positive"); }
+        std::vector<int64_t> a(weights_.size());
+        int32_t n_levels = 0;
+        if (fsk_mismatch_levels(g, weights_.data(), (int32_t)weights_.size(), a.data(), &n_levels) != FSK_OK) {
+            weights_.clear();
+            throw py::value_error(fsk_last_error(nullptr));
         }
     }
     // None / False: off; else a mapping {token_id: token_id} that fsk_set_complement checks (ValueError)
@@ -411,6 +456,13 @@ public:
         d["cell_updates"] = s.cell_updates; d["launches"] = s.launches;
         d["test_block_computed"] = computed_ && !test_block_missing_;
         d["revcomp"] = revcomp_;
+        if (weights_.empty()) d["weights"] = py::none();
+        else {
+            py::list w;
+            for (uint64_t v : weights_) w.append(py::int_(v));
+            d["weights"] = w;
+        }
+        d["mismatch_levels"] = mismatch_info()["levels"];
         fsk_multi_info mi;
         check(fsk_get_multi_info(h_, &mi));
         py::list devs;
@@ -419,6 +471,31 @@ public:
         d["devices"] = devs;
         d["collective"] = mi.ndev == 0 ? "none" : mi.collective == FSK_COLL_RCCL ? "rccl" : "p2p";
         d["comm_ranks"] = mi.comm_ranks; d["exchange_bands"] = mi.bands; d["exchange_int32"] = (bool)mi.narrow;
+        return d;
+    }
+    // what the last compute did in mismatch-weighted mode (fsk_get_mismatch_info): n_levels = 0 with the mode off
+    py::dict mismatch_info() const {
+        int32_t n = 0;
+        check(fsk_get_mismatch_info(h_, &n, nullptr, nullptr, 0));
+        std::vector<int64_t> a((size_t)n);
+        std::vector<int32_t> paths((size_t)n);
+        std::vector<double> ms((size_t)n), fold((size_t)n);
+        if (n) {
+            check(fsk_get_mismatch_info(h_, &n, a.data(), paths.data(), n));
+            check(fsk_get_mismatch_times(h_, ms.data(), fold.data(), n));
+        }
+        py::list levels, coeff;
+        for (int32_t j = 0; j < n; ++j) {
+            coeff.append(a[(size_t)j]);
+            if (a[(size_t)j] == 0) continue;
+            py::dict lv;
+            lv["m"] = j; lv["a"] = a[(size_t)j];
+            lv["path"] = paths[(size_t)j] == FSK_PATH_DENSE ? "dense" : "sparse";
+            lv["ms"] = ms[(size_t)j]; lv["fold_ms"] = fold[(size_t)j];
+            levels.append(lv);
+        }
+        py::dict d;
+        d["n_levels"] = n; d["a"] = coeff; d["levels"] = levels;
         return d;
     }
     void fit(double, double, double, const std::string&) const {
@@ -439,12 +516,12 @@ PYBIND11_MODULE(_fastsk, m) {
     m.doc() = "MI355X-native gapped-k-mer kernel engine behind the FastSK Python surface";
     py::class_<FastSK>(m, "FastSK")
         .def(py::init<int, int, int, bool, double, int, bool, int, const std::string&, py::object, py::object, py::object,
-                      const std::string&, int, py::object>(),
+                      const std::string&, int, py::object, py::object, py::object>(),
              py::arg("g"), py::arg("m"), py::arg("t") = -1, py::arg("approx") = false, py::arg("delta") = 0.025,
              py::arg("max_iters") = -1, py::arg("skip_variance") = false, py::arg("device") = 0,
              py::arg("path") = "auto", py::arg("seed") = py::none(), py::arg("skip_test_block") = false,
              py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0,
-             py::arg("revcomp") = py::none())
+             py::arg("revcomp") = py::none(), py::arg("weights") = py::none(), py::arg("max_mismatches") = py::none())
         .def("compute_kernel", &FastSK::compute_kernel, py::arg("Xtrain"), py::arg("Xtest"))
         .def("compute_kernel_flat", &FastSK::compute_kernel_flat, py::arg("tokens").noconvert(), py::arg("offsets").noconvert(),
              py::arg("n_train"))
@@ -469,7 +546,16 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("get_counts_cells", &FastSK::get_counts_cells, py::arg("rows"), py::arg("cols"))
         .def("get_triangle_dlpack", &FastSK::get_triangle_dlpack)
         .def("set_combo_order", &FastSK::set_combo_order, py::arg("order"))
+        .def("mismatch_info", &FastSK::mismatch_info)
         .def("stats", &FastSK::stats);
+    // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
+    m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {
+        std::vector<int64_t> a(weights.size() + 1);
+        int32_t n = 0;
+        if (fsk_mismatch_levels(g, weights.data(), (int32_t)weights.size(), a.data(), &n) != FSK_OK) throw py::value_error(fsk_last_error(nullptr));
+        a.resize((size_t)n);
+        return a;
+    }, py::arg("g"), py::arg("weights"));
     m.attr("__version__") = "dev";
     m.attr("abi_version") = fsk_abi_version();
 }

@@ -11,6 +11,11 @@
 
 using namespace fsk_detail;
 
+// the staged calls in mismatch-weighted mode: their combination ids would belong to one level only
+#define FSK_NOT_STAGED(e, what)                                                                                              \
+    if ((e)->mm_on())                                                                                                        \
+        return (e)->fail(FSK_ESTATE, what ": the staged path does not exist in mismatch-weighted mode (fsk_set_mismatch_weights): fsk_compute is the entry point")
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -476,7 +481,7 @@ void fsk_detail::one_destroy(fsk_engine* e) {
     if (e->lazy_open) (void)hipEventDestroy(e->lazy_open);
     for (hipEvent_t ev : e->lazy_free) (void)hipEventDestroy(ev);
     for (auto& lane : e->sxs) lane.release();
-    e->d_owner_r0.release(); e->d_U.release(); e->d_U2.release(); e->d_stage32.release(); e->d_blk_r0.release();
+    e->d_owner_r0.release(); e->d_U.release(); e->d_U2.release(); e->d_stage32.release(); e->d_blk_r0.release(); e->mm_scratch.release();
     if (e->h_prod) (void)hipHostFree(e->h_prod);
     if (e->h_sx_pos) (void)hipHostFree(e->h_sx_pos);
     if (e->h_sx_stat) (void)hipHostFree(e->h_sx_stat);
@@ -553,6 +558,7 @@ int fsk_set_seed(fsk_engine* e, uint64_t seed) {
 
 int fsk_load_sequences(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_load_sequences");
     return e->group ? group_load_sequences(e, tokens, offsets, n_train, n_test) : one_load_sequences(e, tokens, offsets, n_train, n_test);
 }
 
@@ -974,17 +980,20 @@ int fsk_counts_device_ptr(fsk_engine* e, void** out) {
 
 int fsk_reset_counts(fsk_engine* e) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_reset_counts");
     return e->group ? group_reset_counts(e, 0, -1) : one_reset_counts(e);
 }
 
 int fsk_reset_counts_rows(fsk_engine* e, int64_t row_begin, int64_t row_end) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_reset_counts_rows");
     if (e->group && (row_begin < 0 || row_end < row_begin)) return e->fail(FSK_EINVAL, "bad row range");
     return e->group ? group_reset_counts(e, row_begin, row_end) : one_reset_counts_rows(e, row_begin, row_end);
 }
 
 int fsk_accumulate(fsk_engine* e, const int32_t* combos, int32_t n) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_accumulate");
     if (!e->loaded) return e->fail(FSK_ESTATE, "load sequences first");
     if (n < 0 || (n > 0 && !combos)) return e->fail(FSK_EINVAL, "bad combo list");
     if (e->group) return group_accumulate(e, combos, n);
@@ -993,6 +1002,7 @@ int fsk_accumulate(fsk_engine* e, const int32_t* combos, int32_t n) {
 
 int fsk_accumulate_rows(fsk_engine* e, const int32_t* combos, int32_t n, int64_t row_begin, int64_t row_end) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_accumulate_rows");
     if (e->group) return e->fail(FSK_ESTATE, "fsk_accumulate_rows is a single-engine call: a group bands its accumulate itself");
     return one_accumulate_rows(e, combos, n, row_begin, row_end);
 }
@@ -1032,8 +1042,17 @@ int fsk_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, in
     if (!e) return FSK_EINVAL;
     if (e->group) return group_compute(e, tokens, offsets, n_train, n_test);
     FSK_ON_DEVICE(e);
+    e->mm_ran_a.clear(); e->mm_ran_path.clear(); e->mm_ran_level_ms.clear(); e->mm_ran_fold_ms.clear();
+    if (e->mm_on() && !e->mm_plain) return mismatch_compute(e, tokens, offsets, n_train, n_test);
     int rc = one_load_sequences(e, tokens, offsets, n_train, n_test);
     if (rc) return rc;
+    if (e->mm_on()) {  // the weights are this kernel's own (a = e_m): one level, and it is the plain compute below
+        e->mm_ran_a = e->mm_a;
+        e->mm_ran_path.assign(e->mm_a.size(), 0);
+        e->mm_ran_path.back() = e->path;
+        e->mm_ran_level_ms.assign(e->mm_a.size(), 0.0);
+        e->mm_ran_fold_ms.assign(e->mm_a.size(), 0.0);
+    }
     const fsk_config& c = e->cfg;
     if (!c.approx) {  // exact: every combination, order irrelevant (integer sum)
         std::vector<int32_t> all((size_t)e->ncomb);
@@ -1057,6 +1076,7 @@ int fsk_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, in
 
 int fsk_run_chains(fsk_engine* e, int32_t first, int32_t step) {
     if (!e) return FSK_EINVAL;
+    FSK_NOT_STAGED(e, "fsk_run_chains");
     if (e->group) return e->fail(FSK_ESTATE, "fsk_run_chains is a single-engine call: a group deals its chains itself (fsk_compute)");
     if (!e->loaded) return e->fail(FSK_ESTATE, "load sequences first");
     const fsk_config& c = e->cfg;
@@ -1481,6 +1501,225 @@ extern "C" const char* fsk_tuning_keys(void) {
     }();
     return text.c_str();
 }
+
+// =============================================================================================
+// MISMATCH-WEIGHTED KERNELS (fsk_set_mismatch_weights): W = sum_h c_h N_h as sum_j a_j S_j over the raw triangles S_j of the
+// levels (g, m = j), each run by an engine of its own into one scratch triangle and folded into K by k_tri_fold.
+namespace fsk_detail {
+
+namespace {
+typedef __int128 i128;
+// C(n, k) exactly, or false when it passes 2^126
+bool binom_i128(int n, int k, i128* out) {
+    if (k < 0 || k > n) { *out = 0; return true; }
+    if (k * 2 > n) k = n - k;
+    u128 r = 1;
+    const u128 limit = (u128)1 << 126;
+    for (int i = 1; i <= k; ++i) {
+        const u128 f = (u128)(n - k + i);
+        if (r > limit / f) return false;
+        r = r * f / (u128)i;
+    }
+    *out = (i128)r;
+    return true;
+}
+}  // namespace
+
+int mismatch_solve(int g, const uint64_t* c, int n, std::vector<int64_t>& a, std::string& why) {
+    a.clear();
+    if (g <= 0 || g > 255 || !c || n < 1 || n > g) { why = "mismatch weights: need 1 <= n <= g <= 255 weights"; return FSK_EINVAL; }
+    if (c[0] < 1) { why = "mismatch weights: c[0] must be at least 1 (it keeps every diagonal positive)"; return FSK_EINVAL; }
+    int d = n - 1;
+    while (d > 0 && c[d] == 0) --d;
+    a.assign((size_t)d + 1, 0);
+    const i128 lo = (i128)INT64_MIN, hi = (i128)INT64_MAX;
+    for (int h = d; h >= 0; --h) {
+        i128 v = (i128)c[h];
+        for (int j = h + 1; j <= d; ++j) {
+            if (a[(size_t)j] == 0) continue;
+            i128 b = 0, term = 0;
+            // (128-bit intermediates; a product or a sum that leaves them is reported like a coefficient that leaves int64)
+            if (!binom_i128(g - h, j - h, &b) || __builtin_mul_overflow((i128)a[(size_t)j], b, &term) || __builtin_sub_overflow(v, term, &v)) {
+                why = "mismatch weights: the coefficient of level " + std::to_string(h) + " does not fit 64 bits";
+                a.clear();
+                return FSK_EINVAL;
+            }
+        }
+        if (v < lo || v > hi) {
+            why = "mismatch weights: the coefficient of level " + std::to_string(h) + " does not fit 64 bits";
+            a.clear();
+            return FSK_EINVAL;
+        }
+        a[(size_t)h] = (int64_t)v;
+    }
+    return FSK_OK;
+}
+
+// K = (first ? 0 : K) + a * S over the whole triangle, on the engine's stream; HIP-event milliseconds into *ms
+static int fold_level(fsk_engine* e, int64_t a, bool first, double* ms) {
+    const u64 n = (u64)e->pairs;
+    const bool vec = ((uintptr_t)e->d_K % 16 == 0) && ((uintptr_t)e->mm_scratch.p % 16 == 0);
+    const u64 n2 = vec ? n / 2 : 0;
+    const u64 work = std::max<u64>(std::max<u64>(n2, n - 2 * n2), 1);
+    const uint32_t blocks = (uint32_t)std::min<u64>((work + 255) / 256, (u64)e->n_cu * 8);  // (a streaming pass: eight workgroups a compute unit, grid-stride beyond)
+    FSK_HIP(hipEventRecord(e->ev0, e->stream));
+    FSK_LAUNCH(fsk::k_tri_fold, dim3(blocks), dim3(256), 0, e->stream, e->d_K, (const u64*)e->mm_scratch.p, (u64)a, n2, n, first ? 1 : 0);
+    FSK_HIP(hipEventRecord(e->ev1, e->stream));
+    FSK_HIP(hipEventSynchronize(e->ev1));  // (the next level overwrites the scratch triangle from another stream)
+    FSK_HIP(hipGetLastError());
+    float t = 0;
+    (void)hipEventElapsedTime(&t, e->ev0, e->ev1);
+    *ms = (double)t;
+    e->st.launches += 1;
+    return FSK_OK;
+}
+
+int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test) {
+    int rc = one_load_sequences(e, tokens, offsets, n_train, n_test);
+    if (rc) return rc;
+    e->lazy_lo = e->lazy_hi = -1;  // (the first fold stores every cell: no zeros are owed)
+    const int g = e->cfg.g, d = (int)e->mm_a.size() - 1;
+    // a failure from here on leaves the handle as it was before any sequences were loaded
+    auto give_up = [&](int code) { e->loaded = false; e->finalized = false; return code; };
+    for (int j = 0; j <= d; ++j) {  // a level's k-mer must fit the sort records (fsk_load_sequences' rule, at k = g - j)
+        if (e->mm_a[(size_t)j] == 0) continue;
+        u64 V = 1;
+        bool wide = false;
+        for (int q = 0; q < g - j; ++q) {
+            if (V > (((u64)1 << 62) / e->sigma)) { wide = true; break; }
+            V *= e->sigma;
+        }
+        int symbits = 1;
+        while (((u64)1 << symbits) < e->sigma) ++symbits;
+        if (wide && (int64_t)symbits * (g - j) > 96)
+            return give_up(e->fail(FSK_EUNSUPPORTED, "mismatch-weighted mode, level %d: a k-mer of %d symbols of %d bits does not fit the 128-bit sort records", j,
+                                   g - j, symbits));
+    }
+    {
+        const uint64_t cmax = *std::max_element(e->mm_c.begin(), e->mm_c.end());
+        if ((u128)cmax * (u128)e->maxW * (u128)e->maxW >= ((u128)1 << 64))
+            return give_up(e->fail(FSK_EUNSUPPORTED, "mismatch-weighted mode: largest weight %llu x max_windows^2 = %u^2 reaches 2^64: the sums would not be exact",
+                                   (unsigned long long)cmax, e->maxW));
+    }
+    if (e->mm_scratch.reserve((size_t)e->pairs) != hipSuccess) {
+        (void)hipGetLastError();
+        return give_up(e->fail(FSK_ENOMEM, "mismatch-weighted mode: cannot allocate the %lld-cell scratch triangle", (long long)e->pairs));
+    }
+    e->mm_ran_a = e->mm_a;
+    e->mm_ran_path.assign((size_t)d + 1, 0);
+    e->mm_ran_level_ms.assign((size_t)d + 1, 0.0);
+    e->mm_ran_fold_ms.assign((size_t)d + 1, 0.0);
+    fsk_stats sum{};
+    bool first = true;
+    for (int step = 0; step <= d; ++step) {
+        const int j = e->tune.mismatch_order ? d - step : step;
+        const int64_t a = e->mm_a[(size_t)j];
+        if (a == 0) continue;
+        const auto t0 = std::chrono::steady_clock::now();
+        // the level (g, m = j): an engine of its own on this device, bound to the scratch triangle, gone before the next one
+        fsk_config cfg = e->cfg;
+        cfg.m = j;
+        cfg.approx = 0;
+        fsk_engine* lv = nullptr;
+        rc = fsk_create(&cfg, &lv);
+        if (rc) return give_up(e->fail(rc, "mismatch-weighted mode, level %d: %s", j, fsk_last_error(nullptr)));
+        lv->tune = e->tune;
+        lv->cfg.profile = e->cfg.profile;
+        lv->cfg_profile0 = e->cfg_profile0;
+        lv->rc_tokens = e->rc_tokens;
+        lv->rc_comps = e->rc_comps;
+        rc = fsk_bind_counts(lv, e->mm_scratch.p, e->pairs);
+        if (!rc) rc = one_load_sequences(lv, tokens, offsets, n_train, n_test);  // (zeroes the bound triangle, or owes the zeros to the first tile launch)
+        if (!rc) {
+            std::vector<int32_t> all((size_t)lv->ncomb);
+            for (int64_t i = 0; i < lv->ncomb; ++i) all[(size_t)i] = (int32_t)i;
+            rc = do_accumulate(lv, all.data(), (int)all.size(), lv->d_K);
+        }
+        if (!rc) rc = one_synchronize(lv);
+        fsk_stats ls{};
+        if (!rc) rc = one_get_stats(lv, &ls);
+        if (rc) {
+            const std::string why = lv->err;
+            one_destroy(lv);
+            return give_up(e->fail(rc, "mismatch-weighted mode, level %d (g = %d, m = %d): %s", j, g, j, why.c_str()));
+        }
+        e->mm_ran_path[(size_t)j] = lv->path;
+        one_destroy(lv);
+        sum.launches += ls.launches; sum.combos_done += ls.combos_done; sum.combos_issued += ls.combos_issued;
+        sum.cell_updates += ls.cell_updates; sum.sort_records += ls.sort_records; sum.sort_passes = std::max(sum.sort_passes, ls.sort_passes);
+        sum.ms_count += ls.ms_count; sum.ms_tile += ls.ms_tile; sum.ms_extract += ls.ms_extract; sum.ms_sort += ls.ms_sort;
+        sum.ms_segment += ls.ms_segment; sum.ms_pairs += ls.ms_pairs; sum.ms_total += ls.ms_total;
+        sum.n_tile_launches += ls.n_tile_launches; sum.dense_macs += ls.dense_macs; sum.panel_bytes += ls.panel_bytes;
+        sum.u4_tile_launches += ls.u4_tile_launches; sum.count_launches += ls.count_launches; sum.batches_redone += ls.batches_redone;
+        e->mm_ran_level_ms[(size_t)j] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        rc = fold_level(e, a, first, &e->mm_ran_fold_ms[(size_t)j]);
+        if (rc) return give_up(rc);
+        first = false;
+    }
+    // what the levels did, summed, in the statistics of this handle
+    fsk_stats& st = e->st;
+    st.launches += sum.launches; st.combos_done = sum.combos_done; st.combos_issued = sum.combos_issued;
+    st.sort_records = sum.sort_records; st.sort_passes = sum.sort_passes;
+    st.ms_count = sum.ms_count; st.ms_tile = sum.ms_tile; st.ms_extract = sum.ms_extract; st.ms_sort = sum.ms_sort;
+    st.ms_segment = sum.ms_segment; st.ms_pairs = sum.ms_pairs; st.ms_total = sum.ms_total;
+    st.n_tile_launches = sum.n_tile_launches; st.dense_macs = sum.dense_macs; st.panel_bytes = sum.panel_bytes;
+    st.u4_tile_launches = sum.u4_tile_launches; st.count_launches = sum.count_launches;
+    e->u_extra = sum.cell_updates;
+    return make_diag(e);
+}
+
+}  // namespace fsk_detail
+
+extern "C" {
+
+int fsk_mismatch_levels(int32_t g, const uint64_t* c, int32_t n, int64_t* a, int32_t* n_levels) {
+    if (!a || !n_levels) return FSK_EINVAL;
+    std::vector<int64_t> av;
+    std::string why;
+    const int rc = fsk_detail::mismatch_solve(g, c, n, av, why);
+    if (rc) { g_create_error = why; return rc; }
+    for (size_t j = 0; j < av.size(); ++j) a[j] = av[j];
+    *n_levels = (int32_t)av.size();
+    return FSK_OK;
+}
+
+int fsk_set_mismatch_weights(fsk_engine* e, const uint64_t* c, int32_t n) {
+    if (!e) return FSK_EINVAL;
+    if (e->group) return e->fail(FSK_EUNSUPPORTED, "mismatch weights on a group handle (fsk_create_multi) are not supported");
+    if (n == 0) { e->mm_c.clear(); e->mm_a.clear(); e->mm_plain = false; return FSK_OK; }
+    if (e->cfg.approx) return e->fail(FSK_EUNSUPPORTED, "mismatch weights with approx = 1: a sample of combinations under signed level coefficients estimates nothing");
+    if (n != e->cfg.m + 1 || !c) return e->fail(FSK_EINVAL, "mismatch weights: need m + 1 = %d weights, got %d", e->cfg.m + 1, n);
+    std::vector<int64_t> a;
+    std::string why;
+    const int rc = mismatch_solve(e->cfg.g, c, n, a, why);
+    if (rc) return e->fail(rc, "%s", why.c_str());
+    e->mm_c.assign(c, c + n);
+    e->mm_a = a;
+    e->mm_plain = (int)a.size() == n && a.back() == 1;
+    for (size_t j = 0; j + 1 < a.size(); ++j) e->mm_plain = e->mm_plain && a[j] == 0;
+    return FSK_OK;
+}
+
+int fsk_get_mismatch_info(fsk_engine* e, int32_t* n_levels, int64_t* a, int32_t* paths, int32_t cap) {
+    if (!e || !n_levels) return FSK_EINVAL;
+    *n_levels = (int32_t)e->mm_ran_a.size();
+    for (int32_t j = 0; j < *n_levels && j < cap; ++j) {
+        if (a) a[j] = e->mm_ran_a[(size_t)j];
+        if (paths) paths[j] = e->mm_ran_path[(size_t)j];
+    }
+    return FSK_OK;
+}
+
+int fsk_get_mismatch_times(fsk_engine* e, double* level_ms, double* fold_ms, int32_t cap) {
+    if (!e) return FSK_EINVAL;
+    for (int32_t j = 0; j < (int32_t)e->mm_ran_a.size() && j < cap; ++j) {
+        if (level_ms) level_ms[j] = e->mm_ran_level_ms[(size_t)j];
+        if (fold_ms) fold_ms[j] = e->mm_ran_fold_ms[(size_t)j];
+    }
+    return FSK_OK;
+}
+
+}  // extern "C"
 
 #ifdef FSK_TEST_HOOKS
 // ---- test builds only (tests/hooks, the CPU emulation; never the product): the hand-written wave primitives of fsk_gfx950.h,

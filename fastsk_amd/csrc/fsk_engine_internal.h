@@ -121,6 +121,7 @@ using fsk_detail::DevBuf;
     X(sparse_desc_parts, 2048, 1, 1 << 16, "sparse, descriptors: parts (k_sx_consume workgroups) the bands' streams are cut into, about") \
     X(sparse_share, 0, -1, 254, "sparse: leading kept positions sorted once per group of consecutive combos that share them (0: by cost; -1: never); batches of more than 16 slots only (smaller ones read their positions by id), and never when the presort's scratch passes a quarter of the free memory") \
     X(seed_splitmix, 0, 0, 1, "approx modes: 1 = fsk_set_seed draws the engine's older splitmix64 Fisher-Yates order (0: the reference's std::shuffle of minstd_rand0)") \
+    X(mismatch_order, 0, 0, 1, "mismatch-weighted mode: 1 = the levels run from m = d down to 0 (0: from 0 up to d)")                   \
     X(collective, 0, 0, 2, "fsk_create_multi: FSK_COLL_* when fsk_config.collective is FSK_COLL_AUTO")                                \
     X(deadline_ms, 120000, -1, 86400000, "fsk_create_multi: the fail-fast bound when fsk_config.deadline_ms is 0 (negative: none)")   \
     FSK_TUNING_TEST_KEYS(X)
@@ -212,6 +213,18 @@ struct fsk_engine {
     bool revcomp = false;
     uint32_t maxW1 = 0;
     DevBuf<uint16_t> d_comp;
+
+    // mismatch-weighted mode (fsk_set_mismatch_weights): the weights c_0..c_m as set (empty: off), the level coefficients
+    // a_0..a_d solved from them, and whether they are today's kernel (a = e_m: nothing of the mode runs). mm_scratch holds
+    // one level's raw triangle between its accumulate and its fold into K. mm_ran_*: what the last fsk_compute did.
+    std::vector<uint64_t> mm_c;
+    std::vector<int64_t> mm_a;
+    bool mm_plain = false;
+    DevBuf<u64> mm_scratch;
+    std::vector<int64_t> mm_ran_a;
+    std::vector<int32_t> mm_ran_path;
+    std::vector<double> mm_ran_level_ms, mm_ran_fold_ms;
+    bool mm_on() const { return !mm_c.empty(); }
 
     // combos
     std::vector<uint8_t> all_pos;  // [ncomb][k]
@@ -470,6 +483,10 @@ void one_destroy(fsk_engine* e);
 // the combos the approx modes accumulate as plain integer sums (skip_variance): fastsk_kernel.cpp:148,275
 void skip_variance_combos(fsk_engine* e, std::vector<int32_t>& used);
 int approx_chains(const fsk_engine* e);  // T of fastsk_kernel.cpp:54-61
+// mismatch-weighted mode: the level coefficients a_0..a_d of the weights c_0..c_{n-1} at window length g (FSK_EINVAL, `why`
+// set, when c_0 = 0 or a coefficient does not fit int64); fsk_compute with the mode on and a != e_m
+int mismatch_solve(int g, const uint64_t* c, int n, std::vector<int64_t>& a, std::string& why);
+int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test);
 
 // fsk_multi.hip: the same calls on a group (e->group != nullptr)
 int group_load_sequences(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test);

@@ -104,4 +104,35 @@ __global__ __launch_bounds__(256) void k_digest(const u64* K, u64 c0, u64 count,
     }
 }
 
+// The level fold of the mismatch-weighted mode (fsk_set_mismatch_weights): K[i] = (first ? 0 : K[i]) + a * S[i] mod 2^64
+// over the n cells of a triangle, S the raw triangle of one level (g, m = j) and a its signed coefficient as a 64-bit
+// pattern. The first level stores, so K needs no zero fill. A pure streaming pass, 16 (first) or 24 bytes a cell: a lane
+// moves two cells per 16-byte load and store over the n2 pairs (n2 = n / 2 when both pointers are 16-byte aligned, else 0),
+// the cells from 2 * n2 on are the scalar tail. Grid-stride with a 64-bit index (N = 100,000: 5 * 10^9 cells); the host
+// sizes the grid from the compute units.
+__global__ __launch_bounds__(256) void k_tri_fold(u64* __restrict__ K, const u64* __restrict__ S, u64 a, u64 n2, u64 n, int first) {
+    const u64 stride = (u64)gridDim.x * 256;
+    const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
+    ulonglong2* K2 = reinterpret_cast<ulonglong2*>(K);
+    const ulonglong2* S2 = reinterpret_cast<const ulonglong2*>(S);
+    if (first) {
+        for (u64 i = t; i < n2; i += stride) {
+            const ulonglong2 s = S2[i];
+            ulonglong2 k;
+            k.x = a * s.x;
+            k.y = a * s.y;
+            K2[i] = k;
+        }
+    } else {
+        for (u64 i = t; i < n2; i += stride) {
+            const ulonglong2 s = S2[i];
+            ulonglong2 k = K2[i];
+            k.x += a * s.x;
+            k.y += a * s.y;
+            K2[i] = k;
+        }
+    }
+    for (u64 i = 2 * n2 + t; i < n; i += stride) K[i] = (first ? 0ull : K[i]) + a * S[i];
+}
+
 }  // namespace fsk

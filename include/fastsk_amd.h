@@ -33,7 +33,7 @@ extern "C" {
                               4: fsk_set_tuning / fsk_get_tuning / fsk_tuning_keys (one FSK_TUNING variable instead of
                                  two dozen FSK_* switches);
                               5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
-                                 (added since, no layout changed: fsk_set_complement) */
+                                 (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers) */
 
 enum {
     FSK_OK = 0,
@@ -224,6 +224,33 @@ int fsk_set_seed(fsk_engine* e, uint64_t seed);
  * a load is the closure under the map of the tokens present. */
 int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 
+/* Mismatch-weighted kernels (the mismatch-truncated gapped k-mer kernel LS-GKM ships as "-l 11 -k 7 -d 3", the l-mer
+ * filters of Ghandi et al., "pairs of l-mers within d mismatches"). With N_h(x, y) the number of pairs (one g-window of x,
+ * one of y) that differ in exactly h positions, the kernel of this header is K = sum_{h<=m} C(g-h, m-h) N_h; this call
+ * replaces the binomial weights by c[0..m] (non-negative integers; scale rational weights, the normalised kernel does
+ * not see the scale):   W(x, y) = sum_{h<=m} c[h] N_h(x, y),   exact in 64 bits.
+ * How: the raw triangle S_j of (g, m = j) over all its C(g, j) combinations is sum_{h<=j} C(g-h, j-h) N_h; with d the last
+ * h whose c[h] != 0 and a_d = c[d], a_h = c[h] - sum_{j=h+1..d} a_j C(g-h, j-h) (h = d-1 .. 0; signed),
+ * W = sum_{j<=d} a_j S_j mod 2^64 cell for cell — pairs further apart than d cancel. fsk_compute runs the levels with
+ * a_j != 0 one after another (each with this engine's device, path, skip_test_block, tuning and complement map) into one
+ * scratch triangle and folds it into the result (k_tri_fold); peak device memory is the result triangle, one scratch
+ * triangle and one level's working set. When c is this header's own weights (a = e_m) nothing of that runs.
+ * n = 0 switches the mode off (the default); otherwise n == m + 1 and c[0] >= 1 (every diagonal stays positive), else
+ * FSK_EINVAL; FSK_EINVAL when a coefficient does not fit int64; FSK_EUNSUPPORTED on a group handle and on an engine
+ * created with approx = 1 (a sample of combinations under signed coefficients estimates nothing). Takes effect from the
+ * next fsk_compute. With the mode on fsk_compute is the entry point: fsk_load_sequences, fsk_accumulate*,
+ * fsk_reset_counts* and fsk_run_chains return FSK_ESTATE (their combination ids belong to one level); every getter,
+ * fsk_finalize and fsk_save_kernel work on W as they do on K. fsk_compute returns FSK_EUNSUPPORTED, naming the level,
+ * when a level's k-mer does not fit the sort records ((g-j) * bits a symbol > 96), and when
+ * max(c) * max_windows^2 >= 2^64 (the bound that makes the sums mod 2^64 exact); the engine stays usable. */
+int fsk_set_mismatch_weights(fsk_engine* e, const uint64_t* c, int32_t n);
+/* What the last fsk_compute did in that mode: *n_levels = d + 1 (0: mode off), and for j < min(cap, d + 1) the
+ * coefficient a[j] (0: the level was skipped) and the dataflow paths[j] (FSK_PATH_DENSE / FSK_PATH_SPARSE) it took. */
+int fsk_get_mismatch_info(fsk_engine* e, int32_t* n_levels, int64_t* a, int32_t* paths, int32_t cap);
+/* ... and how long it took, in milliseconds: level_ms[j] the host time of level j (load, accumulate, wait), fold_ms[j]
+ * the HIP-event time of its fold; zeros for skipped levels and when the weights were this header's own. */
+int fsk_get_mismatch_times(fsk_engine* e, double* level_ms, double* fold_ms, int32_t cap);
+
 /* ---- staged path (multi-GPU sharding, benchmarking with inputs resident in HBM) ------------ */
 /* lengths check + dictionary + packing + H2D: fastsk.cpp:32-88 (extractFeatures is replaced by
  * bit-packed sequences that every combo re-reads) */
@@ -333,6 +360,9 @@ int fsk_combo_positions(int32_t g, int32_t k, int64_t combo, int32_t* out); /* g
 /* the permutation of 0..n-1 that std::shuffle(begin, end, std::default_random_engine{seed}) of libstdc++ produces
  * (fastsk_kernel.cpp:31-38 with n = C(g,m) and seed = time(0)); host only */
 int fsk_seed_order(uint64_t seed, int64_t n, int32_t* out);
+/* the solver of fsk_set_mismatch_weights on its own: weights c[0..n-1] (n <= g, c[0] >= 1) at window length g ->
+ * coefficients a[0..d] (room for n) and *n_levels = d + 1, d the last h with c[h] != 0; FSK_EINVAL as above; host only */
+int fsk_mismatch_levels(int32_t g, const uint64_t* c, int32_t n, int64_t* a, int32_t* n_levels);
 
 
 /* ---- input: native counterpart of FastaUtility.read_data + Vocabulary (src/fastsk/utils.py:5-96)
