@@ -76,7 +76,8 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_run_chains", "fsk_get_kernel_sum_device", "fsk_set_kernel_sum_device", "fsk_create_multi", "fsk_get_multi_info",
            "fsk_counts_digest", "fsk_alloc_block_device", "fsk_free_device", "fsk_set_skip_test_block",
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
-           "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels"]
+           "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
+           "fsk_set_wildcards"]
 
 
 _hip_shared = False
@@ -209,6 +210,7 @@ class Library:
             "fsk_tuning_keys": ([], C.c_char_p),
             "fsk_seed_order": ([C.c_uint64, i64, vp], C.c_int),
             "fsk_set_complement": ([vp, vp, vp, i32], C.c_int),
+            "fsk_set_wildcards": ([vp, vp, i32], C.c_int),
             "fsk_set_mismatch_weights": ([vp, vp, i32], C.c_int),
             "fsk_get_mismatch_info": ([vp, C.POINTER(i32), vp, vp, i32], C.c_int),
             "fsk_get_mismatch_times": ([vp, vp, vp, i32], C.c_int),
@@ -299,6 +301,26 @@ def complement_arrays(mapping):
     return (np.array([k for k, _ in pairs], dtype=np.int32), np.array([v for _, v in pairs], dtype=np.int32))
 
 
+def wildcard_array(wildcards):
+    """The ``wildcards=`` keyword -> int32 array for ``fsk_set_wildcards``, checked as the engine checks it (integers that
+    fit 32 bits, none listed twice): ``ValueError`` otherwise. ``None`` / ``False`` / an empty sequence: an empty array, i.e.
+    the mode off."""
+    if wildcards is None or wildcards is False:
+        return np.zeros(0, dtype=np.int32)
+    if isinstance(wildcards, (str, bytes)) or not hasattr(wildcards, "__iter__"):
+        raise ValueError("wildcards must be None or a sequence of token ids")
+    out = []
+    for t in wildcards:
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise ValueError("wildcards: token ids must be integers, got %r" % (t,))
+        if not -2 ** 31 <= int(t) < 2 ** 31:
+            raise ValueError("wildcards: token ids must fit 32 bits")
+        out.append(int(t))
+    if len(set(out)) != len(out):
+        raise ValueError("wildcards: a token is listed twice")
+    return np.array(out, dtype=np.int32)
+
+
 def mismatch_levels(g, weights, lib=None):
     """The level coefficients ``a_0..a_d`` of mismatch weights ``c_0..c_m`` at window length ``g`` (``fsk_mismatch_levels``, host
     only): ``sum_h c_h N_h == sum_j a_j S_j`` with ``S_j`` the raw kernel of ``(g, m=j)``. ``d`` is the last ``h`` with
@@ -371,8 +393,10 @@ class Engine:
 
     def __init__(self, g, m, t=-1, approx=False, delta=0.025, max_iters=-1, skip_variance=False, device=0,
                  path=PATH_AUTO, profile=False, lib=None, skip_test_block=False, devices=None, collective=COLL_AUTO,
-                 bands=0, deadline_ms=0, tuning=None, revcomp=None, weights=None, max_mismatches=None):
+                 bands=0, deadline_ms=0, tuning=None, revcomp=None, weights=None, max_mismatches=None,
+                 wildcards=None):
         weights = mismatch_weights(g, m, weights, max_mismatches)
+        wildcards = wildcard_array(wildcards)
         if weights is not None and approx:
             raise ValueError("weights= / max_mismatches= with approx=True: a sample of combinations under signed level "
                              "coefficients estimates nothing")
@@ -402,12 +426,15 @@ class Engine:
         self.device = device
         self._keep = None
         self.revcomp = False
+        self.wildcards = []
         for key, value in (tuning or {}).items():
             self.set_tuning(key, value)
         self.weights = None
         try:
             if revcomp is not None and revcomp is not False:
                 self.set_complement(revcomp)
+            if len(wildcards):
+                self.set_wildcards(wildcards)
             if weights is not None:
                 self.set_mismatch_weights(weights)
         except Exception:
@@ -468,6 +495,20 @@ class Engine:
             raise ValueError("tokens and complements must be 1-D and of equal length")
         self._ck(self.lib.L.fsk_set_complement(self.h, tokens.ctypes.data, complements.ctypes.data, len(tokens)))
         self.revcomp = len(tokens) > 0
+
+    def set_wildcards(self, wildcards):
+        """Wildcard mode from the next ``load_sequences`` / ``compute`` on: a g-window that holds one of the token ids
+        ``wildcards`` (``FastaUtility.wildcards()``: the ``n`` of DNA) at any position is not a window. ``None`` or ``[]``
+        switch it off. Checked here (``ValueError``) as the engine checks it."""
+        self.set_wildcard_array(wildcard_array(wildcards))
+
+    def set_wildcard_array(self, tokens):
+        """``fsk_set_wildcards`` as it is: one int32 array, checked by the engine alone."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tokens.ndim != 1:
+            raise ValueError("wildcards must be 1-D")
+        self._ck(self.lib.L.fsk_set_wildcards(self.h, tokens.ctypes.data if len(tokens) else None, len(tokens)))
+        self.wildcards = sorted(int(t) for t in tokens)
 
     def set_mismatch_weights(self, weights):
         """Mismatch-weighted mode from the next ``compute`` on: ``weights`` are ``c_0..c_m`` (``W = sum_h c_h N_h``, N_h the
@@ -658,5 +699,6 @@ class Engine:
         self._ck(self.lib.L.fsk_get_stats(self.h, C.byref(s)))
         d = s.as_dict()
         d["revcomp"] = self.revcomp  # (as set: in force from the next load on)
+        d["wildcards"] = list(self.wildcards)
         d["weights"] = None if self.weights is None else list(self.weights)  # (mismatch-weighted mode, as set)
         return d

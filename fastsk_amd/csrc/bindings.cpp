@@ -7,7 +7,7 @@
 //   - errors raise ValueError / RuntimeError instead of printf + exit(1) (fastsk.cpp:53-58);
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
 //     NotImplementedError (they are unusable from Python in the reference as well);
-//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches), numpy and
+//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
 //   - skip_test_block (default False: compute_kernel computes the whole N x N triangle, as fastsk.cpp:30-118 does).
@@ -32,6 +32,9 @@
 //     weights = c_0..c_m, W = sum_h c_h N_h over the pairs of g-windows at exactly h mismatches; max_mismatches = d is
 //     shorthand for the gapped k-mer kernel truncated at d mismatches, c_h = C(g-h, m-h) for h <= d and 0 beyond (LS-GKM's
 //     "-l g -k g-m -d d"). Checked before any device call (ValueError); not with approx=True or devices=[...].
+//   - wildcards (default None: off): token ids that stand for "unknown" (fsk_set_wildcards; FastaUtility.wildcards() returns
+//     the id of DNA's n) — a g-window that holds one at any position is not a window, as in every k-mer tool; the reference
+//     has no such mode and matches n with n. Checked before any device call (ValueError).
 #include "../../include/fastsk_amd.h"
 
 namespace py = pybind11;
@@ -127,6 +130,7 @@ class FastSK {
     // skip_test_block="lazy" / None: the test x test block is left out of compute_kernel and computed only if asked for
     bool lazy_test_block_ = false, test_block_missing_ = false;
     bool revcomp_ = false;
+    std::vector<int32_t> wildcards_;
     std::vector<uint64_t> weights_;      // mismatch-weighted mode: c_0..c_m (empty: off)
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
@@ -237,9 +241,11 @@ class FastSK {
 public:
     FastSK(int g, int m, int t, bool approx, double delta, int max_iters, bool skip_variance, int device,
            const std::string& path, py::object seed, py::object skip_test_block, py::object devices,
-           const std::string& collective, int deadline_ms, py::object revcomp, py::object weights, py::object max_mismatches) {
+           const std::string& collective, int deadline_ms, py::object revcomp, py::object weights, py::object max_mismatches,
+           py::object wildcards) {
         fsk_config c{};
         parse_weights(g, m, weights, max_mismatches);  // (host only: ValueError before any device call)
+        parse_wildcards(wildcards);
         if (!weights_.empty() && approx)
             throw py::value_error("weights= / max_mismatches= with approx=True: a sample of combinations under signed level coefficients estimates nothing");
         if (!weights_.empty() && !devices.is_none())
@@ -272,6 +278,7 @@ public:
         try {
             if (!seed.is_none()) check(fsk_set_seed(h_, seed.cast<uint64_t>()));
             set_revcomp(revcomp);
+            if (!wildcards_.empty()) check(fsk_set_wildcards(h_, wildcards_.data(), (int32_t)wildcards_.size()));
             if (!weights_.empty()) check(fsk_set_mismatch_weights(h_, weights_.data(), (int32_t)weights_.size()));
         } catch (...) {
             fsk_destroy(h_);
@@ -311,6 +318,30 @@ public:
         if (fsk_mismatch_levels(g, weights_.data(), (int32_t)weights_.size(), a.data(), &n_levels) != FSK_OK) {
             weights_.clear();
             throw py::value_error(fsk_last_error(nullptr));
+        }
+    }
+    // wildcards= -> wildcards_ (empty: off), checked as fsk_set_wildcards checks them
+    void parse_wildcards(const py::object& wildcards) {
+        wildcards_.clear();
+        if (wildcards.is_none() || (py::isinstance<py::bool_>(wildcards) && !wildcards.cast<bool>())) return;
+        if (py::isinstance<py::str>(wildcards) || py::isinstance<py::bytes>(wildcards) || !py::isinstance<py::iterable>(wildcards))
+            throw py::value_error("wildcards must be None or a sequence of token ids");
+        for (auto t : wildcards.cast<py::iterable>()) {
+            if (py::isinstance<py::bool_>(t) || !(py::isinstance<py::int_>(t) || py::hasattr(t, "__index__"))) {
+                wildcards_.clear();
+                throw py::value_error("wildcards: token ids must be integers");
+            }
+            long long v = 0;
+            try {
+                v = py::int_(t.attr("__index__")()).cast<long long>();
+            } catch (...) {
+                wildcards_.clear();
+                throw py::value_error("wildcards: token ids must fit 32 bits");
+            }
+            if (v < INT32_MIN || v > INT32_MAX) { wildcards_.clear(); throw py::value_error("wildcards: token ids must fit 32 bits"); }
+            for (int32_t seen : wildcards_)
+                if (seen == (int32_t)v) { wildcards_.clear(); throw py::value_error("wildcards: a token is listed twice"); }
+            wildcards_.push_back((int32_t)v);
         }
     }
     // None / False: off; else a mapping {token_id: token_id} that fsk_set_complement checks (ValueError)
@@ -456,6 +487,11 @@ public:
         d["cell_updates"] = s.cell_updates; d["launches"] = s.launches;
         d["test_block_computed"] = computed_ && !test_block_missing_;
         d["revcomp"] = revcomp_;
+        {
+            py::list wl;
+            for (int32_t v : wildcards_) wl.append(v);
+            d["wildcards"] = wl;
+        }
         if (weights_.empty()) d["weights"] = py::none();
         else {
             py::list w;
@@ -516,12 +552,13 @@ PYBIND11_MODULE(_fastsk, m) {
     m.doc() = "MI355X-native gapped-k-mer kernel engine behind the FastSK Python surface";
     py::class_<FastSK>(m, "FastSK")
         .def(py::init<int, int, int, bool, double, int, bool, int, const std::string&, py::object, py::object, py::object,
-                      const std::string&, int, py::object, py::object, py::object>(),
+                      const std::string&, int, py::object, py::object, py::object, py::object>(),
              py::arg("g"), py::arg("m"), py::arg("t") = -1, py::arg("approx") = false, py::arg("delta") = 0.025,
              py::arg("max_iters") = -1, py::arg("skip_variance") = false, py::arg("device") = 0,
              py::arg("path") = "auto", py::arg("seed") = py::none(), py::arg("skip_test_block") = false,
              py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0,
-             py::arg("revcomp") = py::none(), py::arg("weights") = py::none(), py::arg("max_mismatches") = py::none())
+             py::arg("revcomp") = py::none(), py::arg("weights") = py::none(), py::arg("max_mismatches") = py::none(),
+             py::arg("wildcards") = py::none())
         .def("compute_kernel", &FastSK::compute_kernel, py::arg("Xtrain"), py::arg("Xtest"))
         .def("compute_kernel_flat", &FastSK::compute_kernel_flat, py::arg("tokens").noconvert(), py::arg("offsets").noconvert(),
              py::arg("n_train"))

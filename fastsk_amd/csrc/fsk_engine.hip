@@ -474,6 +474,7 @@ void fsk_detail::one_destroy(fsk_engine* e) {
     if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
     if (e->chain_stream) (void)hipStreamSynchronize(e->chain_stream);  // (variance mode may leave a dropped batch's sums running)
     e->d_words.release(); e->d_wstart.release(); e->d_len.release(); e->d_fstart.release(); e->d_featseq.release(); e->d_win.release(); e->d_comp.release();
+    e->d_vbits.release(); e->d_vstart.release(); e->d_fwin.release();
     e->d_pos.release(); e->d_allpos.release(); e->d_bsum.release(); e->d_seqblk.release(); e->K_store.release(); e->d_Kf64.release(); e->d_Khat.release(); e->d_prod.release();
     e->d_diag.release(); e->d_stage.release(); e->d_stage_u64.release(); e->d_Kslots.release(); e->d_cell_idx.release(); e->d_C4.release(); e->d_C4H.release(); e->d_rowmask.release(); e->d_flag.release(); e->d_tiletab.release(); e->d_rare.release(); e->d_rare_n.release(); e->d_common.release(); e->d_keybits.release(); e->d_lut.release(); e->d_vc.release();
     if (e->lane_stream) { (void)hipStreamSynchronize(e->lane_stream); (void)hipStreamDestroy(e->lane_stream); }
@@ -542,7 +543,23 @@ int fsk_detail::one_set_complement(fsk_engine* e, const int32_t* tokens, const i
     return FSK_OK;
 }
 
+// fsk_set_wildcards: kept sorted; the next load counts and packs with them
+int fsk_detail::one_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n) {
+    if (n < 0 || (n > 0 && !tokens)) return e->fail(FSK_EINVAL, "wildcards: a null array or a negative length");
+    std::vector<int32_t> w(tokens, tokens + n);
+    std::sort(w.begin(), w.end());
+    for (size_t i = 1; i < w.size(); ++i)
+        if (w[i] == w[i - 1]) return e->fail(FSK_EINVAL, "wildcards: token %d is listed twice", w[i]);
+    e->wild_tokens.swap(w);
+    return FSK_OK;
+}
+
 extern "C" {
+
+int fsk_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n) {
+    if (!e) return FSK_EINVAL;
+    return e->group ? group_set_wildcards(e, tokens, n) : one_set_wildcards(e, tokens, n);
+}
 
 int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n) {
     if (!e) return FSK_EINVAL;
@@ -587,6 +604,19 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     // reverse-complement mode: every sequence owns the windows of both its strands
     const bool rc_on = !e->rc_tokens.empty();
     const int64_t strands = rc_on ? 2 : 1;
+    // wildcard mode: a window that holds a wildcard is none. `wild_on`: some sequence really holds one (a set whose tokens do
+    // not occur leaves this load the plain one, to the launch)
+    const bool wild_set = !e->wild_tokens.empty();
+    uint8_t wild_small[256] = {0};
+    for (int32_t t : e->wild_tokens)
+        if (t >= 0 && t < 256) wild_small[t] = 1;
+    auto is_wild = [&](int32_t t) {
+        return (uint32_t)t < 256u ? wild_small[t] != 0 : std::binary_search(e->wild_tokens.begin(), e->wild_tokens.end(), t);
+    };
+    if (wild_set && rc_on)
+        for (size_t q = 0; q < e->rc_tokens.size(); ++q)
+            if (is_wild(e->rc_tokens[q]) && !is_wild(e->rc_comps[q]))
+                return e->fail(FSK_EINVAL, "wildcard token %d has the complement %d, which is not a wildcard", e->rc_tokens[q], e->rc_comps[q]);
     int64_t shortest_train = INT64_MAX, shortest_test = INT64_MAX, longest = 0, nfeat = 0;
     for (int64_t i = 0; i < N; ++i) {
         const int64_t len = offsets[i + 1] - offsets[i];
@@ -601,6 +631,48 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     if (n_test > 0 && g > shortest_test)
         return e->fail(FSK_ESHORT, "g cannot be longer than the shortest sequence in a dataset. g = %d, but shortest test sequence has length %lld", g, (long long)shortest_test);
     if (nfeat >= ((int64_t)1 << 31) || longest >= ((int64_t)1 << 24)) return e->fail(FSK_EUNSUPPORTED, "input too large (g-mers >= 2^31 or a sequence >= 2^24)");
+    // wildcard mode: the windows free of wildcards, per sequence — their number (nvalid), one bit a window position
+    // (vbits, sequence i from word vstart[i]; bits past the last position stay zero) —, found with the length of the
+    // wildcard-free run that ends at every symbol: the window that ends there is valid when the run reaches g
+    bool wild_on = false;
+    std::vector<uint32_t> nvalid, vstart, vbits;
+    int64_t most_valid = longest - g + 1;
+    if (wild_set) {
+        const int64_t total_tok = offsets[N] - off0;
+        for (int64_t i = 0; i < total_tok && !wild_on; ++i) wild_on = is_wild(tokens[i]);
+    }
+    if (wild_on) {
+        nvalid.resize((size_t)N);
+        vstart.resize((size_t)N + 1);
+        uint64_t vw = 0;
+        for (int64_t i = 0; i < N; ++i) {
+            vstart[(size_t)i] = (uint32_t)vw;
+            vw += (uint64_t)(offsets[i + 1] - offsets[i] - g + 1 + 31) / 32;
+        }
+        vstart[(size_t)N] = (uint32_t)vw;  // (fewer words than symbols: below 2^31)
+        vbits.assign((size_t)vw + 1, 0u);
+        nfeat = 0;
+        most_valid = 0;
+        for (int64_t i = 0; i < N; ++i) {
+            const int32_t* sq = tokens + (offsets[i] - off0);
+            const int64_t len = offsets[i + 1] - offsets[i];
+            uint32_t* vb = vbits.data() + vstart[(size_t)i];
+            int64_t run = 0, nv = 0;
+            for (int64_t p = 0; p < len; ++p) {
+                run = is_wild(sq[p]) ? 0 : run + 1;
+                if (run >= g) {
+                    const int64_t j = p - g + 1;
+                    vb[j >> 5] |= 1u << (j & 31);
+                    ++nv;
+                }
+            }
+            if (nv == 0)
+                return e->fail(FSK_ESHORT, "sequence %lld has no window of length g = %d that is free of wildcards: it would have no features", (long long)i, g);
+            nvalid[(size_t)i] = (uint32_t)nv;
+            nfeat += strands * nv;
+            most_valid = std::max(most_valid, nv);
+        }
+    }
     tl_lengths = tl_ms(tl0);
     // ---- alphabet: rank-remap the tokens that occur (equality preserving; the reference's
     // dict_size = |{0} U tokens|, fastsk.cpp:70-85, only serves as its counting-sort radix), then pack,
@@ -622,7 +694,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             const int64_t len = offsets[i + 1] - offsets[i];
             len32[i] = (uint32_t)len;
             fstart[i] = fcount;
-            fcount += (uint32_t)(strands * (len - g + 1));
+            fcount += (uint32_t)(strands * (wild_on ? (int64_t)nvalid[(size_t)i] : len - g + 1));
         }
         fstart[N] = fcount;
     }
@@ -643,7 +715,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             if (!rc_comp_of(distinct[q], &c)) {
                 int32_t first = distinct[q];
                 for (int64_t i = 0; i < total; ++i)
-                    if (!rc_comp_of(tokens[i], &c)) { first = tokens[i]; break; }
+                    if (!rc_comp_of(tokens[i], &c) && !(wild_on && is_wild(tokens[i]))) { first = tokens[i]; break; }
                 return e->fail(FSK_EINVAL, "token %d occurs in the sequences but not in the complement map", first);
             }
             distinct.push_back(c);
@@ -726,7 +798,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
                 for (int v = 0; v < 256; ++v) {
                     cnt[v] = 0;
                     for (int t = 0; t < nt; ++t) cnt[v] += hist[(size_t)t][(size_t)v];
-                    if (cnt[v]) distinct.push_back(v);
+                    if (cnt[v] && !(wild_on && wild_small[v])) distinct.push_back(v);
                 }
                 rc_mid = rc_close();
                 if (rc_mid) return;
@@ -788,6 +860,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             std::sort(distinct.begin(), distinct.end());
             distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
         }
+        if (wild_on) distinct.erase(std::remove_if(distinct.begin(), distinct.end(), is_wild), distinct.end());
         { const int rc_cl = rc_close(); if (rc_cl) return rc_cl; }
         if (distinct.size() > sym_freq.size()) sym_freq.assign(distinct.size(), 0);
         wstart_v.resize((size_t)N);
@@ -806,6 +879,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             const int32_t* sq = tokens + (offsets[i] - off0);
             uint32_t* w = words_v.data() + wstart_v[i];
             for (uint32_t p = 0; p < len32[i]; ++p) {
+                if (wild_on && is_wild(sq[p])) continue;  // (rank 0 in the words, counted nowhere)
                 uint32_t r = direct ? lut[(size_t)(sq[p] - base)]
                                     : (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), sq[p]) - distinct.begin());
                 const uint32_t bitpos = p * (uint32_t)bits;
@@ -830,7 +904,11 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         for (size_t r = 0; r < distinct.size(); ++r) both[r] = sym_freq[r] + sym_freq[comp_rank[r]];
         sym_freq.swap(both);
     }
-    const int64_t total_sym = strands * total;  // symbols counted, both strands
+    int64_t total_sym = strands * total;  // symbols counted, both strands
+    if (wild_on) {
+        total_sym = 0;
+        for (size_t r = 0; r < distinct.size() && r < sym_freq.size(); ++r) total_sym += sym_freq[r];
+    }
     tl_pack = tl_ms(tl0);
     // ---- commit
     // (the dense dataflow's tile table depends on the number of sequences and the train / test split alone: a set of the same
@@ -841,8 +919,9 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     e->sigma = sigma; e->bits = bits; e->V = V; e->Vq = (uint32_t)((V + 3) / 4);
     e->Lmax = (uint32_t)longest; e->Lmin = (uint32_t)std::min(shortest_train, n_test > 0 ? shortest_test : shortest_train);
     e->maxW1 = (uint32_t)(longest - g + 1);
-    e->maxW = (uint32_t)strands * e->maxW1;
+    e->maxW = (uint32_t)strands * (uint32_t)most_valid;
     e->revcomp = rc_on;
+    e->wild = wild_on;
     e->n_panels = (uint32_t)((N + fsk::PANEL - 1) / fsk::PANEL);
     e->h_len = len32; e->h_fstart = fstart; e->featseq_ready = false;
     e->prep_valid = false; e->vc_sum = 0; e->vc_n = 0;
@@ -897,6 +976,8 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         // (reverse-complement mode: the rare symbols' places are listed on one strand only — the marking pass over every
         // window of both strands, k_dense_count<true, ., true>, instead)
         if (rc_on) e->compact_rare = false;
+        // (wildcard mode likewise: the windows around a rare symbol's place may hold a wildcard, which the marking pass knows)
+        if (wild_on) e->compact_rare = false;
         e->rare_places = (uint32_t)places;
     }
     FSK_HIP(e->d_words.reserve(n_words_alloc));
@@ -906,6 +987,29 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     if (rc_on) {
         FSK_HIP(e->d_comp.reserve(comp_rank.size()));
         FSK_HIP(hipMemcpy(e->d_comp.p, comp_rank.data(), comp_rank.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    if (wild_on) {
+        // the window of every feature, for the sparse dataflow: a sequence's valid forward windows in order, then (second
+        // strand) window j' of rc(x), valid exactly when forward window (len - g) - j' is, as len - g + 1 + j'
+        std::vector<uint32_t> fwin((size_t)nfeat);
+        for (int64_t i = 0; i < N; ++i) {
+            const uint32_t nw = len32[(size_t)i] - (uint32_t)g + 1u;
+            const uint32_t* vb = vbits.data() + vstart[(size_t)i];
+            uint32_t* out = fwin.data() + fstart[(size_t)i];
+            for (uint32_t j = 0; j < nw; ++j)
+                if ((vb[j >> 5] >> (j & 31u)) & 1u) *out++ = j;
+            if (rc_on)
+                for (uint32_t j = 0; j < nw; ++j) {
+                    const uint32_t f = nw - 1u - j;
+                    if ((vb[f >> 5] >> (f & 31u)) & 1u) *out++ = nw + j;
+                }
+        }
+        FSK_HIP(e->d_vbits.reserve(vbits.size()));
+        FSK_HIP(e->d_vstart.reserve(vstart.size()));
+        FSK_HIP(e->d_fwin.reserve(std::max<size_t>(1, fwin.size())));
+        FSK_HIP(hipMemcpy(e->d_vbits.p, vbits.data(), vbits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        FSK_HIP(hipMemcpy(e->d_vstart.p, vstart.data(), vstart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        FSK_HIP(hipMemcpy(e->d_fwin.p, fwin.data(), fwin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (staged) {  // everything sits in pinned memory: four copies on the stream, nothing to wait for
         FSK_HIP(hipMemcpyAsync(e->d_words.p, p_words, n_words_alloc * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
@@ -1628,6 +1732,7 @@ int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offset
         lv->cfg_profile0 = e->cfg_profile0;
         lv->rc_tokens = e->rc_tokens;
         lv->rc_comps = e->rc_comps;
+        lv->wild_tokens = e->wild_tokens;
         rc = fsk_bind_counts(lv, e->mm_scratch.p, e->pairs);
         if (!rc) rc = one_load_sequences(lv, tokens, offsets, n_train, n_test);  // (zeroes the bound triangle, or owes the zeros to the first tile launch)
         if (!rc) {

@@ -126,6 +126,10 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     // a cell, counts both)
     const uint32_t maxW1 = e->maxW1;
     size_t extra = compact ? (size_t)Vkeys * 2 : 0;
+    // (wildcard mode: the staged windows' validity, one bit each, a set per strand that may be resident, and the round-up
+    // to a dword boundary: at most 1024 windows are staged at a time)
+    const size_t wild_lds = e->wild ? (size_t)(e->revcomp ? 2 : 1) * ((std::min(maxW1, 1024u) + 31u) / 32u) * fsk::PANEL * sizeof(uint32_t) + 4 : 0;
+    extra += wild_lds;
     DensePlan plan = dense_plan(maxW1, e->cfg.g, e->Vq, extra);  // may be re-planned below
     if (plan.CH == 0) return e->fail(FSK_EUNSUPPORTED, "dense path: LDS plan does not fit");
     // ... and when a strand is staged in one pass, the second strand gets a staging buffer of its own behind the table, so
@@ -162,6 +166,13 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     auto k_count = e->revcomp ? fsk::k_dense_count<false, false, true> : fsk::k_dense_count<false, false, false>;
     auto k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true> : fsk::k_dense_count<false, true, false>;
     auto k_mark = e->revcomp ? fsk::k_dense_count<true, false, true> : fsk::k_dense_count<true, false, false>;
+    if (e->wild) {
+        k_count = e->revcomp ? fsk::k_dense_count<false, false, true, true> : fsk::k_dense_count<false, false, false, true>;
+        k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true, true> : fsk::k_dense_count<false, true, false, true>;
+        k_mark = e->revcomp ? fsk::k_dense_count<true, false, true, true> : fsk::k_dense_count<true, false, false, true>;
+    }
+    const uint32_t* const vbits = e->wild ? (const uint32_t*)e->d_vbits.p : (const uint32_t*)nullptr;
+    const uint32_t* const vstart = e->wild ? (const uint32_t*)e->d_vstart.p : (const uint32_t*)nullptr;
     const uint16_t* const comp = e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr;
     FSK_HIP(fsk_hw::allow_dynamic_lds(k_count, lds));
     FSK_HIP(fsk_hw::allow_dynamic_lds(k_count_lut, lds));
@@ -235,12 +246,12 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                     FSK_HIP(hipMemsetAsync(e->d_keybits.p, 0, (size_t)nb * Vw * sizeof(uint32_t), e->stream));
                     FSK_LAUNCH(k_mark, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                                e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows, comp, rc_rows);
+                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows, comp, rc_rows, vbits, vstart);
                 }
                 FSK_LAUNCH(fsk::k_dense_keylut, dim3(nb), dim3(256), 0, e->stream, e->d_keybits.p, Vkeys, e->d_lut.p, e->d_vc.p);
                 FSK_LAUNCH(k_count_lut, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                            e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows, comp, rc_rows);
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart);
                 h_vc.resize((size_t)nb);
                 FSK_HIP(hipMemcpyAsync(h_vc.data(), e->d_vc.p, (size_t)nb * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
                 FSK_HIP(hipStreamSynchronize(e->stream));
@@ -255,7 +266,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             } else {
                 FSK_LAUNCH(k_count, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                            e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows, comp, rc_rows);
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart);
             }
             e->toc(&e->st.ms_count);
             e->st.count_launches += 1;

@@ -213,6 +213,15 @@ struct fsk_engine {
     bool revcomp = false;
     uint32_t maxW1 = 0;
     DevBuf<uint16_t> d_comp;
+    // wildcard mode (fsk_set_wildcards): the tokens as set, sorted (empty: off); what the LOADED sequences carry — wild
+    // (some sequence really holds one; else the load is the plain one), the validity bitmap of the forward windows (one
+    // bit a window position, sequence i from word vstart[i], bits past its last window zero; the dense count kernel) and,
+    // for the sparse dataflow, the window of every feature (fwin[f]: its place among the sequence's window positions, the
+    // second strand's after the first's). The packed sequences hold rank 0 where a wildcard stands. nfeat, fstart and maxW
+    // count valid windows; maxW1 stays the window POSITIONS of the longest sequence (what is staged).
+    std::vector<int32_t> wild_tokens;
+    bool wild = false;
+    DevBuf<uint32_t> d_vbits, d_vstart, d_fwin;
 
     // mismatch-weighted mode (fsk_set_mismatch_weights): the weights c_0..c_m as set (empty: off), the level coefficients
     // a_0..a_d solved from them, and whether they are today's kernel (a = e_m: nothing of the mode runs). mm_scratch holds
@@ -478,6 +487,7 @@ int one_synchronize(fsk_engine* e);
 int one_finalize(fsk_engine* e);
 int one_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
 int one_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
+int one_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
 int one_get_stats(fsk_engine* e, fsk_stats* out);
 void one_destroy(fsk_engine* e);
 // the combos the approx modes accumulate as plain integer sums (skip_variance): fastsk_kernel.cpp:148,275
@@ -498,6 +508,7 @@ int group_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, 
 int group_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
 int group_set_seed(fsk_engine* e, uint64_t seed);
 int group_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
+int group_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
 int group_get_stats(fsk_engine* e, fsk_stats* out);
 int group_set_skip_test_block(fsk_engine* e, int32_t skip);
 int group_set_tuning(fsk_engine* e, const char* key, int64_t value, std::string& err);

@@ -16,11 +16,34 @@ namespace fsk {
 // mapped through the combo's compaction table when LUT.
 // kcache (several key sweeps over one staging pass): the first sweep stores every window's
 // (compacted) key in LDS, kmode 1; the later sweeps read it back instead of recomputing, kmode 2.
-template <int K, bool MARK, bool LUT>
+// WILD (wildcard mode): `vl` holds the chunk's window validity, word q of lane r at vl[q * PANEL + r], bit b = window
+// cb + 32 q + b of the strand at hand; a window whose bit is clear is predicated off wherever j < nwin is tested (a wildcard
+// is staged as symbol 0, so the key of such a window stays inside the rank table and the histogram).
+__device__ __forceinline__ bool window_valid(const uint32_t* vl, uint32_t rel, uint32_t r) {
+    return ((FSK_LDS_LOAD_U32(vl + (rel >> 5) * PANEL + r) >> (rel & 31u)) & 1u) != 0u;
+}
+// 32 validity bits of the FORWARD windows s .. s + 31 of a sequence whose bitmap is the nw words from vb (bits past its
+// last window are zero there); windows outside the bitmap read as invalid. s may be negative.
+__device__ __forceinline__ uint32_t valid_bits32(const uint32_t* vbits, uint32_t vb, uint32_t nw, int32_t s) {
+    if (s <= -32 || s >= (int32_t)(nw * 32u)) return 0u;
+    const int32_t wi = s >> 5;  // (floor)
+    const uint32_t sh = (uint32_t)s & 31u;
+    const uint32_t lo = wi >= 0 ? vbits[vb + (uint32_t)wi] : 0u;
+    const uint32_t hi = wi + 1 < (int32_t)nw ? vbits[vb + (uint32_t)(wi + 1)] : 0u;
+    return sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+}
+__device__ __forceinline__ uint32_t reverse_bits32(uint32_t x) {  // (the compiler's own idiom: one v_bfrev_b32)
+    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0f0f0f0fu) | ((x & 0x0f0f0f0fu) << 4);
+    x = ((x >> 8) & 0x00ff00ffu) | ((x & 0x00ff00ffu) << 8);
+    return (x >> 16) | (x << 16);
+}
+template <int K, bool MARK, bool LUT, bool WILD>
 __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* hist, const uint16_t* lut, const uint32_t (&pr)[16],
                                               int k, uint32_t sigma, uint32_t j0, uint32_t hi, uint32_t cb, uint32_t nwin,
                                               uint32_t r, uint32_t half, uint32_t key_lo, uint32_t key_n, uint16_t* kcache,
-                                              int kmode) {
+                                              int kmode, const uint32_t* vl) {
     if (K > 0 && kmode == 0) {
         // The common case (every BASELINE config; with key compaction both of its passes — MARK sets the key's bit, LUT
         // counts the key's rank — unless a window-key cache is in use): WPT windows per trip. Window j+4 of a lane lies
@@ -47,13 +70,16 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
             }
 #pragma unroll
             for (int u = 0; u < WPT; ++u) {
+                // (WILD: the trip condition keeps j + 4 u below hi, inside the chunk's validity words)
                 if (MARK) {
-                    if (j + 4u * u < nwin) atomicOr(&hist[kk[u] >> 5], 1u << (kk[u] & 31u));  // hist doubles as the key bitmap
+                    if (j + 4u * u < nwin && (!WILD || window_valid(vl, j + 4u * u - cb, r)))
+                        atomicOr(&hist[kk[u] >> 5], 1u << (kk[u] & 31u));  // hist doubles as the key bitmap
                     continue;
                 }
                 // (the table sits in LDS; a padding row's key is 0, inside it)
                 const uint32_t key = (LUT ? (uint32_t)FSK_LDS_LOAD_U16(lut + kk[u]) : kk[u]) - key_lo;  // wraps for keys below the sweep: rejected by the compare
-                if (j + 4u * u < nwin && key < key_n) atomicAdd(&hist[key * 32u + (r >> 1)], 1u << half);
+                if (j + 4u * u < nwin && key < key_n && (!WILD || window_valid(vl, j + 4u * u - cb, r)))
+                    atomicAdd(&hist[key * 32u + (r >> 1)], 1u << half);
             }
         }
         for (; j < hi; j += 4u) {  // the last few windows of the chunk
@@ -64,17 +90,17 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
                 p[c] += 4 * PANEL;
             }
             if (MARK) {
-                if (j < nwin) atomicOr(&hist[k0 >> 5], 1u << (k0 & 31u));
+                if (j < nwin && (!WILD || window_valid(vl, j - cb, r))) atomicOr(&hist[k0 >> 5], 1u << (k0 & 31u));
                 continue;
             }
             if (LUT) k0 = (uint32_t)FSK_LDS_LOAD_U16(lut + k0);
             k0 -= key_lo;
-            if (j < nwin && k0 < key_n) atomicAdd(&hist[k0 * 32u + (r >> 1)], 1u << half);
+            if (j < nwin && k0 < key_n && (!WILD || window_valid(vl, j - cb, r))) atomicAdd(&hist[k0 * 32u + (r >> 1)], 1u << half);
         }
         return;
     }
     for (uint32_t j = j0; j < hi; j += 4) {
-        if (j < nwin) {
+        if (j < nwin && (!WILD || window_valid(vl, j - cb, r))) {  // (an invalid window is neither cached nor replayed)
             uint32_t key = 0;  // keys stay below 2^24 on this path (V <= 16384): 24-bit multiplies issue at full rate
             if (!MARK && kmode == 2) {  // workgroup-uniform
                 key = kcache[j * PANEL + r];
@@ -102,21 +128,21 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
     }
 }
 
-template <bool MARK, bool LUT>
+template <bool MARK, bool LUT, bool WILD>
 __device__ __forceinline__ void count_windows_k(const uint8_t* symT, uint32_t* hist, const uint16_t* lut, const uint32_t (&pr)[16],
                                                 int k, uint32_t sigma, uint32_t j0, uint32_t hi, uint32_t cb, uint32_t nwin,
                                                 uint32_t r, uint32_t half, uint32_t key_lo, uint32_t key_n, uint16_t* kcache,
-                                                int kmode) {
+                                                int kmode, const uint32_t* vl) {
     switch (k) {  // workgroup-uniform
-        case 1: count_windows<1, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 2: count_windows<2, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 3: count_windows<3, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 4: count_windows<4, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 5: count_windows<5, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 6: count_windows<6, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 7: count_windows<7, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        case 8: count_windows<8, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
-        default: count_windows<0, MARK, LUT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode); break;
+        case 1: count_windows<1, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 2: count_windows<2, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 3: count_windows<3, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 4: count_windows<4, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 5: count_windows<5, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 6: count_windows<6, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 7: count_windows<7, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 8: count_windows<8, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        default: count_windows<0, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
     }
 }
 
@@ -151,13 +177,21 @@ __device__ __forceinline__ void pack_count_row(const uint16_t* hist16, uint32_t 
 // and the overflow flag carry two-strand counts and nothing after this kernel knows. rc_rows != 0: the second strand has
 // sym_rows = rc_rows rows of its own behind the table (CH >= max_win: both strands are unpacked once per workgroup);
 // rc_rows == 0: the one buffer is re-staged strand by strand. No window-key cache in this mode (kc_rows = 0).
-template <bool MARK, bool LUT, bool RC>
+//
+// WILD (wildcard mode): a window that holds a wildcard is not counted. The sequences hold symbol 0 where a wildcard stands;
+// which windows are valid comes from the per-sequence bitmap of the load (vbits, sequence i from word vstart[i]) and is
+// staged beside the symbols, whenever they are: ceil(CH / 32) words a lane behind everything else in LDS (a second set when
+// both strands are resident). Window j' of the second strand is valid exactly when forward window (len - g) - j' is: its
+// words are the forward ones read backwards. A window of one chunk whose wildcard lies in the overlap rows of the next
+// is invalid in the bitmap like any other.
+template <bool MARK, bool LUT, bool RC, bool WILD = false>
 __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, uint32_t sigma, uint32_t Vq,
                                                      uint32_t Vcq, uint32_t max_win, uint32_t CH, const uint8_t* combo_pos,
                                                      int n_slots, int slots_per_chunk, uint32_t* C4, uint32_t* C4H,
                                                      uint32_t* rowmask, uint32_t nst, uint32_t* overflow_flag, uint32_t V,
                                                      const uint16_t* lut_g, const uint16_t* vc, uint32_t* keybits,
-                                                     uint32_t kc_rows, const uint16_t* comp, uint32_t rc_rows) {
+                                                     uint32_t kc_rows, const uint16_t* comp, uint32_t rc_rows,
+                                                     const uint32_t* vbits, const uint32_t* vstart) {
     // Counts leave as two 4-bit planes, count = lo + 16 * hi (8 keys per dword): C4 holds lo and
     // is all the tile kernel multiplies for almost every key; C4H holds hi, zero unless a k-mer
     // occurs more than 15 times in one sequence (poly-A, runs of 'n'); rowmask[panel][slot][..]
@@ -178,12 +212,19 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
     uint16_t* kcache = lut + (LUT ? V : 0u);
     uint8_t* symT2 = RC && rc_rows != 0u ? reinterpret_cast<uint8_t*>(kcache) : symT;  // (RC: the place of the cache is the second strand's)
     constexpr int STRANDS = RC ? 2 : 1;
+    // (WILD) validity words: behind the cache / the second strand's symbols, on a dword boundary
+    const uint32_t vwords = (CH + 31u) >> 5;
+    uint32_t* const vld = reinterpret_cast<uint32_t*>(
+        smem + (((size_t)sym_rows * PANEL + (size_t)Vcq * 512 + (LUT ? (size_t)V * 2 : 0) + (RC ? (size_t)rc_rows * PANEL : (size_t)kc_rows * PANEL * 2) + 3) & ~(size_t)3));
+    uint32_t* const vld2 = RC && rc_rows != 0u ? vld + (size_t)vwords * PANEL : vld;
     const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
     const uint32_t panel = blockIdx.x;
     const uint32_t seq = panel * PANEL + r;
     const uint32_t len = seq < S.n_seq ? S.len[seq] : 0u;
     const uint32_t wbase = seq < S.n_seq ? S.wstart[seq] : 0u;
     const uint32_t nwin = len >= (uint32_t)g ? len - g + 1 : 0u;
+    const uint32_t vbase = WILD && seq < S.n_seq ? vstart[seq] : 0u;
+    const uint32_t vnw = WILD && seq < S.n_seq ? vstart[seq + 1] - vbase : 0u;
     const bool single = CH >= max_win;
     const int slot0 = blockIdx.y * slots_per_chunk;
     const int slot1 = slot0 + slots_per_chunk < n_slots ? slot0 + slots_per_chunk : n_slots;
@@ -216,6 +257,7 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
             for (uint32_t i = tid; i < hist_dwords; i += 256) hist[i] = 0u;
             for (int strand = 0; strand < STRANDS; ++strand) {
                 uint8_t* const sy = RC && strand ? symT2 : symT;
+                uint32_t* const vl = RC && strand ? vld2 : vld;
                 const bool kept = !RC || rc_rows != 0u;  // a strand's staged symbols outlive the other strand's pass
                 for (uint32_t cb = 0; cb < max_win; cb += CH) {
                     if (!single || !kept || (slot == slot0 && kc0 == 0)) {
@@ -228,12 +270,20 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
                             }
                             sy[p * PANEL + r] = (uint8_t)sym;
                         }
+                        if (WILD) {
+                            for (uint32_t q = (uint32_t)w; q < vwords; q += 4u) {
+                                uint32_t vb32;
+                                if (RC && strand) vb32 = reverse_bits32(valid_bits32(vbits, vbase, vnw, (int32_t)nwin - 1 - (int32_t)(cb + 32u * q) - 31));
+                                else vb32 = valid_bits32(vbits, vbase, vnw, (int32_t)(cb + 32u * q));
+                                vl[q * PANEL + r] = vb32;
+                            }
+                        }
                     }
                     __syncthreads();  // symbols staged, histogram zeroed, table loaded
                     const uint32_t hi = cb + CH < max_win ? cb + CH : max_win;
                     const int kmode = (MARK || kc_rows == 0u) ? 0 : (kc0 == 0u ? 1 : 2);
-                    count_windows_k<MARK, LUT>(sy, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half, key_lo, key_n,
-                                               kcache, kmode);
+                    count_windows_k<MARK, LUT, WILD>(sy, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half, key_lo, key_n,
+                                                     kcache, kmode, vl);
                 }
             }
             __syncthreads();

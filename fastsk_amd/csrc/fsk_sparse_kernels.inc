@@ -152,12 +152,14 @@ __device__ __forceinline__ int block_excl_maxscan_256(int v, int* tmp, int* tota
 // batch then needs no copy command at all; this kernel also zeroes the batch's counters (batch_stats).
 // RC (reverse-complement mode): a sequence owns 2 (len - g + 1) features; feature j of its second half is window
 // j - (len - g + 1) of rc(x), whose symbol c is comp[x[len - 1 - (j - (len - g + 1)) - c]].
+// WILD (wildcard mode): a sequence owns its valid windows only, so feature f is no longer window f - fstart[seq]: fwin[f] is
+// (the second strand's windows numbered on after the first's, as above).
 struct SxIds { int32_t id[16]; };
-template <typename RecT, bool RC>
+template <typename RecT, bool RC, bool WILD = false>
 __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* feat_seq, const uint32_t* fstart, uint32_t nfeat, uint32_t tps,
                                                     int k, uint32_t sigma, int sb, const uint8_t* combo_pos, RecT* rec,
                                                     uint32_t* blockhist, uint32_t dmask, SxIds ids, u64* batch_stats, int by_id,
-                                                    int symbits, const uint16_t* comp, int g) {
+                                                    int symbits, const uint16_t* comp, int g, const uint32_t* fwin) {
     // (symbits != 0: a k-mer space beyond 2^62 — the key is the symbols' bit fields side by side, which a 128-bit record holds)
     typedef typename std::conditional<sizeof(RecT) == 16, RecT, u64>::type key_t;
     __shared__ uint32_t h[256];
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void k_sx_extract(SeqView S, const uint32_t* f
 #pragma unroll
         for (int u = 0; u < EX_B; ++u) {
             const uint32_t f = base + (uint32_t)(it0 + u) * 256u + tid;
-            j[u] = f - fstart[seq[u]];
+            j[u] = WILD ? (f < nfeat ? fwin[f] : 0u) : f - fstart[seq[u]];
             wbase[u] = S.wstart[seq[u]];
             back[u] = false;
             if (RC && f < nfeat) {
@@ -236,13 +238,14 @@ __global__ __launch_bounds__(256) void k_sx_featseq(const uint32_t* fstart, uint
 // L2 / MALL (16 bytes x features).
 // RC (reverse-complement mode): the second half of a sequence's features are the windows of rc(x), written reversed and
 // complemented (see k_sx_extract) — everything that reads the window array then sees twice the features and no strands.
-template <int WW, bool RC>
+// WILD (wildcard mode): the window of feature f is fwin[f] (see k_sx_extract); the array holds the valid windows only.
+template <int WW, bool RC, bool WILD = false>
 __global__ __launch_bounds__(256) void k_sx_windows(SeqView S, const uint32_t* feat_seq, const uint32_t* fstart, uint32_t nfeat, int g,
-                                                    uint32_t* win, const uint16_t* comp) {
+                                                    uint32_t* win, const uint16_t* comp, const uint32_t* fwin) {
     const uint32_t f = blockIdx.x * 256u + threadIdx.x;
     if (f >= nfeat) return;
     const uint32_t seq = feat_seq[f], wbase = S.wstart[seq];
-    uint32_t j = f - fstart[seq];
+    uint32_t j = WILD ? fwin[f] : f - fstart[seq];
     bool back = false;
     if (RC) {
         const uint32_t len = S.len[seq], nwin = len - (uint32_t)g + 1u;

@@ -170,6 +170,17 @@ class FastaUtility:
             out[a], out[b] = b, a
         return out
 
+    def wildcards(self, symbols="n"):
+        """The token ids of the symbols that stand for "unknown" — ``n`` for DNA, pass ``"x"`` for protein —: what
+        ``FastSK(..., wildcards=...)`` takes. A symbol not seen yet gets its id now (as in ``complement()``), so that a file
+        read later through this object agrees with the list."""
+        out = []
+        for sym in symbols:
+            idx = self._vocab.add(str(sym).lower())
+            if idx not in out:
+                out.append(idx)
+        return out
+
     def shortest_seq(self, data_file):
         _, offsets, _ = self.read_packed(data_file)
         return int(np.diff(offsets).min())

@@ -33,7 +33,8 @@ extern "C" {
                               4: fsk_set_tuning / fsk_get_tuning / fsk_tuning_keys (one FSK_TUNING variable instead of
                                  two dozen FSK_* switches);
                               5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
-                                 (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers) */
+                                 (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers;
+                                  fsk_set_wildcards) */
 
 enum {
     FSK_OK = 0,
@@ -133,7 +134,8 @@ typedef struct fsk_stats {
                                 remainder products of the rows with counts above 15 included (profile = 1)  */
     uint64_t panel_bytes;    /* bytes of count panels written (= read at least once)            */
     double u4_tile_launches; /* launches of the 4-bit tile kernel (v_dot8_u32_u4)                */
-    double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo */
+    double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo
+                                (wildcards set: of the windows free of them) */
     double count_launches;   /* launches of the segment-count kernel (panel cache misses)        */
     double compact_keys_avg; /* key compaction on: mean keys per combo that really occur (else 0) */
     double batches_redone;   /* sparse: batches enqueued ahead of their word count that did not fit */
@@ -223,6 +225,20 @@ int fsk_set_seed(fsk_engine* e, uint64_t seed);
  * token, when the data hold a token the map does not list (nothing is self-complemented silently). The alphabet of
  * a load is the closure under the map of the tokens present. */
 int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
+
+/* Wildcard symbols (the unknown base 'n' of DNA, the 'x' of protein): the n token ids listed are WILDCARDS. A g-window
+ * that holds a wildcard at ANY of its g positions is not a window — for every combination, whether or not the combination
+ * keeps the position. Everything else is this header's algorithm on the windows that remain (per-combination counts, the
+ * sum over combinations, reverse complement, the mismatch-weighted kernels, both approx modes, normalisation): with the
+ * fragments of x its maximal wildcard-free runs of at least g symbols, K(x, y) = sum over the fragments s of x and t of y
+ * of the plain K(s, t). n = 0 switches the mode off (the default). Takes effect from the next fsk_load_sequences /
+ * fsk_compute; a group handle sets it on every engine; the levels of the mismatch-weighted mode inherit it. FSK_EINVAL on a
+ * null array, a negative n or a token listed twice. At load: a sequence without a single wildcard-free window has no
+ * features and would have a zero diagonal — FSK_ESHORT naming its index, as for a sequence shorter than g; in
+ * reverse-complement mode a wildcard need not be listed in the complement map, and when it is its complement must be a
+ * wildcard too, else FSK_EINVAL naming the token. fsk_stats: n_feat and max_windows count the valid windows (they bound a
+ * cell), alphabet and key_space the real symbols only. A wildcard that does not occur in the data changes nothing. */
+int fsk_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
 
 /* Mismatch-weighted kernels (the mismatch-truncated gapped k-mer kernel LS-GKM ships as "-l 11 -k 7 -d 3", the l-mer
  * filters of Ghandi et al., "pairs of l-mers within d mismatches"). With N_h(x, y) the number of pairs (one g-window of x,
