@@ -182,6 +182,13 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
         FSK_HIP(e->d_lut.reserve((size_t)chunk * Vkeys));
         FSK_HIP(e->d_vc.reserve((size_t)chunk));
     }
+    // Shift classes (fsk_engine_dense_shift.hip): one weighted Gram product per chain of combinations that differ by a shift of
+    // all kept positions, the other members by edge lookups. Checked per call; any other call runs as it always did. The
+    // 16384 tiles of the default are a condition, not a tuned number: from there a tile has one workgroup anyway.
+    const bool use_shift = e->tune.dense_shift >= 0 && chunk == n && n >= 2 && !compact && !e->revcomp && !e->wild &&
+                           !(e->mm_on() && !e->mm_plain) && Vq8 <= 32 && first_test_tile == 0xffffffffu && !e->cfg.skip_test_block &&
+                           ((e->tune.tile_splits == 0 && n_tiles >= 16384) || (e->tune.tile_splits == 1 && e->tune.dense_shift > 0)) &&
+                           dense_shift_plan(e, combos, n, by_overflow);
     std::vector<uint16_t> h_vc;
     std::vector<uint8_t> pos;
     const uint8_t* chunk_pos = e->d_pos.p;  // the kept positions of the chunk at hand, on the device
@@ -189,13 +196,13 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
         const int nb = std::min(chunk, n - s);
         // the count panels of an unchanged single-chunk combo list are reused by the FOLLOWING row
         // bands of one pass (row0 > 0); a call that starts at row 0 always recounts
-        const bool cached = row0 > 0 && e->prep_valid && nb == n && (int)e->prep_combos.size() == n &&
+        const bool cached = row0 > 0 && e->prep_valid && nb == n && (int)e->prep_combos.size() == n && e->prep_shift == use_shift &&
                             std::equal(combos, combos + n, e->prep_combos.begin());
         if (!cached) {
             e->prep_valid = false;
             // the chunk's kept positions: a run of consecutive combo ids (every exact call: 0, 1, 2, ...) reads them from the
             // resident table of all combos, uploaded once per engine; any other list is gathered and uploaded
-            bool consecutive = true;
+            bool consecutive = !use_shift;  // (the shift plan's slot order: chain bases first)
             for (int q = 1; q < nb && consecutive; ++q) consecutive = combos[s + q] == combos[s] + q;
             if (consecutive) {
                 if (!e->allpos_ready) {
@@ -208,7 +215,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             } else {
                 pos.resize((size_t)nb * e->k);
                 for (int q = 0; q < nb; ++q)
-                    memcpy(&pos[(size_t)q * e->k], &e->all_pos[(size_t)combos[s + q] * e->k], e->k);
+                    memcpy(&pos[(size_t)q * e->k], &e->all_pos[(size_t)combos[s + (use_shift ? e->shift.order[(size_t)q] : q)] * e->k], e->k);
                 FSK_HIP(hipMemcpyAsync(e->d_pos.p, pos.data(), pos.size(), hipMemcpyHostToDevice, e->stream));
                 FSK_HIP(hipMemsetAsync(e->d_flag.p, 0, sizeof(uint32_t), e->stream));
                 FSK_HIP(hipStreamSynchronize(e->stream));  // `pos` is a pageable temporary
@@ -302,9 +309,16 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                                e->d_U.p, compact ? (const uint16_t*)e->d_vc.p : (const uint16_t*)nullptr);
                 }
             }
+            if (use_shift && !e->prep_overflow) {  // the edge keys stay with the panels: row bands reuse them
+                e->tic();
+                const int rck = dense_shift_edge_keys(e, chunk_pos, panels_pad);
+                if (rck) return rck;
+                e->toc(&e->st.ms_tile);
+            }
             if (nb == n) {
                 e->prep_combos.assign(combos, combos + n);
                 e->prep_valid = true;
+                e->prep_shift = use_shift;
             }
         }
         if (e->prep_overflow) {
@@ -344,6 +358,8 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             n_splits = std::max(1, std::min({n_splits, nb, 4096}));
         }
         if (e->tune.tile_splits > 0) n_splits = std::min({nb, (int)e->tune.tile_splits, 4096});
+        if (use_shift && n_splits != 1) return e->fail(FSK_ESTATE, "internal: the shift-class plan with a split tile launch");
+        const int n_mult = use_shift ? (int)e->shift.n_bases : nb;  // slots the tile launch multiplies
         const int slots_per_split = (nb + n_splits - 1) / n_splits;
         n_splits = (nb + slots_per_split - 1) / slots_per_split;
         // Store instead of add? Only the first launch over rows that are still "zero by contract",
@@ -365,13 +381,16 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             }
         }
         if (e->profile_sync())  // the flagged rows' remainder products of this launch, for fsk_stats.dense_macs (read by fsk_get_stats)
-            FSK_LAUNCH(fsk::k_dense_remainder_rows, dim3((uint32_t)((n_tiles + 255) / 256), (uint32_t)nb), dim3(256), 0, e->stream,
+            FSK_LAUNCH(fsk::k_dense_remainder_rows, dim3((uint32_t)((n_tiles + 255) / 256), (uint32_t)n_mult), dim3(256), 0, e->stream,
                        (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (uint32_t)n_tiles, (uint32_t)nb, nst, compact ? 1 : 0,
                        e->d_U.p + 1);
         e->tic();
         // (small N, the combo range split over several workgroups a tile: their sums through 32-bit staging blocks, not atomics)
         const bool small = n_splits >= 2 && e->tune.dense_small != 0 && dense_small_stage_bytes(n_tiles, n_splits) <= ((size_t)2 << 30);
-        if (small) {
+        if (use_shift) {
+            const int rcs = dense_shift_tiles(e, n_tiles, nb, Vq8, nst, K, store, panels_pad);
+            if (rcs) return rcs;
+        } else if (small) {
             const int rcs = dense_tile_small(e, compact, n_tiles, n_splits, nb, Vq8, nst, K, slots_per_split);
             if (rcs) return rcs;
         } else if (compact)
@@ -382,7 +401,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                        e->d_rowmask.p, e->d_tiletab.p, nb, Vq8, nst, (uint32_t)e->N, K, slots_per_split, store);
         e->toc(&e->st.ms_tile);
         e->st.n_tile_launches += 1;
-        u64 row_sum = (u64)Vq8 * (u64)nb;  // dword rows multiplied per tile (the flagged rows' remainder products are added by fsk_get_stats)
+        u64 row_sum = (u64)Vq8 * (u64)n_mult;  // dword rows multiplied per tile (the flagged rows' remainder products are added by fsk_get_stats)
         if (compact && (int)e->h_vc_cache.size() == nb) {
             row_sum = 0;
             for (uint16_t v : e->h_vc_cache) row_sum += (v + 7u) / 8u;

@@ -1,0 +1,128 @@
+// fsk_engine_dense_shift.hip — the DENSE dataflow by shift classes (the headline, config 5: 495 combinations of g = 12, k = 4
+// are 165 shapes at up to nine shifts): one weighted Gram product per chain of consecutive shifts and the other members by
+// edge lookups (fsk_kernels_dense_shift.h has the identity). The reference work it stands for is the same as
+// fsk_engine_dense.hip's: cntsrtna + countAndUpdateTri per combo (shared.cpp:156-191, 268-333).
+//
+//   dense_shift_plan   host arithmetic on the kept positions: shapes -> chains -> slot order (chain bases first, grouped by
+//                      chain length), the groups of the base launch, the derived steps. Cached by the combination list.
+//   k_dense_edge_keys  the two keys of every (sequence, derived step), once per counted list
+//   k_dense_tile_shift the body of the headline kernel (fsk_tile_kernel_dma.inc, FSK_DMA_SHIFT) over the chain bases, one
+//                      launch per group of equal chain length n, whose sums leave as (u64) sum x n: the first launch stores
+//                      when the pass may (every cell j <= i, zeros included), the later ones add their non-zero cells. (One
+//                      launch that flushes and clears at every group end keeps 64 sums, the flush's index arithmetic and the
+//                      pipeline's state live at once: 128 VGPRs and 92 bytes of scratch a lane from the compiler.)
+//   k_dense_shift_fix  the derived steps
+//
+// A translation unit of its own, like fsk_engine_dense_small.hip: nothing here can reach the register allocation of
+// k_dense_tile_dma / k_dense_tile_dma_compact.
+#include "fsk_engine_internal.h"
+#include "fsk_kernels_dense_shift.h"
+
+#include <map>
+
+using namespace fsk_detail;
+
+namespace fsk {
+
+#define FSK_DMA_SHIFT 1
+#define FSK_DMA_KERNEL k_dense_tile_shift
+#define FSK_DMA_COMPACT 0
+#include "fsk_tile_kernel_dma.inc"
+#undef FSK_DMA_KERNEL
+#undef FSK_DMA_COMPACT
+#undef FSK_DMA_SHIFT
+
+}  // namespace fsk
+
+namespace fsk_detail {
+
+// The plan of a combination list. Combinations are grouped by shape (kept positions minus the first), sorted by shift inside
+// a shape and cut into chains of consecutive shifts: a list with gaps, in any order or with a repeated id simply gives
+// shorter chains, a chain of one is a plain slot of weight 1. Returns whether the shift path can run the list: some chain has
+// a derived step, and the correction sums stay inside int32.
+bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow) {
+    ShiftPlan& p = e->shift;
+    if (!(p.by_overflow == by_overflow && (int)p.combos.size() == n && std::equal(combos, combos + n, p.combos.begin()))) {
+        p = ShiftPlan();
+        p.combos.assign(combos, combos + n);
+        p.by_overflow = by_overflow;
+        const int k = e->k;
+        std::map<std::vector<uint8_t>, std::vector<std::pair<int, int>>> shapes;  // shape -> (shift, place in the list)
+        for (int q = 0; q < n; ++q) {
+            const uint8_t* pos = &e->all_pos[(size_t)combos[q] * k];
+            std::vector<uint8_t> shape(pos, pos + k);
+            for (auto& x : shape) x = (uint8_t)(x - pos[0]);
+            shapes[shape].push_back({(int)pos[0], q});
+        }
+        std::vector<std::vector<int>> chains;
+        for (auto& kv : shapes) {
+            auto& v = kv.second;
+            std::stable_sort(v.begin(), v.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+            for (size_t i = 0; i < v.size(); ++i) {
+                if (i == 0 || v[i].first != v[i - 1].first + 1) chains.emplace_back();
+                chains.back().push_back(v[i].second);
+            }
+        }
+        std::stable_sort(chains.begin(), chains.end(), [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() > b.size(); });
+        p.n_bases = (uint32_t)chains.size();
+        p.order.resize((size_t)n);
+        uint32_t derived = p.n_bases;
+        size_t group_begin = 0;
+        for (size_t c = 0; c < chains.size(); ++c) {
+            const std::vector<int>& ch = chains[c];
+            const uint32_t len = (uint32_t)ch.size();
+            p.order[c] = ch[0];
+            // groups of equal chain length, of at most by_overflow slots (u32 sums; the product by the length is taken in 64 bits)
+            if (c == 0 || chains[c - 1].size() != ch.size() || (u64)(c - group_begin) >= by_overflow) {
+                p.groups.push_back(0u);
+                p.groups.push_back(len);
+                group_begin = c;
+            }
+            p.groups[p.groups.size() - 2] = (uint32_t)c + 1u;  // the group's end slot
+            uint32_t lower = (uint32_t)c;
+            for (uint32_t u = 1; u < len; ++u) {  // step u - 1 -> u of the chain, weight (len - 1) - (u - 1)
+                const uint32_t upper = derived++;
+                p.order[upper] = ch[u];
+                p.steps.push_back(upper << 16 | lower);
+                p.steps.push_back(len - u);
+                p.wsum += len - u;
+                lower = upper;
+            }
+        }
+    }
+    return !p.steps.empty() && n <= 32768 && ((u64)2 * e->maxW + 32) * p.wsum < ((u64)1 << 31);
+}
+
+// the plan's tables on the device, and the edge keys of the list just counted (chunk_pos: its kept positions in slot order)
+int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad) {
+    ShiftPlan& p = e->shift;
+    const uint32_t n_steps = (uint32_t)(p.steps.size() / 2), np_seq = panels_pad * fsk::PANEL;
+    FSK_HIP(e->d_shift_steps.reserve(p.steps.size()));
+    FSK_HIP(e->d_edge_keys.reserve((size_t)n_steps * np_seq));
+    FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p, p.steps.data(), p.steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_LAUNCH(fsk::k_dense_edge_keys, dim3(panels_pad, (n_steps + 3u) / 4u), dim3(256), 0, e->stream, e->view(), e->cfg.g, e->k, e->sigma, chunk_pos,
+               (const uint32_t*)e->d_shift_steps.p, n_steps, np_seq, e->d_edge_keys.p);
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors are pageable memory)
+    e->st.launches += 1;
+    return FSK_OK;
+}
+
+// the tile pass of accumulate_dense: the weighted base products, then the corrections
+int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t nst, u64* K, int store, uint32_t panels_pad) {
+    const ShiftPlan& p = e->shift;
+    int slot0 = 0;
+    for (size_t gi = 0; gi + 1 < p.groups.size(); gi += 2) {  // {end slot, chain length}
+        const int end = (int)p.groups[gi];
+        FSK_LAUNCH(fsk::k_dense_tile_shift, dim3((uint32_t)n_tiles, 1), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
+                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, nb, Vq8, nst, (uint32_t)e->N, K, end - slot0, gi == 0 ? store : 0,
+                   slot0, p.groups[gi + 1]);
+        slot0 = end;
+    }
+    FSK_LAUNCH(fsk::k_dense_shift_fix, dim3((uint32_t)n_tiles), dim3(512), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
+               (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
+               (const uint16_t*)e->d_edge_keys.p, panels_pad * fsk::PANEL, nb, Vq8, (uint32_t)e->N, K);
+    e->st.launches += (int32_t)(p.groups.size() / 2);  // (the groups and the corrections; the caller counts one)
+    return FSK_OK;
+}
+
+}  // namespace fsk_detail

@@ -93,6 +93,7 @@ using fsk_detail::DevBuf;
     X(compact_rare, -1, -1, 1, "dense: keys that occur from the places of the rare symbols (1) or a marking pass over every window (0)") \
     X(tile_splits, 0, 0, 4096, "dense: combo splits per tile (0: by the size of the launch)")                                        \
     X(dense_small, 0, 0, 1, "dense: 1 = a split tile launch (small N) leaves its sums as 32-bit staging blocks that k_dense_widen adds into K (0: one 64-bit atomic a cell and split — measured faster: the atomics drain under other workgroups' dot products)")                                        \
+    X(dense_shift, 0, -1, 1, "dense: one weighted Gram product per chain of shifted combinations, the other members by edge lookups (fsk_engine_dense_shift.hip) — 1 = whenever the call is eligible, -1 = never (0: when eligible, tile_splits = 0 and the launch has 16384 tiles or more, the size from which a tile has one workgroup anyway)") \
     X(dense_chunk, 0, 0, 1 << 24, "dense: cap of the count kernel's staging chunk, in windows (0: none)")                             \
     X(variance_dense_slots, 1, 0, 1, "variance mode, dense: 0 = zero fill + k_welford per iteration instead of storing slot triangles") \
     X(var_slots16, 1, 0, 1, "variance mode, sparse: 0 = u32 slot triangles from the start")                                          \
@@ -169,6 +170,18 @@ struct SxScratch {
         d_tile_stat.release(); d_segc.release(); d_tile_lrh.release(); d_tile_rs.release(); d_tile_lth.release(); d_tile_ts.release();
         d_E.release(); d_sxstat.release();
     }
+};
+
+// The shift-class plan of a combination list (fsk_engine_dense_shift.hip): the count panels' slot order — chain bases first,
+// grouped by chain length, then the derived members —, the base launch's groups {end slot, weight} and the derived steps
+// {upper slot << 16 | lower slot, weight}.
+struct ShiftPlan {
+    std::vector<int32_t> combos;   // the list the plan was made for
+    u64 by_overflow = 0;           // ... and the most slots a u32 sum takes
+    std::vector<int32_t> order;    // slot -> place in the list
+    std::vector<uint32_t> groups, steps;
+    uint32_t n_bases = 0;
+    u64 wsum = 0;                  // sum of the steps' weights
 };
 
 struct fsk_engine {
@@ -273,6 +286,10 @@ struct fsk_engine {
     uint32_t tab_ftt = 0xffffffffu;               // ... and the first all-test tile column it was built for (skip_test_block)
     std::vector<int32_t> prep_combos;              // combos whose count panels are resident
     bool prep_valid = false, prep_overflow = false;
+    bool prep_shift = false;                       // ... in the slot order of the shift-class plan, with its edge keys
+    ShiftPlan shift;
+    DevBuf<uint32_t> d_shift_steps;
+    DevBuf<uint16_t> d_edge_keys;                  // [derived step][panel][dword of the panel row]: delta | sigma << 8
     // sparse scratch
     SxScratch sxs[2];                     // lane 0: every exact accumulate; lanes 0 and 1: variance mode's batches in flight
     hipStream_t lane_stream = nullptr;    // lane 1's stream (lane 0 runs on `stream`)
@@ -462,6 +479,11 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
 // fsk_engine_dense_small.hip: the split tile launch at small N through 32-bit staging blocks
 size_t dense_small_stage_bytes(u64 n_tiles, int n_splits);
 int dense_tile_small(fsk_engine* e, bool compact, u64 n_tiles, int n_splits, int nb, uint32_t Vq8, uint32_t nst, u64* K, int slots_per_split);
+
+// fsk_engine_dense_shift.hip: one weighted Gram product per chain of shifted combinations, the rest by edge lookups
+bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow);
+int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad);
+int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t nst, u64* K, int store, uint32_t panels_pad);
 
 // fsk_engine_sparse.hip
 // which lane (scratch set + stream) the deferred batch `defer` of variance mode runs in

@@ -7,6 +7,9 @@
 //   k_dense_tile_small / k_dense_tile_small_compact   small N, the combo range split over several workgroups a tile: a
 //       workgroup's 128 x 128 partial sums leave as PLAIN 32-bit stores into a staging block of its own (one 1 KB store a
 //       wave and register) instead of one 64-bit atomic a cell and split; k_dense_widen adds a tile's blocks into K.
+// and once more, in fsk_engine_dense_shift.hip, with FSK_DMA_SHIFT 1:
+//   k_dense_tile_shift   a group of chain bases of the shift-class plan, slots [slot0, slot0 + slots_per_split) of the n_slots
+//       counted: every sum leaves multiplied by `weight`, the group's chain length, the product taken in 64 bits.
 // Two plain functions rather than one template: instantiations of one template share register-
 // allocation context on hipcc, and a second variant must not perturb the common one.
 //
@@ -42,6 +45,9 @@
 #ifndef FSK_DMA_STAGE32
 #define FSK_DMA_STAGE32 0
 #endif
+#ifndef FSK_DMA_SHIFT
+#define FSK_DMA_SHIFT 0
+#endif
 __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, const uint32_t* C4H, const uint32_t* rowmask,
                                                         const uint32_t* tile_tab, int n_slots, uint32_t Vq8, uint32_t nst,
                                                         uint32_t N,
@@ -53,6 +59,9 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
                                                         int slots_per_split, int store
 #if FSK_DMA_COMPACT
                                                         , const uint16_t* vc
+#endif
+#if FSK_DMA_SHIFT
+                                                        , int slot0, uint32_t weight
 #endif
 ) {
     constexpr int MAXF = 4;           // flagged rows whose hi plane is fetched per round
@@ -71,7 +80,11 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     const uint32_t tile = tile_tab[blockIdx.x];
     const uint32_t ti = tile >> 16, tj = tile & 0xffffu;
+#if FSK_DMA_SHIFT
+    const int s0 = slot0;
+#else
     const int s0 = blockIdx.y * slots_per_split;
+#endif
     const int s1 = s0 + slots_per_split < n_slots ? s0 + slots_per_split : n_slots;
 #if !FSK_DMA_STAGE32
     if (s0 >= s1) return;
@@ -315,8 +328,13 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
             // are stored, not added: the pass needs no 8 N^2/2-byte fill in front of it.
             if (j <= i && (store || acc[a][b] != 0u)) {
                 const uint32_t lo = fsk_hw::vgpr_copy(acc[a][b]);  // a copy: see the header
+#if FSK_DMA_SHIFT
+                if (store) K[tri_index(i, j)] = (u64)lo * weight;
+                else atomicAdd(&K[tri_index(i, j)], (u64)lo * weight);
+#else
                 if (store) K[tri_index(i, j)] = (u64)lo;
                 else atomicAdd(&K[tri_index(i, j)], (u64)lo);
+#endif
             }
         }
     }

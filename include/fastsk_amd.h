@@ -120,18 +120,22 @@ typedef struct fsk_stats {
                                 count panels by k_dense_distinct when profile = 1, else 0)                */
     uint64_t sort_records;   /* records pushed through the radix sort                           */
     int32_t sort_passes;     /* 8-bit LSD passes per batch                                      */
-    int32_t launches;        /* kernel launches in accumulate                                   */
+    int32_t launches;        /* kernel launches in accumulate (shift classes: the edge-key kernel, every group's
+                                base launch and the correction launch count here only)         */
     /* HIP-event milliseconds on the engine's stream (profile=1), summed over launches         */
     double ms_count;         /* dense: k-mer extraction + LDS counting sort -> count panels     */
-    double ms_tile;          /* dense: tiled co-occurrence accumulate + flush                   */
+    double ms_tile;          /* dense: tiled co-occurrence accumulate + flush (shift classes: with the edge
+                                keys and the corrections)                                       */
     double ms_extract;       /* sparse: key extraction                                          */
     double ms_sort;          /* sparse: radix sort                                              */
     double ms_segment;       /* sparse: run/segment detection + compaction                      */
     double ms_pairs;         /* sparse: per-run pair atomics                                    */
     double ms_total;         /* whole accumulate calls                                          */
-    int64_t n_tile_launches; /* launches of the tile kernel (for per-launch averages)           */
+    int64_t n_tile_launches; /* tile passes: one per chunk and row band, however many kernels a pass launches */
     uint64_t dense_macs;     /* count multiply-adds issued by the tile kernel: 8 per dword row and cell, the exact
-                                remainder products of the rows with counts above 15 included (profile = 1)  */
+                                remainder products of the rows with counts above 15 included (profile = 1). Shift
+                                classes (tuning dense_shift): the chain bases alone, tiles x rows x bases x 8 x 128^2 —
+                                the derived combinations cost lookups, not multiply-adds        */
     uint64_t panel_bytes;    /* bytes of count panels written (= read at least once)            */
     double u4_tile_launches; /* launches of the 4-bit tile kernel (v_dot8_u32_u4)                */
     double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo
