@@ -2,7 +2,7 @@
 ``FastSK(g, m, ...).compute_kernel(Xtrain, Xtest)`` path)."""
 from .utils import FastaUtility, Vocabulary  # noqa: F401
 
-__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels"]
+__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile"]
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "mismatch_levels":  # (host only, but it lives in the HIP library)
         from ._native import mismatch_levels
         return mismatch_levels
+    if name == "center_profile":  # (host only, pure Python)
+        from ._native import center_profile
+        return center_profile
     raise AttributeError(name)

@@ -77,7 +77,7 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_counts_digest", "fsk_alloc_block_device", "fsk_free_device", "fsk_set_skip_test_block",
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
            "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
-           "fsk_set_wildcards"]
+           "fsk_set_wildcards", "fsk_set_center_weights"]
 
 
 _hip_shared = False
@@ -211,6 +211,7 @@ class Library:
             "fsk_seed_order": ([C.c_uint64, i64, vp], C.c_int),
             "fsk_set_complement": ([vp, vp, vp, i32], C.c_int),
             "fsk_set_wildcards": ([vp, vp, i32], C.c_int),
+            "fsk_set_center_weights": ([vp, vp, i32], C.c_int),
             "fsk_set_mismatch_weights": ([vp, vp, i32], C.c_int),
             "fsk_get_mismatch_info": ([vp, C.POINTER(i32), vp, vp, i32], C.c_int),
             "fsk_get_mismatch_times": ([vp, vp, vp, i32], C.c_int),
@@ -321,6 +322,55 @@ def wildcard_array(wildcards):
     return np.array(out, dtype=np.int32)
 
 
+def center_weight_array(center_weights):
+    """The ``center_weights=`` keyword -> uint32 array for ``fsk_set_center_weights``, checked as the engine checks it (at
+    most 4096 integers in 0..255, the first at least 1): ``ValueError`` otherwise. ``None`` / ``False`` / an empty sequence:
+    an empty array, i.e. the mode off."""
+    if center_weights is None or center_weights is False:
+        return np.zeros(0, dtype=np.uint32)
+    if isinstance(center_weights, (str, bytes)) or not hasattr(center_weights, "__iter__"):
+        raise ValueError("center_weights must be None or a sequence of integers")
+    out = []
+    for w in center_weights:
+        if isinstance(w, bool) or not isinstance(w, (int, np.integer)):
+            raise ValueError("center_weights: weights must be integers, got %r" % (w,))
+        if not 0 <= int(w) <= 255:
+            raise ValueError("center_weights: weights must lie in 0..255, got %d" % int(w))
+        out.append(int(w))
+    if len(out) > 4096:
+        raise ValueError("center_weights: %d entries, at most 4096" % len(out))
+    if out and out[0] == 0:
+        raise ValueError("center_weights: the first entry (the centre's weight) must be at least 1")
+    return np.array(out, dtype=np.uint32)
+
+
+def center_profile(plateau, halflife, levels=8, floor=0):
+    """A centre-weight profile for ``center_weights=`` (host only): ``levels`` within ``plateau`` windows of the centre,
+    halved every ``halflife`` windows beyond, rounded to integers and never below ``floor`` --
+    ``w[d] = max(floor, int(levels * 2 ** (-max(0, d - plateau) / halflife) + 0.5))`` -- cut where it first reaches its
+    final constant (the last entry extends outwards). The shape of LS-GKM's ``-M`` / ``-H`` weighting, quantised; not its
+    constants. ``ValueError`` when the arguments are out of range or the profile would be longer than 4096 entries."""
+    for name, v in (("plateau", plateau), ("levels", levels), ("floor", floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("center_profile: %s must be an integer" % name)
+    if plateau < 0 or not 1 <= levels <= 255 or not 0 <= floor <= 255:
+        raise ValueError("center_profile: need plateau >= 0, 1 <= levels <= 255 and 0 <= floor <= 255")
+    if not halflife > 0:
+        raise ValueError("center_profile: halflife must be positive")
+    final = max(int(floor), 0)  # (the weight decays to 0 before rounding: the final constant is the floor)
+    out = []
+    d = 0
+    while True:
+        w = max(int(floor), int(levels * 2.0 ** (-max(0, d - plateau) / float(halflife)) + 0.5))
+        out.append(w)
+        if w == final:
+            break
+        d += 1
+        if d >= 4096:
+            raise ValueError("center_profile: the profile reaches its final constant past 4096 entries")
+    return out
+
+
 def mismatch_levels(g, weights, lib=None):
     """The level coefficients ``a_0..a_d`` of mismatch weights ``c_0..c_m`` at window length ``g`` (``fsk_mismatch_levels``, host
     only): ``sum_h c_h N_h == sum_j a_j S_j`` with ``S_j`` the raw kernel of ``(g, m=j)``. ``d`` is the last ``h`` with
@@ -394,9 +444,10 @@ class Engine:
     def __init__(self, g, m, t=-1, approx=False, delta=0.025, max_iters=-1, skip_variance=False, device=0,
                  path=PATH_AUTO, profile=False, lib=None, skip_test_block=False, devices=None, collective=COLL_AUTO,
                  bands=0, deadline_ms=0, tuning=None, revcomp=None, weights=None, max_mismatches=None,
-                 wildcards=None):
+                 wildcards=None, center_weights=None):
         weights = mismatch_weights(g, m, weights, max_mismatches)
         wildcards = wildcard_array(wildcards)
+        center_weights = center_weight_array(center_weights)
         if weights is not None and approx:
             raise ValueError("weights= / max_mismatches= with approx=True: a sample of combinations under signed level "
                              "coefficients estimates nothing")
@@ -427,6 +478,7 @@ class Engine:
         self._keep = None
         self.revcomp = False
         self.wildcards = []
+        self.center_weights = None
         for key, value in (tuning or {}).items():
             self.set_tuning(key, value)
         self.weights = None
@@ -435,6 +487,8 @@ class Engine:
                 self.set_complement(revcomp)
             if len(wildcards):
                 self.set_wildcards(wildcards)
+            if len(center_weights):
+                self.set_center_weights(center_weights)
             if weights is not None:
                 self.set_mismatch_weights(weights)
         except Exception:
@@ -509,6 +563,20 @@ class Engine:
             raise ValueError("wildcards must be 1-D")
         self._ck(self.lib.L.fsk_set_wildcards(self.h, tokens.ctypes.data if len(tokens) else None, len(tokens)))
         self.wildcards = sorted(int(t) for t in tokens)
+
+    def set_center_weights(self, center_weights):
+        """Centre-weighted mode from the next ``load_sequences`` / ``compute`` on: window p of a sequence of length L counts
+        ``w[min(|2p + g - L| // 2, len(w) - 1)]`` times (``center_profile()`` builds such a ``w``). ``None`` or ``[]``
+        switch it off. Checked here (``ValueError``) as the engine checks it."""
+        self.set_center_weight_array(center_weight_array(center_weights))
+
+    def set_center_weight_array(self, w):
+        """``fsk_set_center_weights`` as it is: one uint32 array, checked by the engine alone."""
+        w = np.ascontiguousarray(w, dtype=np.uint32)
+        if w.ndim != 1:
+            raise ValueError("center_weights must be 1-D")
+        self._ck(self.lib.L.fsk_set_center_weights(self.h, w.ctypes.data if len(w) else None, len(w)))
+        self.center_weights = [int(x) for x in w] if len(w) else None
 
     def set_mismatch_weights(self, weights):
         """Mismatch-weighted mode from the next ``compute`` on: ``weights`` are ``c_0..c_m`` (``W = sum_h c_h N_h``, N_h the
@@ -700,5 +768,6 @@ class Engine:
         d = s.as_dict()
         d["revcomp"] = self.revcomp  # (as set: in force from the next load on)
         d["wildcards"] = list(self.wildcards)
+        d["center_weights"] = None if self.center_weights is None else list(self.center_weights)
         d["weights"] = None if self.weights is None else list(self.weights)  # (mismatch-weighted mode, as set)
         return d

@@ -7,7 +7,7 @@
 //   - errors raise ValueError / RuntimeError instead of printf + exit(1) (fastsk.cpp:53-58);
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
 //     NotImplementedError (they are unusable from Python in the reference as well);
-//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards), numpy and
+//   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
 //   - skip_test_block (default False: compute_kernel computes the whole N x N triangle, as fastsk.cpp:30-118 does).
@@ -35,6 +35,11 @@
 //   - wildcards (default None: off): token ids that stand for "unknown" (fsk_set_wildcards; FastaUtility.wildcards() returns
 //     the id of DNA's n) — a g-window that holds one at any position is not a window, as in every k-mer tool; the reference
 //     has no such mode and matches n with n. Checked before any device call (ValueError).
+//   - center_weights (default None: off): a profile w of at most 4096 integers in 0..255, w[0] >= 1 (fsk_set_center_weights;
+//     fastsk_amd.center_profile() builds one) — window p of a sequence of length L counts w[min(|2p + g - L| / 2, len(w) - 1)]
+//     times, the centre-weighted gapped k-mer kernel (LS-GKM's "-t 4"); the reference weighs every window 1. Checked before
+//     any device call (ValueError). Keyword-only, in an overload of its own: the signature that ends in wildcards stays as it
+//     was, by position too.
 #include "../../include/fastsk_amd.h"
 
 namespace py = pybind11;
@@ -131,6 +136,7 @@ class FastSK {
     bool lazy_test_block_ = false, test_block_missing_ = false;
     bool revcomp_ = false;
     std::vector<int32_t> wildcards_;
+    std::vector<uint32_t> center_weights_;  // centre-weighted mode: the profile (empty: off)
     std::vector<uint64_t> weights_;      // mismatch-weighted mode: c_0..c_m (empty: off)
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
@@ -242,10 +248,11 @@ public:
     FastSK(int g, int m, int t, bool approx, double delta, int max_iters, bool skip_variance, int device,
            const std::string& path, py::object seed, py::object skip_test_block, py::object devices,
            const std::string& collective, int deadline_ms, py::object revcomp, py::object weights, py::object max_mismatches,
-           py::object wildcards) {
+           py::object wildcards, py::object center_weights) {
         fsk_config c{};
         parse_weights(g, m, weights, max_mismatches);  // (host only: ValueError before any device call)
         parse_wildcards(wildcards);
+        parse_center_weights(center_weights);
         if (!weights_.empty() && approx)
             throw py::value_error("weights= / max_mismatches= with approx=True: a sample of combinations under signed level coefficients estimates nothing");
         if (!weights_.empty() && !devices.is_none())
@@ -279,6 +286,7 @@ public:
             if (!seed.is_none()) check(fsk_set_seed(h_, seed.cast<uint64_t>()));
             set_revcomp(revcomp);
             if (!wildcards_.empty()) check(fsk_set_wildcards(h_, wildcards_.data(), (int32_t)wildcards_.size()));
+            if (!center_weights_.empty()) check(fsk_set_center_weights(h_, center_weights_.data(), (int32_t)center_weights_.size()));
             if (!weights_.empty()) check(fsk_set_mismatch_weights(h_, weights_.data(), (int32_t)weights_.size()));
         } catch (...) {
             fsk_destroy(h_);
@@ -319,6 +327,29 @@ public:
             weights_.clear();
             throw py::value_error(fsk_last_error(nullptr));
         }
+    }
+    // center_weights= -> center_weights_ (empty: off), checked as fsk_set_center_weights checks them
+    void parse_center_weights(const py::object& cw) {
+        center_weights_.clear();
+        if (cw.is_none() || (py::isinstance<py::bool_>(cw) && !cw.cast<bool>())) return;
+        if (py::isinstance<py::str>(cw) || py::isinstance<py::bytes>(cw) || !py::isinstance<py::iterable>(cw))
+            throw py::value_error("center_weights must be None or a sequence of integers");
+        std::vector<uint32_t> out;
+        for (auto t : cw.cast<py::iterable>()) {
+            if (py::isinstance<py::bool_>(t) || !(py::isinstance<py::int_>(t) || py::hasattr(t, "__index__")))
+                throw py::value_error("center_weights: weights must be integers");
+            long long v = -1;
+            try {
+                v = py::int_(t.attr("__index__")()).cast<long long>();
+            } catch (...) {
+                v = -1;
+            }
+            if (v < 0 || v > 255) throw py::value_error("center_weights: weights must lie in 0..255");
+            out.push_back((uint32_t)v);
+            if (out.size() > 4096) throw py::value_error("center_weights: at most 4096 entries");
+        }
+        if (!out.empty() && out[0] == 0) throw py::value_error("center_weights: the first entry (the centre's weight) must be at least 1");
+        center_weights_.swap(out);
     }
     // wildcards= -> wildcards_ (empty: off), checked as fsk_set_wildcards checks them
     void parse_wildcards(const py::object& wildcards) {
@@ -492,6 +523,12 @@ public:
             for (int32_t v : wildcards_) wl.append(v);
             d["wildcards"] = wl;
         }
+        if (center_weights_.empty()) d["center_weights"] = py::none();
+        else {
+            py::list cl;
+            for (uint32_t v : center_weights_) cl.append(v);
+            d["center_weights"] = cl;
+        }
         if (weights_.empty()) d["weights"] = py::none();
         else {
             py::list w;
@@ -551,14 +588,29 @@ public:
 PYBIND11_MODULE(_fastsk, m) {
     m.doc() = "MI355X-native gapped-k-mer kernel engine behind the FastSK Python surface";
     py::class_<FastSK>(m, "FastSK")
-        .def(py::init<int, int, int, bool, double, int, bool, int, const std::string&, py::object, py::object, py::object,
-                      const std::string&, int, py::object, py::object, py::object, py::object>(),
+        // (two overloads: the signature as it was, wildcards its last keyword, by position or by name; and the same followed
+        // by center_weights, keyword-only and without a default, so that a call that does not name it is the first's)
+        .def(py::init([](int g, int m, int t, bool approx, double delta, int max_iters, bool skip_variance, int device,
+                         const std::string& path, py::object seed, py::object skip_test_block, py::object devices,
+                         const std::string& collective, int deadline_ms, py::object revcomp, py::object weights,
+                         py::object max_mismatches, py::object wildcards) {
+                 return new FastSK(g, m, t, approx, delta, max_iters, skip_variance, device, path, seed, skip_test_block, devices,
+                                   collective, deadline_ms, revcomp, weights, max_mismatches, wildcards, py::none());
+             }),
              py::arg("g"), py::arg("m"), py::arg("t") = -1, py::arg("approx") = false, py::arg("delta") = 0.025,
              py::arg("max_iters") = -1, py::arg("skip_variance") = false, py::arg("device") = 0,
              py::arg("path") = "auto", py::arg("seed") = py::none(), py::arg("skip_test_block") = false,
              py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0,
              py::arg("revcomp") = py::none(), py::arg("weights") = py::none(), py::arg("max_mismatches") = py::none(),
              py::arg("wildcards") = py::none())
+        .def(py::init<int, int, int, bool, double, int, bool, int, const std::string&, py::object, py::object, py::object,
+                      const std::string&, int, py::object, py::object, py::object, py::object, py::object>(),
+             py::arg("g"), py::arg("m"), py::arg("t") = -1, py::arg("approx") = false, py::arg("delta") = 0.025,
+             py::arg("max_iters") = -1, py::arg("skip_variance") = false, py::arg("device") = 0,
+             py::arg("path") = "auto", py::arg("seed") = py::none(), py::arg("skip_test_block") = false,
+             py::arg("devices") = py::none(), py::arg("collective") = "auto", py::arg("deadline_ms") = 0,
+             py::arg("revcomp") = py::none(), py::arg("weights") = py::none(), py::arg("max_mismatches") = py::none(),
+             py::arg("wildcards") = py::none(), py::kw_only(), py::arg("center_weights"))
         .def("compute_kernel", &FastSK::compute_kernel, py::arg("Xtrain"), py::arg("Xtest"))
         .def("compute_kernel_flat", &FastSK::compute_kernel_flat, py::arg("tokens").noconvert(), py::arg("offsets").noconvert(),
              py::arg("n_train"))

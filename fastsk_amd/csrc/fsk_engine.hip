@@ -227,7 +227,7 @@ bool dense_is_cheaper(const fsk_engine* e) {
 }
 
 int choose_path(fsk_engine* e) {
-    bool dense_ok = e->V <= DENSE_MAX_KEYS && e->bits <= 8 && e->k <= 16 && e->Lmax < 65536 && e->maxW < 65536 && dense_plan(e->maxW1, e->cfg.g, e->Vq).CH > 0;
+    bool dense_ok = e->V <= DENSE_MAX_KEYS && e->bits <= 8 && e->k <= 16 && e->Lmax < 65536 && e->maxW < 65536 && dense_plan(e->maxW1, e->cfg.g, e->Vq, dense_mode_lds(e)).CH > 0;
     if (e->cfg.path == FSK_PATH_DENSE) {
         if (!dense_ok)
             return e->fail(FSK_EUNSUPPORTED, "dense path needs alphabet^k <= %llu and the panel histogram to fit in LDS",
@@ -474,7 +474,7 @@ void fsk_detail::one_destroy(fsk_engine* e) {
     if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
     if (e->chain_stream) (void)hipStreamSynchronize(e->chain_stream);  // (variance mode may leave a dropped batch's sums running)
     e->d_words.release(); e->d_wstart.release(); e->d_len.release(); e->d_fstart.release(); e->d_featseq.release(); e->d_win.release(); e->d_comp.release();
-    e->d_vbits.release(); e->d_vstart.release(); e->d_fwin.release();
+    e->d_vbits.release(); e->d_vstart.release(); e->d_fwin.release(); e->d_cw.release();
     e->d_pos.release(); e->d_allpos.release(); e->d_bsum.release(); e->d_seqblk.release(); e->K_store.release(); e->d_Kf64.release(); e->d_Khat.release(); e->d_prod.release();
     e->d_diag.release(); e->d_stage.release(); e->d_stage_u64.release(); e->d_Kslots.release(); e->d_cell_idx.release(); e->d_C4.release(); e->d_C4H.release(); e->d_rowmask.release(); e->d_flag.release(); e->d_tiletab.release(); e->d_rare.release(); e->d_rare_n.release(); e->d_common.release(); e->d_keybits.release(); e->d_lut.release(); e->d_vc.release();
     if (e->lane_stream) { (void)hipStreamSynchronize(e->lane_stream); (void)hipStreamDestroy(e->lane_stream); }
@@ -554,7 +554,25 @@ int fsk_detail::one_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t 
     return FSK_OK;
 }
 
+// fsk_set_center_weights: the profile is checked here; the next load weighs its windows with it
+int fsk_detail::one_set_center_weights(fsk_engine* e, const uint32_t* w, int32_t n) {
+    if (n < 0 || (n > 0 && !w)) return e->fail(FSK_EINVAL, "center weights: a null array or a negative length");
+    if (n > 4096) return e->fail(FSK_EINVAL, "center weights: %d entries, at most 4096", n);
+    for (int32_t i = 0; i < n; ++i)
+        if (w[i] > 255u) return e->fail(FSK_EINVAL, "center weights: entry %d is %u, at most 255", i, w[i]);
+    if (n > 0 && w[0] == 0u) return e->fail(FSK_EINVAL, "center weights: the first entry (the centre's weight) must be at least 1");
+    std::vector<uint8_t> p((size_t)n);
+    for (int32_t i = 0; i < n; ++i) p[(size_t)i] = (uint8_t)w[i];
+    e->cw_profile.swap(p);
+    return FSK_OK;
+}
+
 extern "C" {
+
+int fsk_set_center_weights(fsk_engine* e, const uint32_t* w, int32_t n) {
+    if (!e) return FSK_EINVAL;
+    return e->group ? group_set_center_weights(e, w, n) : one_set_center_weights(e, w, n);
+}
 
 int fsk_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n) {
     if (!e) return FSK_EINVAL;
@@ -634,12 +652,42 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     // wildcard mode: the windows free of wildcards, per sequence — their number (nvalid), one bit a window position
     // (vbits, sequence i from word vstart[i]; bits past the last position stay zero) —, found with the length of the
     // wildcard-free run that ends at every symbol: the window that ends there is valid when the run reaches g
-    bool wild_on = false;
+    //
+    // centre-weighted mode: window p of a sequence of nw windows lies d = |2 p - (nw - 1)| / 2 from its centre (2 p + g - len,
+    // halved downwards) and counts w[min(d, n - 1)] times. The distances the data reach are 0 .. (longest - g) / 2: `cw_on`
+    // when one of their weights is not 1 (else this load is the plain one, to the launch), and a weight of 0 among them
+    // clears windows in the validity bitmap as a wildcard does. nvalid, nfeat and most_valid are then SUMS OF WEIGHTS.
+    const std::vector<uint8_t>& cwp = e->cw_profile;
+    bool cw_on = false, cw_zero = false;
+    if (!cwp.empty() && longest >= g) {
+        const size_t reach = std::min<size_t>((size_t)((longest - g) / 2), cwp.size() - 1);
+        for (size_t d = 0; d <= reach; ++d) { cw_on = cw_on || cwp[d] != 1; cw_zero = cw_zero || cwp[d] == 0; }
+    }
+    auto cw_of = [&](int64_t p, int64_t nw) -> int64_t {
+        const int64_t t = 2 * p - (nw - 1);
+        return (int64_t)cwp[(size_t)std::min<int64_t>((t < 0 ? -t : t) / 2, (int64_t)cwp.size() - 1)];
+    };
+    bool wild_tok = false;  // some sequence really holds a wildcard
     std::vector<uint32_t> nvalid, vstart, vbits;
     int64_t most_valid = longest - g + 1;
     if (wild_set) {
         const int64_t total_tok = offsets[N] - off0;
-        for (int64_t i = 0; i < total_tok && !wild_on; ++i) wild_on = is_wild(tokens[i]);
+        for (int64_t i = 0; i < total_tok && !wild_tok; ++i) wild_tok = is_wild(tokens[i]);
+    }
+    const bool wild_on = wild_tok || cw_zero;
+    if (cw_on && !wild_on) {  // every window stays one: only the sums change
+        nvalid.resize((size_t)N);
+        nfeat = 0;
+        most_valid = 0;
+        for (int64_t i = 0; i < N; ++i) {
+            const int64_t nw = offsets[i + 1] - offsets[i] - g + 1;
+            int64_t nv = 0;
+            for (int64_t p = 0; p < nw; ++p) nv += cw_of(p, nw);
+            if (nv >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
+            nvalid[(size_t)i] = (uint32_t)nv;
+            nfeat += strands * nv;
+            most_valid = std::max(most_valid, nv);
+        }
     }
     if (wild_on) {
         nvalid.resize((size_t)N);
@@ -659,20 +707,26 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             uint32_t* vb = vbits.data() + vstart[(size_t)i];
             int64_t run = 0, nv = 0;
             for (int64_t p = 0; p < len; ++p) {
-                run = is_wild(sq[p]) ? 0 : run + 1;
+                run = wild_tok && is_wild(sq[p]) ? 0 : run + 1;
                 if (run >= g) {
                     const int64_t j = p - g + 1;
+                    const int64_t wgt = cw_on ? cw_of(j, len - g + 1) : 1;
+                    if (wgt == 0) continue;  // (a window of weight 0 is none)
                     vb[j >> 5] |= 1u << (j & 31);
-                    ++nv;
+                    nv += wgt;
                 }
             }
             if (nv == 0)
-                return e->fail(FSK_ESHORT, "sequence %lld has no window of length g = %d that is free of wildcards: it would have no features", (long long)i, g);
+                return e->fail(FSK_ESHORT, "sequence %lld has no window of length g = %d that is free of wildcards%s: it would have no features", (long long)i, g,
+                               cw_on ? " and has a center weight above 0" : "");
+            if (nv >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
             nvalid[(size_t)i] = (uint32_t)nv;
             nfeat += strands * nv;
             most_valid = std::max(most_valid, nv);
         }
     }
+    // (the weighted features are the sort records and the 32-bit feature offsets: the bound again, now that they are known)
+    if (nfeat >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
     tl_lengths = tl_ms(tl0);
     // ---- alphabet: rank-remap the tokens that occur (equality preserving; the reference's
     // dict_size = |{0} U tokens|, fastsk.cpp:70-85, only serves as its counting-sort radix), then pack,
@@ -694,7 +748,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             const int64_t len = offsets[i + 1] - offsets[i];
             len32[i] = (uint32_t)len;
             fstart[i] = fcount;
-            fcount += (uint32_t)(strands * (wild_on ? (int64_t)nvalid[(size_t)i] : len - g + 1));
+            fcount += (uint32_t)(strands * (wild_on || cw_on ? (int64_t)nvalid[(size_t)i] : len - g + 1));
         }
         fstart[N] = fcount;
     }
@@ -715,7 +769,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             if (!rc_comp_of(distinct[q], &c)) {
                 int32_t first = distinct[q];
                 for (int64_t i = 0; i < total; ++i)
-                    if (!rc_comp_of(tokens[i], &c) && !(wild_on && is_wild(tokens[i]))) { first = tokens[i]; break; }
+                    if (!rc_comp_of(tokens[i], &c) && !(wild_tok && is_wild(tokens[i]))) { first = tokens[i]; break; }
                 return e->fail(FSK_EINVAL, "token %d occurs in the sequences but not in the complement map", first);
             }
             distinct.push_back(c);
@@ -798,7 +852,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
                 for (int v = 0; v < 256; ++v) {
                     cnt[v] = 0;
                     for (int t = 0; t < nt; ++t) cnt[v] += hist[(size_t)t][(size_t)v];
-                    if (cnt[v] && !(wild_on && wild_small[v])) distinct.push_back(v);
+                    if (cnt[v] && !(wild_tok && wild_small[v])) distinct.push_back(v);
                 }
                 rc_mid = rc_close();
                 if (rc_mid) return;
@@ -860,7 +914,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             std::sort(distinct.begin(), distinct.end());
             distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
         }
-        if (wild_on) distinct.erase(std::remove_if(distinct.begin(), distinct.end(), is_wild), distinct.end());
+        if (wild_tok) distinct.erase(std::remove_if(distinct.begin(), distinct.end(), is_wild), distinct.end());
         { const int rc_cl = rc_close(); if (rc_cl) return rc_cl; }
         if (distinct.size() > sym_freq.size()) sym_freq.assign(distinct.size(), 0);
         wstart_v.resize((size_t)N);
@@ -879,7 +933,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
             const int32_t* sq = tokens + (offsets[i] - off0);
             uint32_t* w = words_v.data() + wstart_v[i];
             for (uint32_t p = 0; p < len32[i]; ++p) {
-                if (wild_on && is_wild(sq[p])) continue;  // (rank 0 in the words, counted nowhere)
+                if (wild_tok && is_wild(sq[p])) continue;  // (rank 0 in the words, counted nowhere)
                 uint32_t r = direct ? lut[(size_t)(sq[p] - base)]
                                     : (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), sq[p]) - distinct.begin());
                 const uint32_t bitpos = p * (uint32_t)bits;
@@ -905,7 +959,7 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         sym_freq.swap(both);
     }
     int64_t total_sym = strands * total;  // symbols counted, both strands
-    if (wild_on) {
+    if (wild_tok) {
         total_sym = 0;
         for (size_t r = 0; r < distinct.size() && r < sym_freq.size(); ++r) total_sym += sym_freq[r];
     }
@@ -922,6 +976,9 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     e->maxW = (uint32_t)strands * (uint32_t)most_valid;
     e->revcomp = rc_on;
     e->wild = wild_on;
+    e->cw = cw_on;
+    e->cw_n = cw_on ? (uint32_t)cwp.size() : 0u;
+    e->fwin_on = wild_on || cw_on;
     e->n_panels = (uint32_t)((N + fsk::PANEL - 1) / fsk::PANEL);
     e->h_len = len32; e->h_fstart = fstart; e->featseq_ready = false;
     e->prep_valid = false; e->vc_sum = 0; e->vc_n = 0;
@@ -978,6 +1035,8 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         if (rc_on) e->compact_rare = false;
         // (wildcard mode likewise: the windows around a rare symbol's place may hold a wildcard, which the marking pass knows)
         if (wild_on) e->compact_rare = false;
+        // (centre-weighted mode likewise: the marking pass, whose keys are the counted ones)
+        if (cw_on) e->compact_rare = false;
         e->rare_places = (uint32_t)places;
     }
     FSK_HIP(e->d_words.reserve(n_words_alloc));
@@ -988,28 +1047,38 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         FSK_HIP(e->d_comp.reserve(comp_rank.size()));
         FSK_HIP(hipMemcpy(e->d_comp.p, comp_rank.data(), comp_rank.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
-    if (wild_on) {
+    if (wild_on || cw_on) {
         // the window of every feature, for the sparse dataflow: a sequence's valid forward windows in order, then (second
         // strand) window j' of rc(x), valid exactly when forward window (len - g) - j' is, as len - g + 1 + j'
+        // (centre-weighted mode: a window is listed as often as it weighs — w(j') = w(forward twin) — and so becomes that
+        // many equal sort records: the run length of the segment stage is the weighted multiplicity)
         std::vector<uint32_t> fwin((size_t)nfeat);
         for (int64_t i = 0; i < N; ++i) {
             const uint32_t nw = len32[(size_t)i] - (uint32_t)g + 1u;
-            const uint32_t* vb = vbits.data() + vstart[(size_t)i];
+            const uint32_t* vb = wild_on ? vbits.data() + vstart[(size_t)i] : nullptr;
             uint32_t* out = fwin.data() + fstart[(size_t)i];
             for (uint32_t j = 0; j < nw; ++j)
-                if ((vb[j >> 5] >> (j & 31u)) & 1u) *out++ = j;
+                if (!vb || ((vb[j >> 5] >> (j & 31u)) & 1u))
+                    for (int64_t c = cw_on ? cw_of(j, nw) : 1; c > 0; --c) *out++ = j;
             if (rc_on)
                 for (uint32_t j = 0; j < nw; ++j) {
                     const uint32_t f = nw - 1u - j;
-                    if ((vb[f >> 5] >> (f & 31u)) & 1u) *out++ = nw + j;
+                    if (!vb || ((vb[f >> 5] >> (f & 31u)) & 1u))
+                        for (int64_t c = cw_on ? cw_of(f, nw) : 1; c > 0; --c) *out++ = nw + j;
                 }
         }
+        FSK_HIP(e->d_fwin.reserve(std::max<size_t>(1, fwin.size())));
+        FSK_HIP(hipMemcpy(e->d_fwin.p, fwin.data(), fwin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (cw_on) {
+        FSK_HIP(e->d_cw.reserve(cwp.size()));
+        FSK_HIP(hipMemcpy(e->d_cw.p, cwp.data(), cwp.size(), hipMemcpyHostToDevice));
+    }
+    if (wild_on) {
         FSK_HIP(e->d_vbits.reserve(vbits.size()));
         FSK_HIP(e->d_vstart.reserve(vstart.size()));
-        FSK_HIP(e->d_fwin.reserve(std::max<size_t>(1, fwin.size())));
         FSK_HIP(hipMemcpy(e->d_vbits.p, vbits.data(), vbits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         FSK_HIP(hipMemcpy(e->d_vstart.p, vstart.data(), vstart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        FSK_HIP(hipMemcpy(e->d_fwin.p, fwin.data(), fwin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (staged) {  // everything sits in pinned memory: four copies on the stream, nothing to wait for
         FSK_HIP(hipMemcpyAsync(e->d_words.p, p_words, n_words_alloc * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
@@ -1733,6 +1802,7 @@ int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offset
         lv->rc_tokens = e->rc_tokens;
         lv->rc_comps = e->rc_comps;
         lv->wild_tokens = e->wild_tokens;
+        lv->cw_profile = e->cw_profile;
         rc = fsk_bind_counts(lv, e->mm_scratch.p, e->pairs);
         if (!rc) rc = one_load_sequences(lv, tokens, offsets, n_train, n_test);  // (zeroes the bound triangle, or owes the zeros to the first tile launch)
         if (!rc) {

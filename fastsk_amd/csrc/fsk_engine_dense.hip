@@ -31,6 +31,15 @@ DensePlan dense_plan(uint32_t maxW, int g, uint32_t Vq, size_t extra) {
     return p;
 }
 
+size_t dense_mode_lds(const fsk_engine* e) {
+    // (wildcard mode: the staged windows' validity, one bit each, a set per strand that may be resident, and the round-up
+    // to a dword boundary: at most 1024 windows are staged at a time)
+    size_t extra = e->wild ? (size_t)(e->revcomp ? 2 : 1) * ((std::min(e->maxW1, 1024u) + 31u) / 32u) * fsk::PANEL * sizeof(uint32_t) + 4 : 0;
+    // (centre-weighted mode: the profile, one byte a distance, in front of them)
+    if (e->cw) extra += (((size_t)e->cw_n + 3) & ~(size_t)3) + (e->wild ? 0 : 4);
+    return extra;
+}
+
 namespace {
 
 // XCD-aware tile order for the tile rows [t0, t1) of the lower-triangular tile grid: 8x8
@@ -126,10 +135,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     // a cell, counts both)
     const uint32_t maxW1 = e->maxW1;
     size_t extra = compact ? (size_t)Vkeys * 2 : 0;
-    // (wildcard mode: the staged windows' validity, one bit each, a set per strand that may be resident, and the round-up
-    // to a dword boundary: at most 1024 windows are staged at a time)
-    const size_t wild_lds = e->wild ? (size_t)(e->revcomp ? 2 : 1) * ((std::min(maxW1, 1024u) + 31u) / 32u) * fsk::PANEL * sizeof(uint32_t) + 4 : 0;
-    extra += wild_lds;
+    extra += dense_mode_lds(e);
     DensePlan plan = dense_plan(maxW1, e->cfg.g, e->Vq, extra);  // may be re-planned below
     if (plan.CH == 0) return e->fail(FSK_EUNSUPPORTED, "dense path: LDS plan does not fit");
     // ... and when a strand is staged in one pass, the second strand gets a staging buffer of its own behind the table, so
@@ -171,6 +177,17 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
         k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true, true> : fsk::k_dense_count<false, true, false, true>;
         k_mark = e->revcomp ? fsk::k_dense_count<true, false, true, true> : fsk::k_dense_count<true, false, false, true>;
     }
+    if (e->cw) {  // (the marking pass needs no weights)
+        if (e->wild) {
+            k_count = e->revcomp ? fsk::k_dense_count<false, false, true, true, true> : fsk::k_dense_count<false, false, false, true, true>;
+            k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true, true, true> : fsk::k_dense_count<false, true, false, true, true>;
+        } else {
+            k_count = e->revcomp ? fsk::k_dense_count<false, false, true, false, true> : fsk::k_dense_count<false, false, false, false, true>;
+            k_count_lut = e->revcomp ? fsk::k_dense_count<false, true, true, false, true> : fsk::k_dense_count<false, true, false, false, true>;
+        }
+    }
+    const uint8_t* const wprof = e->cw ? (const uint8_t*)e->d_cw.p : (const uint8_t*)nullptr;
+    const uint32_t wn = e->cw ? e->cw_n : 0u;
     const uint32_t* const vbits = e->wild ? (const uint32_t*)e->d_vbits.p : (const uint32_t*)nullptr;
     const uint32_t* const vstart = e->wild ? (const uint32_t*)e->d_vstart.p : (const uint32_t*)nullptr;
     const uint16_t* const comp = e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr;
@@ -185,7 +202,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     // Shift classes (fsk_engine_dense_shift.hip): one weighted Gram product per chain of combinations that differ by a shift of
     // all kept positions, the other members by edge lookups. Checked per call; any other call runs as it always did. The
     // 16384 tiles of the default are a condition, not a tuned number: from there a tile has one workgroup anyway.
-    const bool use_shift = e->tune.dense_shift >= 0 && chunk == n && n >= 2 && !compact && !e->revcomp && !e->wild &&
+    const bool use_shift = e->tune.dense_shift >= 0 && chunk == n && n >= 2 && !compact && !e->revcomp && !e->wild && !e->cw &&
                            !(e->mm_on() && !e->mm_plain) && Vq8 <= 32 && first_test_tile == 0xffffffffu && !e->cfg.skip_test_block &&
                            ((e->tune.tile_splits == 0 && n_tiles >= 16384) || (e->tune.tile_splits == 1 && e->tune.dense_shift > 0)) &&
                            dense_shift_plan(e, combos, n, by_overflow);
@@ -253,12 +270,12 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                     FSK_HIP(hipMemsetAsync(e->d_keybits.p, 0, (size_t)nb * Vw * sizeof(uint32_t), e->stream));
                     FSK_LAUNCH(k_mark, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                                e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows, comp, rc_rows, vbits, vstart);
+                               e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, e->d_keybits.p, kc_rows, comp, rc_rows, vbits, vstart, wprof, wn);
                 }
                 FSK_LAUNCH(fsk::k_dense_keylut, dim3(nb), dim3(256), 0, e->stream, e->d_keybits.p, Vkeys, e->d_lut.p, e->d_vc.p);
                 FSK_LAUNCH(k_count_lut, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                            e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart);
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, e->d_lut.p, e->d_vc.p, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart, wprof, wn);
                 h_vc.resize((size_t)nb);
                 FSK_HIP(hipMemcpyAsync(h_vc.data(), e->d_vc.p, (size_t)nb * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
                 FSK_HIP(hipStreamSynchronize(e->stream));
@@ -273,7 +290,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             } else {
                 FSK_LAUNCH(k_count, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
                            e->k, e->sigma, e->Vq, plan.Vcq, maxW1, CH, chunk_pos, nb, slots_per_chunk, e->d_C4.p, e->d_C4H.p,
-                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart);
+                           e->d_rowmask.p, nst, e->d_flag.p, Vkeys, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint32_t*)nullptr, kc_rows, comp, rc_rows, vbits, vstart, wprof, wn);
             }
             e->toc(&e->st.ms_count);
             e->st.count_launches += 1;

@@ -235,6 +235,15 @@ struct fsk_engine {
     std::vector<int32_t> wild_tokens;
     bool wild = false;
     DevBuf<uint32_t> d_vbits, d_vstart, d_fwin;
+    // centre-weighted mode (fsk_set_center_weights): the profile as set (empty: off); what the LOADED sequences carry — cw
+    // (some window of theirs has a weight other than 1; else the load is the plain one), the profile as bytes on the device
+    // (the dense count kernel adds a window's weight where it added 1). A window of weight 0 is no window: it is cleared in
+    // the validity bitmap, so `wild` is on whenever a wildcard or a zero weight occurs. nfeat, fstart and maxW are sums of
+    // weights; fwin lists window p w(p) times (the sparse dataflow: repeated records), `fwin_on` = wild || cw says it exists.
+    std::vector<uint8_t> cw_profile;
+    bool cw = false, fwin_on = false;
+    uint32_t cw_n = 0;  // entries of the profile the loaded sequences were weighed with (d_cw): a later set does not touch it
+    DevBuf<uint8_t> d_cw;
 
     // mismatch-weighted mode (fsk_set_mismatch_weights): the weights c_0..c_m as set (empty: off), the level coefficients
     // a_0..a_d solved from them, and whether they are today's kernel (a = e_m: nothing of the mode runs). mm_scratch holds
@@ -474,6 +483,9 @@ void libstdcxx_shuffle_order(uint64_t seed, int64_t n, int32_t* out);
 // fsk_engine_dense.hip
 struct DensePlan { uint32_t CH = 0, Vcq = 0; size_t lds = 0; };
 DensePlan dense_plan(uint32_t maxW, int g, uint32_t Vq, size_t extra = 0);
+// the LDS the count kernel takes beside symbols, histogram and table for the modes of the loaded sequences: the validity
+// words of wildcard mode, the profile of centre-weighted mode (the `extra` of the plan, in choose_path and accumulate_dense alike)
+size_t dense_mode_lds(const fsk_engine* e);
 int fetch_pending_u(fsk_engine* e);
 int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_t row0, int64_t row1);
 // fsk_engine_dense_small.hip: the split tile launch at small N through 32-bit staging blocks
@@ -510,6 +522,7 @@ int one_finalize(fsk_engine* e);
 int one_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
 int one_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 int one_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
+int one_set_center_weights(fsk_engine* e, const uint32_t* w, int32_t n);
 int one_get_stats(fsk_engine* e, fsk_stats* out);
 void one_destroy(fsk_engine* e);
 // the combos the approx modes accumulate as plain integer sums (skip_variance): fastsk_kernel.cpp:148,275
@@ -531,6 +544,7 @@ int group_set_combo_order(fsk_engine* e, const int32_t* order, int32_t n);
 int group_set_seed(fsk_engine* e, uint64_t seed);
 int group_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* complements, int32_t n);
 int group_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
+int group_set_center_weights(fsk_engine* e, const uint32_t* w, int32_t n);
 int group_get_stats(fsk_engine* e, fsk_stats* out);
 int group_set_skip_test_block(fsk_engine* e, int32_t skip);
 int group_set_tuning(fsk_engine* e, const char* key, int64_t value, std::string& err);

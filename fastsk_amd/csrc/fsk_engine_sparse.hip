@@ -423,11 +423,11 @@ int sx_extract(const SxBatch& c) {
         }, ww == 2, small, four);
     } else {
         auto k = e->revcomp ? fsk::k_sx_extract<RecT, true> : fsk::k_sx_extract<RecT, false>;
-        if (e->wild) k = e->revcomp ? fsk::k_sx_extract<RecT, true, true> : fsk::k_sx_extract<RecT, false, true>;
+        if (e->fwin_on) k = e->revcomp ? fsk::k_sx_extract<RecT, true, true> : fsk::k_sx_extract<RecT, false, true>;
         FSK_LAUNCH(k, dim3(tps, nb), dim3(256), 0, c.stream, e->view(), (const uint32_t*)e->d_featseq.p,
                    (const uint32_t*)e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S.d_blockhist.p, dmask, c.ids, zeroed_stats,
                    c.by_id ? 1 : 0, e->sx_symbits, e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr, e->cfg.g,
-                   e->wild ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
+                   e->fwin_on ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
     }
     e->toc(&e->st.ms_extract, c.stream);
     e->st.launches += 1;
@@ -868,12 +868,12 @@ int ensure_featseq(fsk_engine* e) {
         // (reverse-complement mode: the second half of a sequence's windows are its other strand's)
         auto k = e->win_words == 2 ? (e->revcomp ? fsk::k_sx_windows<2, true> : fsk::k_sx_windows<2, false>)
                                    : (e->revcomp ? fsk::k_sx_windows<4, true> : fsk::k_sx_windows<4, false>);
-        if (e->wild)  // (the window of a feature from the load's map)
+        if (e->fwin_on)  // (the window of a feature from the load's map: wildcards, centre weights)
             k = e->win_words == 2 ? (e->revcomp ? fsk::k_sx_windows<2, true, true> : fsk::k_sx_windows<2, false, true>)
                                   : (e->revcomp ? fsk::k_sx_windows<4, true, true> : fsk::k_sx_windows<4, false, true>);
         FSK_LAUNCH(k, grid, dim3(256), 0, e->stream, e->view(), (const uint32_t*)e->d_featseq.p, (const uint32_t*)e->d_fstart.p,
                    (uint32_t)e->nfeat, e->cfg.g, e->d_win.p, e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr,
-                   e->wild ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
+                   e->fwin_on ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
     }
     FSK_HIP(hipStreamSynchronize(e->stream));  // (every lane's kernels read both arrays)
     e->featseq_ready = true;

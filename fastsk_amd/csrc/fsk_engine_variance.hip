@@ -35,6 +35,10 @@ int enqueue_sequential_sum(fsk_engine* e, const double* d_vals, u64 n, double* b
 // variance mode: T sequential Welford chains (fastsk_kernel.cpp:188-262, 286-315)
 // chains tid = chain_first, chain_first + chain_step, ... < T (all of them: 0, 1); stdevs are chain 0's
 int run_variance_mode(fsk_engine* e, int T, int chain_first, int chain_step) {
+    // (centre-weighted mode: the per-combination triangles of this mode are 32-bit, and weights let one cell of one
+    // combination pass them)
+    if (e->cw && (u64)e->maxW * (u64)e->maxW > 0xffffffffull)
+        return e->fail(FSK_EUNSUPPORTED, "center weights: variance mode keeps 32-bit cells per combination and needs max_windows^2 <= 2^32 - 1 (max_windows = %u); use skip_variance", e->maxW);
     { int rcz = materialise_zero(e); if (rcz) return rcz; }
     // (a previous call may have left the sequential sums of a batch beyond its stop running: see the end of this function)
     if (e->chain_stream) FSK_HIP(hipStreamSynchronize(e->chain_stream));

@@ -39,11 +39,23 @@ __device__ __forceinline__ uint32_t reverse_bits32(uint32_t x) {  // (the compil
     x = ((x >> 8) & 0x00ff00ffu) | ((x & 0x00ff00ffu) << 8);
     return (x >> 16) | (x << 16);
 }
-template <int K, bool MARK, bool LUT, bool WILD>
+// WGT (centre-weighted mode): window j of a sequence of nwin windows lies d = |2 j - (nwin - 1)| / 2 from the sequence's
+// centre (|2 j + g - len|, halved downwards; the same for window j of the second strand, whose forward twin is
+// nwin - 1 - j) and adds wl[min(d, wn1)] to its key's counter where it added 1; `wl` is the profile in LDS, one byte a
+// distance, wn1 its last index. j is the ABSOLUTE window index, so a chunk of a re-staged sequence weighs as the whole does.
+template <bool WGT>
+__device__ __forceinline__ uint32_t window_weight(const uint8_t* wl, uint32_t wn1, uint32_t j, uint32_t nwin) {
+    if (!WGT) return 1u;
+    const int32_t t = (int32_t)(2u * j) - (int32_t)nwin + 1;
+    uint32_t d = (uint32_t)(t < 0 ? -t : t) >> 1;
+    d = d < wn1 ? d : wn1;
+    return FSK_LDS_LOAD_U8(wl + d);
+}
+template <int K, bool MARK, bool LUT, bool WILD, bool WGT>
 __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* hist, const uint16_t* lut, const uint32_t (&pr)[16],
                                               int k, uint32_t sigma, uint32_t j0, uint32_t hi, uint32_t cb, uint32_t nwin,
                                               uint32_t r, uint32_t half, uint32_t key_lo, uint32_t key_n, uint16_t* kcache,
-                                              int kmode, const uint32_t* vl) {
+                                              int kmode, const uint32_t* vl, const uint8_t* wl, uint32_t wn1) {
     if (K > 0 && kmode == 0) {
         // The common case (every BASELINE config; with key compaction both of its passes — MARK sets the key's bit, LUT
         // counts the key's rank — unless a window-key cache is in use): WPT windows per trip. Window j+4 of a lane lies
@@ -79,7 +91,7 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
                 // (the table sits in LDS; a padding row's key is 0, inside it)
                 const uint32_t key = (LUT ? (uint32_t)FSK_LDS_LOAD_U16(lut + kk[u]) : kk[u]) - key_lo;  // wraps for keys below the sweep: rejected by the compare
                 if (j + 4u * u < nwin && key < key_n && (!WILD || window_valid(vl, j + 4u * u - cb, r)))
-                    atomicAdd(&hist[key * 32u + (r >> 1)], 1u << half);
+                    atomicAdd(&hist[key * 32u + (r >> 1)], window_weight<WGT>(wl, wn1, j + 4u * u, nwin) << half);
             }
         }
         for (; j < hi; j += 4u) {  // the last few windows of the chunk
@@ -95,7 +107,8 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
             }
             if (LUT) k0 = (uint32_t)FSK_LDS_LOAD_U16(lut + k0);
             k0 -= key_lo;
-            if (j < nwin && k0 < key_n && (!WILD || window_valid(vl, j - cb, r))) atomicAdd(&hist[k0 * 32u + (r >> 1)], 1u << half);
+            if (j < nwin && k0 < key_n && (!WILD || window_valid(vl, j - cb, r)))
+                atomicAdd(&hist[k0 * 32u + (r >> 1)], window_weight<WGT>(wl, wn1, j, nwin) << half);
         }
         return;
     }
@@ -105,7 +118,7 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
             if (!MARK && kmode == 2) {  // workgroup-uniform
                 key = kcache[j * PANEL + r];
                 key -= key_lo;
-                if (key < key_n) atomicAdd(&hist[key * 32u + (r >> 1)], 1u << half);
+                if (key < key_n) atomicAdd(&hist[key * 32u + (r >> 1)], window_weight<WGT>(wl, wn1, j, nwin) << half);
                 continue;
             }
             if (K > 0) {
@@ -122,27 +135,27 @@ __device__ __forceinline__ void count_windows(const uint8_t* symT, uint32_t* his
                 if (LUT) key = lut[key];
                 if (kmode == 1) kcache[j * PANEL + r] = (uint16_t)key;
                 key -= key_lo;  // wraps for keys below the sweep: rejected by the compare
-                if (key < key_n) atomicAdd(&hist[key * 32u + (r >> 1)], 1u << half);
+                if (key < key_n) atomicAdd(&hist[key * 32u + (r >> 1)], window_weight<WGT>(wl, wn1, j, nwin) << half);
             }
         }
     }
 }
 
-template <bool MARK, bool LUT, bool WILD>
+template <bool MARK, bool LUT, bool WILD, bool WGT>
 __device__ __forceinline__ void count_windows_k(const uint8_t* symT, uint32_t* hist, const uint16_t* lut, const uint32_t (&pr)[16],
                                                 int k, uint32_t sigma, uint32_t j0, uint32_t hi, uint32_t cb, uint32_t nwin,
                                                 uint32_t r, uint32_t half, uint32_t key_lo, uint32_t key_n, uint16_t* kcache,
-                                                int kmode, const uint32_t* vl) {
+                                                int kmode, const uint32_t* vl, const uint8_t* wl, uint32_t wn1) {
     switch (k) {  // workgroup-uniform
-        case 1: count_windows<1, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 2: count_windows<2, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 3: count_windows<3, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 4: count_windows<4, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 5: count_windows<5, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 6: count_windows<6, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 7: count_windows<7, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        case 8: count_windows<8, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
-        default: count_windows<0, MARK, LUT, WILD>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl); break;
+        case 1: count_windows<1, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 2: count_windows<2, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 3: count_windows<3, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 4: count_windows<4, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 5: count_windows<5, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 6: count_windows<6, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 7: count_windows<7, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        case 8: count_windows<8, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
+        default: count_windows<0, MARK, LUT, WILD, WGT>(symT, hist, lut, pr, k, sigma, j0, hi, cb, nwin, r, half, key_lo, key_n, kcache, kmode, vl, wl, wn1); break;
     }
 }
 
@@ -184,14 +197,20 @@ __device__ __forceinline__ void pack_count_row(const uint16_t* hist16, uint32_t 
 // both strands are resident). Window j' of the second strand is valid exactly when forward window (len - g) - j' is: its
 // words are the forward ones read backwards. A window of one chunk whose wildcard lies in the overlap rows of the next
 // is invalid in the bitmap like any other.
-template <bool MARK, bool LUT, bool RC, bool WILD = false>
+//
+// WGT (centre-weighted mode, never with MARK): a window adds its weight (window_weight) instead of 1. The profile, wn bytes
+// at wprof, is copied into LDS once per workgroup, in front of the validity words. A lane's counter holds at most the
+// sequence's sum of weights, below 65,536 by the host's test for this path, so the 16-bit halves cannot carry; a count above
+// 15 goes to the hi plane and one above 255 raises the overflow flag exactly as unit counts do.
+template <bool MARK, bool LUT, bool RC, bool WILD = false, bool WGT = false>
 __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, uint32_t sigma, uint32_t Vq,
                                                      uint32_t Vcq, uint32_t max_win, uint32_t CH, const uint8_t* combo_pos,
                                                      int n_slots, int slots_per_chunk, uint32_t* C4, uint32_t* C4H,
                                                      uint32_t* rowmask, uint32_t nst, uint32_t* overflow_flag, uint32_t V,
                                                      const uint16_t* lut_g, const uint16_t* vc, uint32_t* keybits,
                                                      uint32_t kc_rows, const uint16_t* comp, uint32_t rc_rows,
-                                                     const uint32_t* vbits, const uint32_t* vstart) {
+                                                     const uint32_t* vbits, const uint32_t* vstart, const uint8_t* wprof,
+                                                     uint32_t wn) {
     // Counts leave as two 4-bit planes, count = lo + 16 * hi (8 keys per dword): C4 holds lo and
     // is all the tile kernel multiplies for almost every key; C4H holds hi, zero unless a k-mer
     // occurs more than 15 times in one sequence (poly-A, runs of 'n'); rowmask[panel][slot][..]
@@ -212,10 +231,10 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
     uint16_t* kcache = lut + (LUT ? V : 0u);
     uint8_t* symT2 = RC && rc_rows != 0u ? reinterpret_cast<uint8_t*>(kcache) : symT;  // (RC: the place of the cache is the second strand's)
     constexpr int STRANDS = RC ? 2 : 1;
-    // (WILD) validity words: behind the cache / the second strand's symbols, on a dword boundary
+    // (WGT) the profile's bytes, then (WILD) validity words: behind the cache / the second strand's symbols, on a dword boundary
     const uint32_t vwords = (CH + 31u) >> 5;
-    uint32_t* const vld = reinterpret_cast<uint32_t*>(
-        smem + (((size_t)sym_rows * PANEL + (size_t)Vcq * 512 + (LUT ? (size_t)V * 2 : 0) + (RC ? (size_t)rc_rows * PANEL : (size_t)kc_rows * PANEL * 2) + 3) & ~(size_t)3));
+    uint8_t* const wl = smem + (((size_t)sym_rows * PANEL + (size_t)Vcq * 512 + (LUT ? (size_t)V * 2 : 0) + (RC ? (size_t)rc_rows * PANEL : (size_t)kc_rows * PANEL * 2) + 3) & ~(size_t)3);
+    uint32_t* const vld = reinterpret_cast<uint32_t*>(wl + (WGT ? ((size_t)wn + 3) & ~(size_t)3 : 0));
     uint32_t* const vld2 = RC && rc_rows != 0u ? vld + (size_t)vwords * PANEL : vld;
     const int tid = threadIdx.x, r = tid & 63, w = tid >> 6;
     const uint32_t panel = blockIdx.x;
@@ -232,6 +251,8 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
     const uint32_t Vq8 = (Vq + 1u) >> 1;
     const uint32_t Vw = (V + 31u) >> 5;  // words of the key bitmap
     uint32_t seen = 0;  // OR of every count read out: a bit above bit 7 means some count exceeded 255
+    if (WGT)  // (read after the barrier that follows the first staging)
+        for (uint32_t i = (uint32_t)tid; i < wn; i += 256u) wl[i] = wprof[i];
     for (int slot = slot0; slot < slot1; ++slot) {
         if (!MARK) {
             __syncthreads();  // previous combo's mask written out
@@ -282,8 +303,8 @@ __global__ __launch_bounds__(256) void k_dense_count(SeqView S, int g, int k, ui
                     __syncthreads();  // symbols staged, histogram zeroed, table loaded
                     const uint32_t hi = cb + CH < max_win ? cb + CH : max_win;
                     const int kmode = (MARK || kc_rows == 0u) ? 0 : (kc0 == 0u ? 1 : 2);
-                    count_windows_k<MARK, LUT, WILD>(sy, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half, key_lo, key_n,
-                                                     kcache, kmode, vl);
+                    count_windows_k<MARK, LUT, WILD, WGT && !MARK>(sy, hist, lut, pr, k, sigma, cb + (uint32_t)w, hi, cb, nwin, (uint32_t)r, half,
+                                                                   key_lo, key_n, kcache, kmode, vl, wl, wn - 1u);
                 }
             }
             __syncthreads();

@@ -782,6 +782,17 @@ int group_set_wildcards(fsk_engine* lead, const int32_t* tokens, int32_t n) {
     return FSK_OK;
 }
 
+int group_set_center_weights(fsk_engine* lead, const uint32_t* w, int32_t n) {
+    for (fsk_engine* e : lead->group->member) {
+        const int rc = one_set_center_weights(e, w, n);
+        if (rc) {
+            if (e != lead) lead->err = e->err;
+            return rc;
+        }
+    }
+    return FSK_OK;
+}
+
 int group_set_skip_test_block(fsk_engine* lead, int32_t skip) {
     for (fsk_engine* e : lead->group->member) {
         e->cfg.skip_test_block = skip ? 1 : 0;

@@ -256,7 +256,7 @@ def accumulate_and_reduce(eng, K, combos, group=None, n_bands=None, narrow=None,
 
 def compute_sharded(tokens, offsets, n_train, n_test, g, m, combos=None, group=None, device=None, lib=None,
                     path=_native.PATH_AUTO, profile=False, n_bands=None, narrow=None, shard_by="combos",
-                    replicate=True, revcomp=None, wildcards=None):
+                    replicate=True, revcomp=None, wildcards=None, center_weights=None):
     """Exact (or explicit-combo-list) kernel over the ranks of ``group``.
 
     Returns ``(engine, K)``: the finalized engine of this rank (use ``get_block`` / ``get_train`` /
@@ -279,7 +279,8 @@ def compute_sharded(tokens, offsets, n_train, n_test, g, m, combos=None, group=N
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     eng = _native.Engine(g, m, device=(device.index or 0) if device.type == "cuda" else 0, path=path,
-                         profile=profile, lib=lib, revcomp=revcomp, wildcards=wildcards)
+                         profile=profile, lib=lib, revcomp=revcomp, wildcards=wildcards,
+                         center_weights=center_weights)
     ncomb = eng.lib.num_combos(g, m)
     if combos is None:
         combos = np.arange(ncomb, dtype=np.int32)
@@ -304,7 +305,8 @@ def compute_sharded(tokens, offsets, n_train, n_test, g, m, combos=None, group=N
 
 
 def compute_variance_sharded(tokens, offsets, n_train, n_test, g, m, t, delta=0.025, max_iters=-1, order=None, seed=None,
-                             group=None, device=None, lib=None, path=_native.PATH_AUTO, revcomp=None, wildcards=None):
+                             group=None, device=None, lib=None, path=_native.PATH_AUTO, revcomp=None, wildcards=None,
+                             center_weights=None):
     """Variance (convergence) mode over the ranks of ``group``: the ``t`` Welford chains of the
     reference's worker threads (``fastsk_kernel.cpp:188-281``) are the units — chain c runs on rank
     ``c mod R`` — and their K_hat are summed in fp64 with ONE all-reduce (``fastsk_kernel.cpp:286-315``
@@ -324,7 +326,8 @@ def compute_variance_sharded(tokens, offsets, n_train, n_test, g, m, t, delta=0.
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     eng = _native.Engine(g, m, t=t, approx=True, delta=delta, max_iters=max_iters,
-                         device=(device.index or 0) if device.type == "cuda" else 0, path=path, lib=lib, revcomp=revcomp, wildcards=wildcards)
+                         device=(device.index or 0) if device.type == "cuda" else 0, path=path, lib=lib, revcomp=revcomp, wildcards=wildcards,
+                         center_weights=center_weights)
     if order is not None:
         eng.set_combo_order(order)
     elif seed is not None:

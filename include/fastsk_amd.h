@@ -34,7 +34,7 @@ extern "C" {
                                  two dozen FSK_* switches);
                               5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
                                  (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers;
-                                  fsk_set_wildcards) */
+                                  fsk_set_wildcards; fsk_set_center_weights) */
 
 enum {
     FSK_OK = 0,
@@ -139,7 +139,7 @@ typedef struct fsk_stats {
     uint64_t panel_bytes;    /* bytes of count panels written (= read at least once)            */
     double u4_tile_launches; /* launches of the 4-bit tile kernel (v_dot8_u32_u4)                */
     double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo
-                                (wildcards set: of the windows free of them) */
+                                (wildcards set: of the windows free of them; centre weights set: of the sum of the windows' weights) */
     double count_launches;   /* launches of the segment-count kernel (panel cache misses)        */
     double compact_keys_avg; /* key compaction on: mean keys per combo that really occur (else 0) */
     double batches_redone;   /* sparse: batches enqueued ahead of their word count that did not fit */
@@ -243,6 +243,25 @@ int fsk_set_complement(fsk_engine* e, const int32_t* tokens, const int32_t* comp
  * wildcard too, else FSK_EINVAL naming the token. fsk_stats: n_feat and max_windows count the valid windows (they bound a
  * cell), alphabet and key_space the real symbols only. A wildcard that does not occur in the data changes nothing. */
 int fsk_set_wildcards(fsk_engine* e, const int32_t* tokens, int32_t n);
+
+/* Centre-weighted kernels (the "wgkm" of LS-GKM, -t 4: a g-window counts more the closer it lies to the middle of its
+ * sequence, the summit of a ChIP-seq / ATAC peak). The PROFILE is w[0..n-1], 1 <= n <= 4096, 0 <= w[d] <= 255, w[0] >= 1.
+ * Window p (0 <= p <= L - g) of a sequence of length L lies d(p) = floor(|2p + g - L| / 2) from the sequence's centre and
+ * has the weight W(p) = w[min(d(p), n - 1)]: the last entry extends outwards. Per combination c,
+ *     K_c(x, y) = sum over windows p of x, q of y of W_x(p) W_y(q) [p and q agree at the kept positions of c],
+ * i.e. the features of x hold window p W(p) times; everything else is this header's algorithm on these counts (the sum
+ * over combinations, reverse complement — window p' of rc(x) is forward window L - g - p', at the same d —, wildcards — the
+ * weights apply to the valid windows —, the mismatch-weighted kernels, whose levels inherit the profile, both approx modes,
+ * normalisation). A window of weight 0 is not a window, as one that holds a wildcard is not; a sequence left without any
+ * fails the load with FSK_ESHORT naming its index (only possible together with wildcards). n = 0 switches the mode off (the
+ * default); a profile of ones, or one whose other entries no window of the data reaches, changes nothing, to the launch.
+ * Takes effect from the next fsk_load_sequences / fsk_compute; a group handle sets it on every engine. FSK_EINVAL on a null
+ * array, n < 0 or n > 4096, an entry above 255, w[0] == 0. fsk_stats: n_feat is the sum of all weights and max_windows the
+ * largest sum of one sequence (both strands in reverse-complement mode): they bound a cell as they always did; the weighted
+ * n_feat must stay below 2^31 (FSK_EUNSUPPORTED at load). The variance mode (approx without skip_variance) keeps 32-bit
+ * cells per combination: with the mode on and max_windows^2 > 2^32 - 1, fsk_compute returns FSK_EUNSUPPORTED and the
+ * engine stays usable. The sparse dataflow repeats a window's sort record W(p) times: its cost grows with the mean weight. */
+int fsk_set_center_weights(fsk_engine* e, const uint32_t* w, int32_t n);
 
 /* Mismatch-weighted kernels (the mismatch-truncated gapped k-mer kernel LS-GKM ships as "-l 11 -k 7 -d 3", the l-mer
  * filters of Ghandi et al., "pairs of l-mers within d mismatches"). With N_h(x, y) the number of pairs (one g-window of x,
