@@ -205,7 +205,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     const bool use_shift = e->tune.dense_shift >= 0 && chunk == n && n >= 2 && !compact && !e->revcomp && !e->wild && !e->cw &&
                            !(e->mm_on() && !e->mm_plain) && Vq8 <= 32 && first_test_tile == 0xffffffffu && !e->cfg.skip_test_block &&
                            ((e->tune.tile_splits == 0 && n_tiles >= 16384) || (e->tune.tile_splits == 1 && e->tune.dense_shift > 0)) &&
-                           dense_shift_plan(e, combos, n, by_overflow);
+                           dense_shift_plan(e, combos, n, by_overflow, e->tune.dense_shift_packed >= 0 ? SHIFT_PACKED_CHAIN : 0u);
     std::vector<uint16_t> h_vc;
     std::vector<uint8_t> pos;
     const uint8_t* chunk_pos = e->d_pos.p;  // the kept positions of the chunk at hand, on the device
@@ -214,7 +214,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
         // the count panels of an unchanged single-chunk combo list are reused by the FOLLOWING row
         // bands of one pass (row0 > 0); a call that starts at row 0 always recounts
         const bool cached = row0 > 0 && e->prep_valid && nb == n && (int)e->prep_combos.size() == n && e->prep_shift == use_shift &&
-                            std::equal(combos, combos + n, e->prep_combos.begin());
+                            (!use_shift || e->prep_chain == e->shift.max_chain) && std::equal(combos, combos + n, e->prep_combos.begin());
         if (!cached) {
             e->prep_valid = false;
             // the chunk's kept positions: a run of consecutive combo ids (every exact call: 0, 1, 2, ...) reads them from the
@@ -330,12 +330,15 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                 e->tic();
                 const int rck = dense_shift_edge_keys(e, chunk_pos, panels_pad);
                 if (rck) return rck;
+                const int rcm = dense_shift_keymajor(e, panels_pad, nb, Vq8);
+                if (rcm) return rcm;
                 e->toc(&e->st.ms_tile);
             }
             if (nb == n) {
                 e->prep_combos.assign(combos, combos + n);
                 e->prep_valid = true;
                 e->prep_shift = use_shift;
+                e->prep_chain = use_shift ? e->shift.max_chain : 0u;
             }
         }
         if (e->prep_overflow) {

@@ -11,7 +11,10 @@
 //                      when the pass may (every cell j <= i, zeros included), the later ones add their non-zero cells. (One
 //                      launch that flushes and clears at every group end keeps 64 sums, the flush's index arithmetic and the
 //                      pipeline's state live at once: 128 VGPRs and 92 bytes of scratch a lane from the compiler.)
-//   k_dense_shift_fix  the derived steps
+//   k_dense_keymajor   the count panels once more per counted list as key-major planes (a dword = one key of 8 sequences)
+//   k_dense_shift_packed  the derived steps from those planes, eight cells an LDS read (tuning dense_shift_packed)
+//   k_dense_shift_fix  the derived steps from the count panels themselves: dense_shift_packed = -1, and whenever the key-major
+//                      planes do not fit
 //
 // A translation unit of its own, like fsk_engine_dense_small.hip: nothing here can reach the register allocation of
 // k_dense_tile_dma / k_dense_tile_dma_compact.
@@ -38,14 +41,16 @@ namespace fsk_detail {
 
 // The plan of a combination list. Combinations are grouped by shape (kept positions minus the first), sorted by shift inside
 // a shape and cut into chains of consecutive shifts: a list with gaps, in any order or with a repeated id simply gives
-// shorter chains, a chain of one is a plain slot of weight 1. Returns whether the shift path can run the list: some chain has
-// a derived step, and the correction sums stay inside int32.
-bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow) {
+// shorter chains, a chain of one is a plain slot of weight 1. max_chain != 0 (the packed corrections: their prefix sums are
+// bytes) cuts a chain after that many members: a longer class becomes two chains, one more product. Returns whether the shift
+// path can run the list: some chain has a derived step, and the correction sums stay inside int32.
+bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow, uint32_t max_chain) {
     ShiftPlan& p = e->shift;
-    if (!(p.by_overflow == by_overflow && (int)p.combos.size() == n && std::equal(combos, combos + n, p.combos.begin()))) {
+    if (!(p.by_overflow == by_overflow && p.max_chain == max_chain && (int)p.combos.size() == n && std::equal(combos, combos + n, p.combos.begin()))) {
         p = ShiftPlan();
         p.combos.assign(combos, combos + n);
         p.by_overflow = by_overflow;
+        p.max_chain = max_chain;
         const int k = e->k;
         std::map<std::vector<uint8_t>, std::vector<std::pair<int, int>>> shapes;  // shape -> (shift, place in the list)
         for (int q = 0; q < n; ++q) {
@@ -59,7 +64,7 @@ bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overfl
             auto& v = kv.second;
             std::stable_sort(v.begin(), v.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
             for (size_t i = 0; i < v.size(); ++i) {
-                if (i == 0 || v[i].first != v[i - 1].first + 1) chains.emplace_back();
+                if (i == 0 || v[i].first != v[i - 1].first + 1 || (max_chain != 0u && chains.back().size() >= max_chain)) chains.emplace_back();
                 chains.back().push_back(v[i].second);
             }
         }
@@ -107,6 +112,50 @@ int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t pane
     return FSK_OK;
 }
 
+// The key-major planes of the list just counted, and the edge keys as offsets into them: what k_dense_shift_packed reads. They
+// stay with the panels (row bands reuse them). Leaves e->shift_packed false, and the corrections to k_dense_shift_fix, when the
+// tuning says so, the plan's chains are not cut to the packed kernel's eight steps, or the planes do not fit: never an error.
+// A call that wanted the packed kernel and did not get it says so under trace=1 (the slower kernel otherwise shows only as
+// three launches fewer in fsk_stats.launches). Memory is asked about only when the buffers have to grow; a growth may take half
+// of what is free then, because the results (the normalised triangle of fsk_finalize) are still to be allocated.
+int dense_shift_keymajor(fsk_engine* e, uint32_t panels_pad, int nb, uint32_t Vq8) {
+    const ShiftPlan& p = e->shift;
+    e->shift_packed = false;
+    if (e->tune.dense_shift_packed < 0 || p.max_chain != SHIFT_PACKED_CHAIN) return FSK_OK;
+    const size_t plane = (size_t)panels_pad * Vq8 * fsk::PANEL * (size_t)nb;  // dwords: as many as a plane of the panels
+    const size_t n_keys = (p.steps.size() / 2) * (size_t)panels_pad * fsk::PANEL;
+    const size_t want = (2 * plane + n_keys) * sizeof(uint32_t);
+    const char* why = nullptr;
+    if (e->tune.dense_shift_plane_kb > 0 && want > (size_t)e->tune.dense_shift_plane_kb * 1024) why = "over the dense_shift_plane_kb cap";
+    const size_t grow = (std::max(plane, e->d_KM.cap) - e->d_KM.cap + std::max(plane, e->d_KMH.cap) - e->d_KMH.cap +
+                         std::max(n_keys, e->d_edge_offs.cap) - e->d_edge_offs.cap) * sizeof(uint32_t);
+    if (!why && grow > 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        if (grow > free_b / 2) why = "more than half of the free device memory";
+        else if (e->d_KM.reserve(plane) != hipSuccess || e->d_KMH.reserve(plane) != hipSuccess || e->d_edge_offs.reserve(n_keys) != hipSuccess) {
+            (void)hipGetLastError();
+            e->d_KM.release(); e->d_KMH.release(); e->d_edge_offs.release();
+            why = "hipMalloc failed";
+        }
+    }
+    if (why) {
+        if (e->trace())
+            fprintf(stderr, "[fsk] dense shift classes: the key-major planes (%.1f MB) do not fit, %s: k_dense_shift_fix runs the corrections\n",
+                    (double)want / 1e6, why);
+        return FSK_OK;
+    }
+    const uint32_t n_pairs = panels_pad / 2u;
+    const uint32_t kgrid = (uint32_t)(((size_t)n_pairs * nb * Vq8 * 16u + 255u) / 256u);
+    FSK_LAUNCH(fsk::k_dense_keymajor, dim3(kgrid), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4.p, n_pairs, nb, Vq8, e->d_KM.p);
+    FSK_LAUNCH(fsk::k_dense_keymajor, dim3(kgrid), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4H.p, n_pairs, nb, Vq8, e->d_KMH.p);
+    FSK_LAUNCH(fsk::k_dense_edge_offs, dim3((uint32_t)((n_keys + 255u) / 256u)), dim3(256), 0, e->stream, (const uint16_t*)e->d_edge_keys.p, n_keys,
+               e->d_edge_offs.p);
+    e->st.launches += 3;
+    e->shift_packed = true;
+    return FSK_OK;
+}
+
 // the tile pass of accumulate_dense: the weighted base products, then the corrections
 int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t nst, u64* K, int store, uint32_t panels_pad) {
     const ShiftPlan& p = e->shift;
@@ -118,9 +167,15 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
                    slot0, p.groups[gi + 1]);
         slot0 = end;
     }
-    FSK_LAUNCH(fsk::k_dense_shift_fix, dim3((uint32_t)n_tiles), dim3(512), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
-               (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
-               (const uint16_t*)e->d_edge_keys.p, panels_pad * fsk::PANEL, nb, Vq8, (uint32_t)e->N, K);
+    if (e->shift_packed) {
+        FSK_LAUNCH(fsk::k_dense_shift_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
+                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
+                   (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, p.n_bases, (uint32_t)(32u * p.wsum), (uint32_t)e->N, K);
+    } else {
+        FSK_LAUNCH(fsk::k_dense_shift_fix, dim3((uint32_t)n_tiles), dim3(512), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
+                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
+                   (const uint16_t*)e->d_edge_keys.p, panels_pad * fsk::PANEL, nb, Vq8, (uint32_t)e->N, K);
+    }
     e->st.launches += (int32_t)(p.groups.size() / 2);  // (the groups and the corrections; the caller counts one)
     return FSK_OK;
 }

@@ -94,6 +94,8 @@ using fsk_detail::DevBuf;
     X(tile_splits, 0, 0, 4096, "dense: combo splits per tile (0: by the size of the launch)")                                        \
     X(dense_small, 0, 0, 1, "dense: 1 = a split tile launch (small N) leaves its sums as 32-bit staging blocks that k_dense_widen adds into K (0: one 64-bit atomic a cell and split — measured faster: the atomics drain under other workgroups' dot products)")                                        \
     X(dense_shift, 0, -1, 1, "dense: one weighted Gram product per chain of shifted combinations, the other members by edge lookups (fsk_engine_dense_shift.hip) — 1 = whenever the call is eligible, -1 = never (0: when eligible, tile_splits = 0 and the launch has 16384 tiles or more, the size from which a tile has one workgroup anyway)") \
+    X(dense_shift_packed, 0, -1, 0, "dense, shift classes: the derived steps from key-major planes, eight cells an LDS read (k_dense_keymajor, k_dense_shift_packed; chains cut at nine members) — 0 = whenever the shift path runs and the planes fit, -1 = never: k_dense_shift_fix on the count panels") \
+    X(dense_shift_plane_kb, 0, 0, (int64_t)1 << 40, "dense, shift classes: the key-major planes and offsets may take this many KiB at most (0: half of the free memory; tests: the planes do not fit)") \
     X(dense_chunk, 0, 0, 1 << 24, "dense: cap of the count kernel's staging chunk, in windows (0: none)")                             \
     X(variance_dense_slots, 1, 0, 1, "variance mode, dense: 0 = zero fill + k_welford per iteration instead of storing slot triangles") \
     X(var_slots16, 1, 0, 1, "variance mode, sparse: 0 = u32 slot triangles from the start")                                          \
@@ -181,6 +183,7 @@ struct ShiftPlan {
     std::vector<int32_t> order;    // slot -> place in the list
     std::vector<uint32_t> groups, steps;
     uint32_t n_bases = 0;
+    uint32_t max_chain = 0;        // members a chain was cut after (0: never)
     u64 wsum = 0;                  // sum of the steps' weights
 };
 
@@ -296,9 +299,14 @@ struct fsk_engine {
     std::vector<int32_t> prep_combos;              // combos whose count panels are resident
     bool prep_valid = false, prep_overflow = false;
     bool prep_shift = false;                       // ... in the slot order of the shift-class plan, with its edge keys
+    uint32_t prep_chain = 0;                       // ... whose chains were cut after this many members (ShiftPlan::max_chain)
     ShiftPlan shift;
     DevBuf<uint32_t> d_shift_steps;
     DevBuf<uint16_t> d_edge_keys;                  // [derived step][panel][dword of the panel row]: delta | sigma << 8
+    // the packed corrections (tuning dense_shift_packed): the lo / hi planes key-major, [panel pair][slot][key][16 dwords], and
+    // the edge keys as byte offsets into a staged plane; shift_packed: they hold the resident panels' list
+    DevBuf<uint32_t> d_KM, d_KMH, d_edge_offs;
+    bool shift_packed = false;
     // sparse scratch
     SxScratch sxs[2];                     // lane 0: every exact accumulate; lanes 0 and 1: variance mode's batches in flight
     hipStream_t lane_stream = nullptr;    // lane 1's stream (lane 0 runs on `stream`)
@@ -493,8 +501,10 @@ size_t dense_small_stage_bytes(u64 n_tiles, int n_splits);
 int dense_tile_small(fsk_engine* e, bool compact, u64 n_tiles, int n_splits, int nb, uint32_t Vq8, uint32_t nst, u64* K, int slots_per_split);
 
 // fsk_engine_dense_shift.hip: one weighted Gram product per chain of shifted combinations, the rest by edge lookups
-bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow);
+constexpr uint32_t SHIFT_PACKED_CHAIN = 9;  // members of a chain at most when k_dense_shift_packed runs: 8 steps of byte prefix sums
+bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overflow, uint32_t max_chain);
 int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad);
+int dense_shift_keymajor(fsk_engine* e, uint32_t panels_pad, int nb, uint32_t Vq8);
 int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t nst, u64* K, int store, uint32_t panels_pad);
 
 // fsk_engine_sparse.hip

@@ -8,7 +8,12 @@
 // One weighted Gram product per chain (k_dense_tile_shift, fsk_engine_dense_shift.hip) and four nibble lookups a cell and
 // further shift (k_dense_shift_fix) in the count panels k_dense_count writes anyway. k_dense_edge_keys writes the two keys.
 // Included by fsk_engine_dense_shift.hip only.
+//
+// The corrections have two forms. k_dense_shift_fix reads the count panels as k_dense_count wrote them (a dword = 8 keys of one
+// sequence): one nibble a 32-bit LDS read. k_dense_shift_packed (the default, tuning dense_shift_packed) reads KEY-MAJOR planes
+// (k_dense_keymajor: a dword = one key of 8 sequences): eight cells a read, summed with byte-parallel arithmetic.
 #pragma once
+#include "fsk_bytesel.h"
 #include "fsk_common.h"
 
 namespace fsk {
@@ -187,6 +192,219 @@ __global__ __launch_bounds__(512, 4) void k_dense_shift_fix(const uint32_t* C4, 
             const uint32_t id = w * (uint32_t)QW + (uint32_t)q;
             const u64 i = (u64)ti * TILE + (id >> 6) * PANEL + panel_seq(id & 63u);
             const int v = accC[h][q] + T[id * TILE + ((jd + id) & (TILE - 1u))];
+            if (i < N && j <= i && v != 0) atomicAdd(&K[tri_index(i, j)], (u64)(long long)v);
+        }
+    }
+}
+
+// ---- key-major planes and the packed corrections ------------------------------------------------------------------------
+// A key-major plane holds, per (tile side = panel pair, slot), [key][16 dwords]: dword t of a key is the 4-bit counts of the 8
+// sequences tile_index(t, 0..7) of the tile side (nibble n = tile_index(t, n): the 8 rows, or columns, of the tile kernel's lane
+// group t), so a lane that owns an 8 x 8 block of cells gets a key's counts of its 8 rows or columns in ONE dword. Inside a
+// key's 64 bytes dword t sits at t ^ km_swizzle(key): the lookups of a wave go to per-lane keys, and without the swizzle two
+// keys of equal parity would meet in the same banks whatever the lane groups are.
+__device__ __forceinline__ uint32_t km_swizzle(uint32_t key) { return ((key >> 1) & 3u) << 2; }
+// byte offset of dword t of `key` inside a staged plane = km_offset(key) ^ 4 t
+__device__ __forceinline__ uint32_t km_offset(uint32_t key) { return key << 6 | km_swizzle(key) << 2; }
+
+// Panels -> key-major: thread = (panel pair, slot, dword row of 8 keys, lane group t). The four dwords a lane group owns in a
+// panel row are adjacent (panel_slot), so a thread reads 16 bytes of each of the pair's panels and writes the 8 x 8 nibble
+// transpose: 8 dwords, one a key. grid = ceil(pairs * slots * Vq8 * 16 / 256), block = 256. `plane` = the lo or the hi plane.
+__global__ __launch_bounds__(256) void k_dense_keymajor(const uint32_t* plane, uint32_t n_pairs, int n_slots, uint32_t Vq8, uint32_t* KM) {
+    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t t = (uint32_t)id & 15u;
+    size_t rest = id >> 4;
+    const uint32_t row = (uint32_t)(rest % Vq8);
+    rest /= Vq8;
+    const uint32_t slot = (uint32_t)(rest % (uint32_t)n_slots);
+    const size_t pair = rest / (uint32_t)n_slots;
+    if (pair >= n_pairs) return;
+    const size_t slot_stride = (size_t)Vq8 * PANEL, panel_stride = (size_t)n_slots * slot_stride;
+    const uint32_t* src = plane + 2u * pair * panel_stride + slot * slot_stride + (size_t)row * PANEL + 4u * t;
+    const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + panel_stride);
+    const uint32_t in[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};  // sequence tile_index(t, n), keys 8 row .. 8 row + 7
+    uint32_t* out = KM + (pair * (size_t)n_slots + slot) * ((size_t)Vq8 * 128u);
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; ++q) {
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t n = 0; n < 8u; ++n) v |= ((in[n] >> (4u * q)) & 15u) << (4u * n);
+        const uint32_t key = row * 8u + q;
+        out[key * 16u + (t ^ km_swizzle(key))] = v;
+    }
+}
+
+// The edge keys as the packed kernel wants them: offs[q] = km_offset(delta) | km_offset(sigma) << 16 of keys[q] (14 bits each).
+__global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, size_t n, uint32_t* offs) {
+    const size_t q = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t kk = keys[q];
+    offs[q] = km_offset(kk & 255u) | km_offset(kk >> 8) << 16;
+}
+
+// k_dense_shift_fix's work — same tile table, same masks, same store-then-add contract, same step table — from key-major
+// planes: one workgroup a 128 x 128 tile, 256 threads, a lane = the tile kernel's 8 x 8 block of cells (row group tr, column
+// group tc; register (er, ec) = cell (tile_index(tr, er), tile_index(tc, ec))), 64 int32 sums. Per step the key-major plane of
+// the tile's row side under the UPPER slot (A) and of its column side under the LOWER slot (B) are staged by direct-to-LDS
+// loads, double buffered: 2 x 32 KB, two workgroups a CU.
+//   row term     c_{u+1,i}(sigma_j) - c_{u+1,i}(delta_j) for the lane's column ec: dwords tr of A[sigma_j], A[delta_j]: 8 rows
+//   column term  c_{u,j}(sigma_i) - c_{u,j}(delta_i) for the lane's row er: dwords tc of B[sigma_i], B[delta_i]: 8 columns
+// Keys are per lane. A wave is 8 row groups x 8 column groups, a 32-lane LDS service group 4 x 8: four (eight) keys of 8 (4)
+// adjacent dwords, which km_swizzle spreads over the banks by the keys' low three bits.
+//
+// Byte-parallel sums (m = 0x0f0f0f0f): ((s & m) | 0x10101010) - (d & m) holds four differences + 16, each in [1, 31], no borrow
+// between bytes; the odd nibbles the same after >> 4. Weights are prefix sums, not multiplies: inside a chain
+// sum_u (t1 - u) D_u = sum_r R_r with R_r = sum_{u <= r} D_u, and R stays packed in bytes (R += D': the stored R of step r of a
+// chain lies in [r + 1, 31 (r + 1)] — a byte for the 8 steps dense_shift_plan cuts chains to). Every byte of R is added to its
+// int32 sum (fsk_hw::add_byte). R restarts where a step's lower slot is a chain base. The bias, 16 (r + 1) a term and step, is
+// 32 x the sum of the launch's weights a cell (`bias`), taken off at the flush: the + 32 of the host's bound.
+//
+// Counts above 15: a step runs a second, workgroup-uniform pass when the row mask of EITHER side is set, and that pass reads the
+// key-major HI planes of BOTH sides, staged over the buffer just used, nibble by nibble at 16 x the step's weight (exact, and
+// rare). The unflagged side contributes nothing: k_dense_count writes every hi plane, an unflagged panel's as zeros, and
+// k_dense_keymajor transposes the hi plane unconditionally, so its key-major form is zero too. Loads the compiler can see run one step ahead, as in
+// k_dense_shift_fix. The flush adds, per wave instruction, 8 runs of 8 adjacent cells of K.
+__global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* KM, const uint32_t* KMH, const uint32_t* rowmask, const uint32_t* tile_tab,
+                                                               const uint32_t* steps, uint32_t n_steps, const uint32_t* offs, uint32_t np_seq,
+                                                               int n_slots, uint32_t Vq8, uint32_t n_bases, uint32_t bias, uint32_t N, u64* K) {
+    constexpr uint32_t SIDE = 256u * 16u;  // dwords of one staged plane (256 keys at most on this path)
+    constexpr uint32_t PBUF = 2u * SIDE;   // dwords per stage buffer: A B
+    constexpr uint32_t M4 = 0x0f0f0f0fu, B4 = 0x10101010u;
+    __shared__ __attribute__((aligned(1024))) uint32_t P[2 * PBUF];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t tr = (w >> 1) * 8u + (lane >> 3), tc = (w & 1u) * 8u + (lane & 7u);
+    const uint32_t tile = tile_tab[blockIdx.x];
+    const uint32_t ti = tile >> 16, tj = tile & 0xffffu;
+    const size_t slot_stride = (size_t)Vq8 * 128u;
+    const size_t pair_stride = (size_t)n_slots * slot_stride;
+    const uint32_t side_bytes = Vq8 * 512u;
+
+    uint32_t acc[8][8], Rr[2][8], Rc[2][8];  // acc[er][ec]; R[even / odd nibbles][ec (row term) or er (column term)]
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0u;
+        Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
+    }
+
+    const fsk_hw::lds_addr_t lds_wave = fsk_hw::lds_address(P) + w * 1024u;
+    auto load_stage = [&](const uint32_t* plane, uint32_t buf, uint32_t sl) {
+        const uint32_t up = sl >> 16, lo = sl & 0xffffu;
+#pragma unroll
+        for (uint32_t side = 0; side < 2u; ++side) {
+            const uint32_t* src = plane + (side == 0u ? ti : tj) * pair_stride + (size_t)(side == 0u ? up : lo) * slot_stride;
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q)  // (four waves land 1 KB each: 64 keys a load; the keys past 8 Vq8 are never looked up)
+                if (q * 4096u < side_bytes)
+                    fsk_hw::panel_rows_to_lds(src, side_bytes, lds_wave + (buf * PBUF + side * SIDE + q * 1024u) * 4u, q * 4096u + tid * 16u);
+        }
+    };
+    // a step's key offsets of this lane's 8 rows (oR) and 8 columns (oC), and whether it has rows with counts above 15
+    auto load_meta = [&](uint32_t s, uint32_t sl, uint4 (&oR)[2], uint4 (&oC)[2], uint32_t& fl) {
+        const uint32_t* os = offs + (size_t)s * np_seq;
+#pragma unroll
+        for (uint32_t h = 0; h < 2u; ++h) {
+            oR[h] = *reinterpret_cast<const uint4*>(os + ti * TILE + h * PANEL + 4u * tr);
+            oC[h] = *reinterpret_cast<const uint4*>(os + tj * TILE + h * PANEL + 4u * tc);
+        }
+        const uint32_t up = sl >> 16, lo = sl & 0xffffu;  // (Vq8 <= 32: one mask word a (panel, slot))
+        const uint32_t mA = rowmask[(size_t)(ti * 2u) * n_slots + up] | rowmask[(size_t)(ti * 2u + 1u) * n_slots + up];
+        const uint32_t mB = rowmask[(size_t)(tj * 2u) * n_slots + lo] | rowmask[(size_t)(tj * 2u + 1u) * n_slots + lo];
+        fl = mA | mB;
+    };
+    auto lds_at = [&](uint32_t byte_off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(P) + byte_off); };
+
+    uint32_t sl_cur = steps[0], wt_cur = steps[1];
+    uint32_t sl_nxt = n_steps > 1u ? steps[2] : 0u, wt_nxt = n_steps > 1u ? steps[3] : 0u;
+    uint4 oR_n[2], oC_n[2];
+    uint32_t fl_n;
+    load_meta(0u, sl_cur, oR_n, oC_n, fl_n);
+    uint32_t sl_n2 = 0u, wt_n2 = 0u;
+    uint32_t buf = 0;
+    load_stage(KM, 0u, (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_cur)));
+    fsk_hw::wait_panel_rows();
+    __syncthreads();
+    for (uint32_t s = 0; s < n_steps; ++s) {
+        uint32_t oR[8], oC[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            oR[4 * h] = fsk_hw::vgpr_copy(oR_n[h].x); oR[4 * h + 1] = fsk_hw::vgpr_copy(oR_n[h].y);
+            oR[4 * h + 2] = fsk_hw::vgpr_copy(oR_n[h].z); oR[4 * h + 3] = fsk_hw::vgpr_copy(oR_n[h].w);
+            oC[4 * h] = fsk_hw::vgpr_copy(oC_n[h].x); oC[4 * h + 1] = fsk_hw::vgpr_copy(oC_n[h].y);
+            oC[4 * h + 2] = fsk_hw::vgpr_copy(oC_n[h].z); oC[4 * h + 3] = fsk_hw::vgpr_copy(oC_n[h].w);
+        }
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(fl_n));
+        const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_cur));
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(wt_cur)) & 255u;
+        if (s + 1u < n_steps) {
+            const uint32_t sn = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_nxt));
+            if (s + 2u < n_steps) {
+                sl_n2 = steps[2u * (s + 2u)];
+                wt_n2 = steps[2u * (s + 2u) + 1u];
+            }
+            load_meta(s + 1u, sn, oR_n, oC_n, fl_n);
+            load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
+        }
+        if ((sl & 0xffffu) < n_bases) {  // a new chain: the prefix sums restart
+#pragma unroll
+            for (int a = 0; a < 8; ++a) Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
+        }
+        // (a staged plane's base inside P is a multiple of 16 KB and a key offset has 14 bits: one xor places both halves)
+        const uint32_t baseA = buf * PBUF * 4u, baseB = baseA + SIDE * 4u;
+        const uint32_t xA = ((tr * 4u) | baseA) * 0x10001u, xB = ((tc * 4u) | baseB) * 0x10001u;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {  // row term: column ec = e of this lane, its 8 rows
+            const uint32_t x = oC[e] ^ xA;
+            const uint32_t d = lds_at(x & 0xffffu), sg = lds_at(x >> 16);
+            Rr[0][e] += ((sg & M4) | B4) - (d & M4);
+            Rr[1][e] += (((sg >> 4) & M4) | B4) - ((d >> 4) & M4);
+            acc[0][e] = fsk_hw::add_byte<0>(acc[0][e], Rr[0][e]); acc[1][e] = fsk_hw::add_byte<0>(acc[1][e], Rr[1][e]);
+            acc[2][e] = fsk_hw::add_byte<1>(acc[2][e], Rr[0][e]); acc[3][e] = fsk_hw::add_byte<1>(acc[3][e], Rr[1][e]);
+            acc[4][e] = fsk_hw::add_byte<2>(acc[4][e], Rr[0][e]); acc[5][e] = fsk_hw::add_byte<2>(acc[5][e], Rr[1][e]);
+            acc[6][e] = fsk_hw::add_byte<3>(acc[6][e], Rr[0][e]); acc[7][e] = fsk_hw::add_byte<3>(acc[7][e], Rr[1][e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {  // column term: row er = e of this lane, its 8 columns
+            const uint32_t x = oR[e] ^ xB;
+            const uint32_t d = lds_at(x & 0xffffu), sg = lds_at(x >> 16);
+            Rc[0][e] += ((sg & M4) | B4) - (d & M4);
+            Rc[1][e] += (((sg >> 4) & M4) | B4) - ((d >> 4) & M4);
+            acc[e][0] = fsk_hw::add_byte<0>(acc[e][0], Rc[0][e]); acc[e][1] = fsk_hw::add_byte<0>(acc[e][1], Rc[1][e]);
+            acc[e][2] = fsk_hw::add_byte<1>(acc[e][2], Rc[0][e]); acc[e][3] = fsk_hw::add_byte<1>(acc[e][3], Rc[1][e]);
+            acc[e][4] = fsk_hw::add_byte<2>(acc[e][4], Rc[0][e]); acc[e][5] = fsk_hw::add_byte<2>(acc[e][5], Rc[1][e]);
+            acc[e][6] = fsk_hw::add_byte<3>(acc[e][6], Rc[0][e]); acc[e][7] = fsk_hw::add_byte<3>(acc[e][7], Rc[1][e]);
+        }
+        if (fl != 0u) {  // the hi planes over the buffer just used, at 16 x the weight
+            __syncthreads();  // everyone is done with the lo planes
+            load_stage(KMH, buf, sl);
+            fsk_hw::wait_panel_rows();
+            __syncthreads();
+            const uint32_t mul = 16u * wt;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const uint32_t x = oC[e] ^ xA, y = oR[e] ^ xB;
+                const uint32_t dA = lds_at(x & 0xffffu), sA = lds_at(x >> 16), dB = lds_at(y & 0xffffu), sB = lds_at(y >> 16);
+#pragma unroll
+                for (int n = 0; n < 8; ++n) {
+                    acc[n][e] += (((sA >> (4 * n)) & 15u) - ((dA >> (4 * n)) & 15u)) * mul;
+                    acc[e][n] += (((sB >> (4 * n)) & 15u) - ((dB >> (4 * n)) & 15u)) * mul;
+                }
+            }
+        }
+        fsk_hw::wait_panel_rows();  // this wave's part of the next stage has landed (and every load of this trip)
+        __syncthreads();            // ... everyone's has, and everyone is done with the current buffer
+        sl_cur = sl_nxt; wt_cur = wt_nxt;
+        sl_nxt = sl_n2; wt_nxt = wt_n2;
+        buf ^= 1u;
+    }
+#pragma unroll
+    for (int er = 0; er < 8; ++er) {
+        const u64 i = (u64)ti * TILE + tile_index(tr, (uint32_t)er);
+#pragma unroll
+        for (int ec = 0; ec < 8; ++ec) {
+            const u64 j = (u64)tj * TILE + tile_index(tc, (uint32_t)ec);
+            const int v = (int)(acc[er][ec] - bias);
             if (i < N && j <= i && v != 0) atomicAdd(&K[tri_index(i, j)], (u64)(long long)v);
         }
     }

@@ -135,7 +135,10 @@ typedef struct fsk_stats {
     uint64_t dense_macs;     /* count multiply-adds issued by the tile kernel: 8 per dword row and cell, the exact
                                 remainder products of the rows with counts above 15 included (profile = 1). Shift
                                 classes (tuning dense_shift): the chain bases alone, tiles x rows x bases x 8 x 128^2 —
-                                the derived combinations cost lookups, not multiply-adds        */
+                                the derived combinations cost lookups, not multiply-adds. Tuning dense_shift_packed
+                                (0, the default: the lookups read key-major planes eight cells at a time; -1: the count
+                                panels, one cell a read) cuts a chain after nine members when it is 0: a class of more
+                                shifts is two chains, one more base                              */
     uint64_t panel_bytes;    /* bytes of count panels written (= read at least once)            */
     double u4_tile_launches; /* launches of the 4-bit tile kernel (v_dot8_u32_u4)                */
     double max_windows;      /* max over sequences of (length - g + 1), of both strands in reverse-complement mode: bounds a cell per combo
