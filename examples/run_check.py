@@ -2,7 +2,8 @@
 """End-to-end check in the style of the reference's only CI test (QData/FastSK
 test/run_check.py:37-64): gapped-k-mer kernel on the GPU -> LinearSVC + 5-fold calibration ->
 test AUC >= 0.9 on EP300. Same user code as the reference; only the import resolves to the
-MI355X engine (this repo's `fastsk/` alias package).
+MI355X engine (this repo's `fastsk/` alias package). Then the same data through the resident pipeline
+(`fit_svm` + `decision_function_np`), which the reference does not have.
 
     python examples/run_check.py --train EP300.train.fasta --test EP300.test.fasta
 """
@@ -45,6 +46,17 @@ def main():
     print("calibrated linear SVM on the kernel rows: accuracy %.4f, test AUC %.4f" % (acc, auc))
     if auc < 0.9:  # the reference's acceptance threshold (test/run_check.py:64)
         raise SystemExit("test AUC %.4f is below 0.9" % auc)
+
+    # beside it, the resident pipeline: a C-SVC trained and applied on the triangle the compute call left on the GPU — no kernel
+    # matrix crosses to the host (fit_svm wants labels -1 / +1)
+    t0 = time.time()
+    info = k.fit_svm(np.where(np.array(Ytrain) > 0, 1, -1), C=1.0, eps=1e-3)
+    dec = k.decision_function_np("test")
+    auc_svm = roc_auc_score(Ytest, dec)
+    print("C-SVC on the resident triangle: %d iterations (%s), %d support vectors, fit + decision values in %.3f s, test AUC %.4f"
+          % (info["iterations"], info["form"], info["n_sv"], time.time() - t0, auc_svm))
+    if auc_svm < 0.9:
+        raise SystemExit("test AUC %.4f of the resident SVM is below 0.9" % auc_svm)
 
 
 if __name__ == "__main__":

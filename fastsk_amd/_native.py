@@ -53,6 +53,18 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class SvmInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int64), ("gap", C.c_double), ("objective", C.c_double), ("n_sv", C.c_int64),
+                ("n_bsv", C.c_int64), ("converged", C.c_int32), ("form", C.c_int32), ("launches", C.c_int64),
+                ("ms", C.c_double), ("reserved", C.c_double * 4)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["converged"] = bool(d["converged"])
+        d["form"] = {1: "workgroup", 2: "two-launch"}.get(d["form"], "none")
+        return d
+
+
 class MultiInfo(C.Structure):
     _fields_ = [("ndev", C.c_int32), ("devices", C.c_int32 * 16), ("collective", C.c_int32), ("comm_ranks", C.c_int32),
                 ("bands", C.c_int32), ("narrow", C.c_int32), ("reduce_bytes", C.c_int64),
@@ -77,7 +89,8 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_counts_digest", "fsk_alloc_block_device", "fsk_free_device", "fsk_set_skip_test_block",
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
            "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
-           "fsk_set_wildcards", "fsk_set_center_weights"]
+           "fsk_set_wildcards", "fsk_set_center_weights", "fsk_svm_train", "fsk_svm_get_model", "fsk_svm_decision",
+           "fsk_svm_decision_device"]
 
 
 _hip_shared = False
@@ -216,6 +229,10 @@ class Library:
             "fsk_get_mismatch_info": ([vp, C.POINTER(i32), vp, vp, i32], C.c_int),
             "fsk_get_mismatch_times": ([vp, vp, vp, i32], C.c_int),
             "fsk_mismatch_levels": ([i32, vp, i32, vp, C.POINTER(i32)], C.c_int),
+            "fsk_svm_train": ([vp, vp, i64, C.c_double, C.c_double, i64], C.c_int),
+            "fsk_svm_get_model": ([vp, vp, C.POINTER(C.c_double), C.POINTER(SvmInfo)], C.c_int),
+            "fsk_svm_decision": ([vp, i64, i64, vp], C.c_int),
+            "fsk_svm_decision_device": ([vp, i64, i64, vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -761,6 +778,31 @@ class Engine:
 
     def save_kernel(self, path):
         self._ck(self.lib.L.fsk_save_kernel(self.h, path.encode()))
+
+    # ---- the SVM stage on the resident triangle
+    def svm_train(self, labels, C=1.0, eps=1e-3, max_iter=-1):
+        """``fsk_svm_train``: a C-SVC on the train x train part of the finalized result, ``labels`` in {-1, +1}. Returns the
+        info of the solve (``svm_model()[2]``)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim != 1:
+            raise ValueError("labels must be 1-D")
+        self._ck(self.lib.L.fsk_svm_train(self.h, labels.ctypes.data if len(labels) else None, len(labels), float(C), float(eps),
+                                          int(max_iter)))
+        return self.svm_model()[2]
+
+    def svm_model(self):
+        """(alpha[n_train], rho, info dict) of the last ``svm_train``."""
+        alpha = np.empty(self.n_train, dtype=np.float64)
+        rho = C.c_double(0.0)
+        info = SvmInfo()
+        self._ck(self.lib.L.fsk_svm_get_model(self.h, alpha.ctypes.data, C.byref(rho), C.byref(info)))
+        return alpha, rho.value, info.as_dict()
+
+    def svm_decision(self, r0, r1):
+        """Decision values of rows [r0, r1) of the sequences (train rows first)."""
+        out = np.empty(max(r1 - r0, 0), dtype=np.float64)
+        self._ck(self.lib.L.fsk_svm_decision(self.h, r0, r1, out.ctypes.data))
+        return out
 
     def stats(self):
         s = Stats()

@@ -6,7 +6,9 @@
 // Deviations, all documented in INTEGRATION.md:
 //   - errors raise ValueError / RuntimeError instead of printf + exit(1) (fastsk.cpp:53-58);
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
-//     NotImplementedError (they are unusable from Python in the reference as well);
+//     NotImplementedError (they are unusable from Python in the reference as well); the SVM stage is additive instead:
+//     fit_svm(labels, C, eps, max_iter), get_dual_coef_np(), get_intercept(), decision_function_np / _dlpack(which) train
+//     and score a C-SVC on the triangle the compute call left on the device (fsk_svm_train / fsk_svm_decision);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
@@ -138,6 +140,7 @@ class FastSK {
     std::vector<int32_t> wildcards_;
     std::vector<uint32_t> center_weights_;  // centre-weighted mode: the profile (empty: off)
     std::vector<uint64_t> weights_;      // mismatch-weighted mode: c_0..c_m (empty: off)
+    std::vector<int32_t> labels_;        // fit_svm: the labels of the model at hand
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
 
@@ -571,6 +574,66 @@ public:
         d["n_levels"] = n; d["a"] = coeff; d["levels"] = levels;
         return d;
     }
+    // ---- additive: the SVM stage on the resident triangle (fsk_svm_train / fsk_svm_decision). fit() / score() stay the
+    // reference's stubs; these train and score on the result compute_kernel / compute_train has left on the device.
+    py::dict fit_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter) {
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svm_train(h_, labels.data(), (int64_t)labels.shape(0), C, eps, max_iter);
+        }
+        check(rc);
+        labels_.assign(labels.data(), labels.data() + labels.shape(0));
+        fsk_svm_info s;
+        check(fsk_svm_get_model(h_, nullptr, nullptr, &s));
+        py::dict d;
+        d["iterations"] = s.iterations; d["gap"] = s.gap; d["objective"] = s.objective; d["n_sv"] = s.n_sv; d["n_bsv"] = s.n_bsv;
+        d["converged"] = (bool)s.converged; d["form"] = s.form == 1 ? "workgroup" : "two-launch"; d["launches"] = s.launches;
+        d["ms"] = s.ms;
+        return d;
+    }
+    py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
+        py::array_t<double> out((py::ssize_t)n_train_);
+        check(fsk_svm_get_model(h_, out.mutable_data(), nullptr, nullptr));
+        if ((int64_t)labels_.size() != n_train_) throw std::runtime_error("no model: call fit_svm first");
+        double* a = out.mutable_data();
+        for (int64_t t = 0; t < n_train_; ++t) a[t] = labels_[(size_t)t] > 0 ? a[t] : -a[t];
+        return out;
+    }
+    double get_intercept() const {  // -rho, as scikit-learn's intercept_
+        double rho = 0;
+        check(fsk_svm_get_model(h_, nullptr, &rho, nullptr));
+        return -rho;
+    }
+    void decision_rows(const std::string& which, int64_t* r0, int64_t* r1) const {
+        if (which == "test") { *r0 = n_train_; *r1 = n_train_ + n_test_; }
+        else if (which == "train") { *r0 = 0; *r1 = n_train_; }
+        else throw py::value_error("which must be 'test' or 'train'");
+    }
+    // sum_i alpha_i y_i K(r, i) - rho of the test (or train) rows: only cells with a train column are read, so the
+    // test x test block is neither needed nor computed (skip_test_block=True / "lazy")
+    py::array_t<double> decision_function_np(const std::string& which) const {
+        int64_t r0, r1;
+        decision_rows(which, &r0, &r1);
+        py::array_t<double> out((py::ssize_t)(r1 - r0));
+        check(fsk_svm_decision(h_, r0, r1, out.mutable_data()));
+        return out;
+    }
+    py::capsule decision_function_dlpack(const std::string& which) {
+        int64_t r0, r1;
+        decision_rows(which, &r0, &r1);
+        if (r1 == r0) throw py::value_error("no rows");
+        double rho = 0;
+        check(fsk_svm_get_model(h_, nullptr, &rho, nullptr));  // (RuntimeError before anything is allocated)
+        double* dev = nullptr;
+        check(fsk_alloc_block_device(h_, r0, r1, 0, 1, &dev));  // the engine's allocator: a column of r1 - r0 doubles
+        const int rc = fsk_svm_decision_device(h_, r0, r1, dev);
+        if (rc != FSK_OK) (void)fsk_free_device(h_, dev);
+        check(rc);
+        return dlpack_of(dev, 1, r1 - r0, 1);
+    }
     void fit(double, double, double, const std::string&) const {
         PyErr_SetString(PyExc_NotImplementedError,
                         "fit(): the LIBSVM stage is outside the accelerated path; feed get_train_kernel() to scikit-learn "
@@ -636,6 +699,11 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("get_triangle_dlpack", &FastSK::get_triangle_dlpack)
         .def("set_combo_order", &FastSK::set_combo_order, py::arg("order"))
         .def("mismatch_info", &FastSK::mismatch_info)
+        .def("fit_svm", &FastSK::fit_svm, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3, py::arg("max_iter") = -1)
+        .def("get_dual_coef_np", &FastSK::get_dual_coef_np)
+        .def("get_intercept", &FastSK::get_intercept)
+        .def("decision_function_np", &FastSK::decision_function_np, py::arg("which") = "test")
+        .def("decision_function_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
         .def("stats", &FastSK::stats);
     // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
     m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {

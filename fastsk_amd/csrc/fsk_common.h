@@ -66,6 +66,15 @@ __device__ __forceinline__ u64 tri_index(u64 i, u64 j) {  // j <= i  (tri_access
     return i * (i + 1) / 2 + j;
 }
 
+// One cell of the normalised kernel (fastsk_kernel.cpp:96-103) from a raw cell and the raw diagonals: IEEE fp64 multiply,
+// correctly rounded sqrt and divide, no contraction. What every getter (fsk_kernels_result.h) and the SVM stage
+// (fsk_kernels_svm.h) return or read, so that they agree to the bit.
+__device__ __forceinline__ double normalised_cell(double x, double di, double dj, bool is_diag) {
+    // off-diagonal: K_ij / sqrt(K_ii * K_jj) with the RAW diagonals; diagonal: K_ii / sqrt(K_ii*K_ii)
+    const double prod = is_diag ? __dmul_rn(x, x) : __dmul_rn(di, dj);
+    return __ddiv_rn(x, __dsqrt_rn(prod));
+}
+
 // ---------------------------------------------------------------------------------------------
 // block-wide exclusive scan of one value per thread, 256 threads (4 waves). tmp: >= 4 entries.
 // Every thread of the block must call it.

@@ -127,6 +127,8 @@ using fsk_detail::DevBuf;
     X(mismatch_order, 0, 0, 1, "mismatch-weighted mode: 1 = the levels run from m = d down to 0 (0: from 0 up to d)")                   \
     X(collective, 0, 0, 2, "fsk_create_multi: FSK_COLL_* when fsk_config.collective is FSK_COLL_AUTO")                                \
     X(deadline_ms, 120000, -1, 86400000, "fsk_create_multi: the fail-fast bound when fsk_config.deadline_ms is 0 (negative: none)")   \
+    X(svm_wg_max, 8192, 0, 8192, "fsk_svm_train: up to this many training rows the solver is one workgroup with alpha, G and y in LDS (k_svm_wg); beyond, two launches an iteration (k_svm_select_i / k_svm_select_j); 0 = always those") \
+    X(svm_chunk, 256, 1, 65536, "fsk_svm_train: iterations enqueued between two reads of the solver's status record (k_svm_wg: iterations a launch)") \
     FSK_TUNING_TEST_KEYS(X)
 // keys that exist in test builds only (-DFSK_TEST_HOOKS: the CPU emulation and tests/hooks' library; never the product):
 // engine fault_rank of a group is late by fault_ms before the collective of band fault_band — fault_kind 1: its worker
@@ -185,6 +187,24 @@ struct ShiftPlan {
     uint32_t n_bases = 0;
     uint32_t max_chain = 0;        // members a chain was cut after (0: never)
     u64 wsum = 0;                  // sum of the steps' weights
+};
+
+// The SVM stage (fsk_engine_svm.hip): the model of the last fsk_svm_train on this result and the solver's device state. A new
+// result (make_diag) drops the model; whatever makes the result stale (load, accumulate, reset: finalized = false) hides it.
+struct SvmState {
+    bool valid = false;
+    std::vector<double> alpha;       // [n_train]
+    std::vector<signed char> y;      // [n_train], -1 / +1
+    double rho = 0;
+    fsk_svm_info info{};
+    DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_out;
+    DevBuf<signed char> d_y;
+    DevBuf<unsigned char> d_rec;     // the records the launches of a solve hand each other (fsk_kernels_svm.h)
+    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); }
+    SvmState() = default;
+    SvmState(const SvmState&) = delete;
+    SvmState& operator=(const SvmState&) = delete;
+    ~SvmState() { release(); }
 };
 
 struct fsk_engine {
@@ -379,6 +399,7 @@ struct fsk_engine {
     bool trace() const { return tune.trace != 0; }
 
     fsk_stats st{};
+    SvmState svm;
 
     int fail(int code, const char* fmt, ...) {
         char buf[512];

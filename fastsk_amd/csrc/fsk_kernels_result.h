@@ -15,11 +15,7 @@ __global__ __launch_bounds__(256) void k_diag(const SrcT* K, double* diag, uint3
     if (i < N) diag[i] = (double)K[tri_index(i, i)];
 }
 
-__device__ __forceinline__ double normalised_cell(double x, double di, double dj, bool is_diag) {
-    // off-diagonal: K_ij / sqrt(K_ii * K_jj) with the RAW diagonals; diagonal: K_ii / sqrt(K_ii*K_ii)
-    const double prod = is_diag ? __dmul_rn(x, x) : __dmul_rn(di, dj);
-    return __ddiv_rn(x, __dsqrt_rn(prod));
-}
+// (normalised_cell, the one cell of every getter, lives in fsk_common.h: the SVM stage reads the triangle through it too)
 
 template <typename SrcT>
 __global__ __launch_bounds__(256) void k_block(const SrcT* K, const double* diag, u64 i0, u64 rows, u64 j0, u64 cols,

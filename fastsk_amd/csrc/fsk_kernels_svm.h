@@ -1,0 +1,412 @@
+// fsk_kernels_svm.h — a C-SVC dual solver and its decision values on the RESIDENT result triangle (fsk_svm_train,
+// fsk_svm_decision). Included by fsk_engine_svm.hip only.
+//
+// The kernel is cosine-normalised: every K(t,t) is 1, the whole matrix is on the device, so the solver is SMO with LIBSVM's
+// second-order working-set selection and nothing else — no row cache, no shrinking. A row of Q is read where it lies: cells
+// tri_index(i, 0..i) (contiguous) and tri_index(t, i), t > i (one cell a triangle row), each through normalised_cell, i.e. the
+// very IEEE values the getters hand out, from whichever triangle the result is (u64 counts, fp64 of variance mode).
+//
+// The arithmetic of one iteration is fixed to the operation (tests restate it in numpy and compare bit for bit). With
+// y in {-1, +1}, alpha = 0 and G = -1 at the start, v_t = -y_t G_t:
+//   1. I_up = {y > 0, alpha < C} u {y < 0, alpha > 0}, I_low = {y > 0, alpha > 0} u {y < 0, alpha < C};
+//      i = argmax v over I_up, Gmax = v_i, Gmin = min v over I_low; stop when Gmax - Gmin <= eps (then: at max_iter);
+//   2. b_t = Gmax - v_t, a_t = K_ii + K_tt - 2 K_it = 2 - 2 K_it (TAU where <= 0): j = argmin over I_low, b_t > 0, of -(b_t b_t) / a_t;
+//   3. the two-variable step and its clipping to [0, C]^2 as in LIBSVM's Solver::Solve (svm_step);
+//   4. G_t = G_t + ((Q_it dalpha_i) + (Q_jt dalpha_j)), Q_it = y_i y_t K_it.
+// Every tie goes to the lowest index: (value, index) compared lexicographically is associative, so neither the shape of a
+// reduction tree nor the grid shows in the result. Products and sums are the __d*_rn forms: no contraction.
+#pragma once
+#include "fsk_common.h"
+
+namespace fsk {
+
+constexpr double SVM_TAU = 1e-12;
+constexpr int SVM_NONE = 0x7fffffff;     // index of "no candidate": loses every tie
+constexpr int SVM_WG_THREADS = 1024;     // k_svm_wg: one workgroup
+constexpr int SVM_WG_ITEMS = 8;          // ... of at most this many elements a thread (8192 = svm_wg_max's ceiling)
+constexpr int SVM_PART = 32;             // second level of a workgroup's reductions
+
+// What the launches of one solve hand each other (device memory). rec_b: written by launch B (k_svm_select_j) and by
+// k_svm_wg, read by launch A and the host. rec_a: written by launch A (k_svm_select_i), read by launch B. No launch reads a
+// record that one of its own workgroups writes.
+struct SvmRecB {
+    long long iter;          // two-variable steps taken so far
+    double gmax, gmin;       // of the last selection
+    double ai, Gi;           // alpha_i, G_i before the pending step
+    int i, yi;
+    int done, converged;     // done: stop test met (converged = 1) or max_iter reached (converged = 0)
+    int pending, pad;        // a step (i chosen, j's candidates reduced per workgroup) waits for launch A
+};
+struct SvmRecA {
+    long long iter;
+    int done, pad;           // 1: launch B has said done; 2: launch A found no j candidate, launch B is to say done
+};
+struct SvmCandI {            // a workgroup's share of step 1
+    double vmax, vmin;
+    int imax, pad;
+};
+struct SvmCandJ {            // a workgroup's share of step 2, with what the step needs of j
+    double obj, aj, Gj, Kij;
+    int j, yj;
+};
+
+// cell (a, b) of the symmetric normalised matrix, either order
+template <typename SrcT>
+__device__ __forceinline__ double svm_cell(const SrcT* K, const double* diag, uint32_t a, uint32_t b) {
+    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    const double x = (double)K[tri_index(hi, lo)];
+    return normalised_cell(x, diag[hi], diag[lo], hi == lo);
+}
+
+__device__ __forceinline__ double svm_inf() { return __builtin_huge_val(); }
+__device__ __forceinline__ bool svm_in_up(int y, double a, double C) { return y > 0 ? a < C : a > 0.0; }
+__device__ __forceinline__ bool svm_in_low(int y, double a, double C) { return y > 0 ? a > 0.0 : a < C; }
+__device__ __forceinline__ double svm_v(int y, double G) { return y > 0 ? -G : G; }
+// (value, index) orders: the larger value / the smaller value first, then the lower index
+__device__ __forceinline__ bool svm_better_max(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
+__device__ __forceinline__ bool svm_better_min(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
+// step 2 for one element that lies in I_low: its objective, or "none" (b <= 0)
+__device__ __forceinline__ bool svm_j_objective(double gmax, double v, double kit, double* obj) {
+    const double b = __dsub_rn(gmax, v);
+    if (!(b > 0.0)) return false;
+    double a = __dsub_rn(2.0, __dmul_rn(2.0, kit));
+    if (a <= 0.0) a = SVM_TAU;
+    *obj = -__ddiv_rn(__dmul_rn(b, b), a);
+    return true;
+}
+
+// Step 3: LIBSVM's Solver::Solve for one pair with Q_ii = Q_jj = 1 and C_i = C_j = C; Qij = y_i y_j K_ij. ai, aj: in the old
+// values, out the new ones.
+__device__ __forceinline__ void svm_step(int yi, int yj, double Kij, double Gi, double Gj, double C, double* ai, double* aj) {
+    const double Qij = yi == yj ? Kij : -Kij;
+    double a_i = *ai, a_j = *aj;
+    if (yi != yj) {
+        double quad = __dadd_rn(2.0, __dmul_rn(2.0, Qij));
+        if (quad <= 0.0) quad = SVM_TAU;
+        const double delta = __ddiv_rn(__dsub_rn(-Gi, Gj), quad);
+        const double diff = __dsub_rn(a_i, a_j);
+        a_i = __dadd_rn(a_i, delta);
+        a_j = __dadd_rn(a_j, delta);
+        if (diff > 0.0) {
+            if (a_j < 0.0) { a_j = 0.0; a_i = diff; }
+        } else {
+            if (a_i < 0.0) { a_i = 0.0; a_j = -diff; }
+        }
+        if (diff > 0.0) {  // (C_i - C_j = 0)
+            if (a_i > C) { a_i = C; a_j = __dsub_rn(C, diff); }
+        } else {
+            if (a_j > C) { a_j = C; a_i = __dadd_rn(C, diff); }
+        }
+    } else {
+        double quad = __dsub_rn(2.0, __dmul_rn(2.0, Qij));
+        if (quad <= 0.0) quad = SVM_TAU;
+        const double delta = __ddiv_rn(__dsub_rn(Gi, Gj), quad);
+        const double sum = __dadd_rn(a_i, a_j);
+        a_i = __dsub_rn(a_i, delta);
+        a_j = __dadd_rn(a_j, delta);
+        if (sum > C) {
+            if (a_i > C) { a_i = C; a_j = __dsub_rn(sum, C); }
+        } else {
+            if (a_j < 0.0) { a_j = 0.0; a_i = sum; }
+        }
+        if (sum > C) {
+            if (a_j > C) { a_j = C; a_i = __dsub_rn(sum, C); }
+        } else {
+            if (a_i < 0.0) { a_i = 0.0; a_j = sum; }
+        }
+    }
+    *ai = a_i;
+    *aj = a_j;
+}
+
+// step 4 for one element
+__device__ __forceinline__ double svm_new_G(double G, int yt, int yi, int yj, double kit, double kjt, double dai, double daj) {
+    const double qit = yi == yt ? kit : -kit, qjt = yj == yt ? kjt : -kjt;
+    return __dadd_rn(G, __dadd_rn(__dmul_rn(qit, dai), __dmul_rn(qjt, daj)));
+}
+
+// A workgroup's reduction of one (value, index, tag) a thread, in two levels through LDS (blockDim.x a multiple of 64, at most
+// 1024): thread s < 32 takes entries s, s + 32, ... (consecutive lanes read consecutive entries), then every thread takes
+// the 32 partials (broadcast reads). MAX: the larger value wins, else the smaller; ties to the lower index. Every thread
+// returns the same winner. Two barriers; the arrays may be written again right after the call (the next call's first
+// barrier separates its level-two writes from this call's level-two reads).
+struct SvmRed {
+    double* v;   // [blockDim.x]
+    int* i;      // [blockDim.x]
+    int* w;      // [blockDim.x]  a tag that travels with the winner
+    double* pv;  // [SVM_PART]
+    int* pi;
+    int* pw;
+};
+template <bool MAX>
+__device__ __forceinline__ void svm_reduce(const SvmRed& r, double* v, int* i, int* w) {
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    r.v[tid] = *v; r.i[tid] = *i; r.w[tid] = *w;
+    __syncthreads();
+    if (tid < (uint32_t)SVM_PART) {
+        double bv = r.v[tid];
+        int bi = r.i[tid], bw = r.w[tid];
+        for (uint32_t q = tid + SVM_PART; q < nt; q += SVM_PART) {
+            const double x = r.v[q];
+            const int xi = r.i[q];
+            if (MAX ? svm_better_max(x, xi, bv, bi) : svm_better_min(x, xi, bv, bi)) { bv = x; bi = xi; bw = r.w[q]; }
+        }
+        r.pv[tid] = bv; r.pi[tid] = bi; r.pw[tid] = bw;
+    }
+    __syncthreads();
+    double bv = r.pv[0];
+    int bi = r.pi[0], bw = r.pw[0];
+#pragma unroll 4
+    for (int q = 1; q < SVM_PART; ++q) {
+        const double x = r.pv[q];
+        const int xi = r.pi[q];
+        if (MAX ? svm_better_max(x, xi, bv, bi) : svm_better_min(x, xi, bv, bi)) { bv = x; bi = xi; bw = r.pw[q]; }
+    }
+    *v = bv; *i = bi; *w = bw;
+}
+
+// LDS of k_svm_wg for n elements and nt threads, in bytes (the host sizes the launch with it)
+__host__ __device__ inline size_t svm_wg_lds(uint32_t n, uint32_t nt) {
+    const size_t n8 = ((size_t)n + 7) & ~(size_t)7;
+    return n8 * 17 + (size_t)nt * 16 + (size_t)SVM_PART * 16;
+}
+
+// =============================================================================================
+// ONE WORKGROUP (n <= svm_wg_max <= 8192): alpha, G and y live in LDS (17 bytes an element: 139,264 bytes at 8192, beside
+// 17 KB of reduction scratch — one workgroup may take all 160 KiB of a CU), up to `chunk` iterations a launch. The state is
+// loaded from and written back to device memory around them, so no launch runs unbounded. Element e belongs to thread
+// e mod blockDim.x, which alone writes its alpha and G. Seven barriers an iteration (two a reduction, one before the writes).
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const double* diag, uint32_t n, double C, double eps,
+                                                           long long max_iter, uint32_t chunk, double* alpha, double* G,
+                                                           const signed char* y, SvmRecB* rec) {
+    FSK_DYN_SHARED(unsigned char, smem);
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    const size_t n8 = ((size_t)n + 7) & ~(size_t)7;
+    double* sA = reinterpret_cast<double*>(smem);
+    double* sG = sA + n8;
+    SvmRed red;
+    red.v = sG + n8;
+    red.pv = red.v + nt;
+    red.i = reinterpret_cast<int*>(red.pv + SVM_PART);
+    red.w = red.i + nt;
+    red.pi = red.w + nt;
+    red.pw = red.pi + SVM_PART;
+    signed char* sY = reinterpret_cast<signed char*>(red.pw + SVM_PART);
+
+    for (uint32_t e = tid; e < n; e += nt) { sA[e] = alpha[e]; sG[e] = G[e]; sY[e] = y[e]; }
+    long long iter = rec->iter;
+    double gmax = rec->gmax, gmin = rec->gmin;
+    int done = 0, converged = 0;
+    __syncthreads();
+
+    for (uint32_t c = 0; c < chunk; ++c) {
+        // ---- 1. i, Gmax, Gmin
+        double vmax = -svm_inf(), vmin = svm_inf();
+        int imax = SVM_NONE, none = 0;
+        for (uint32_t e = tid; e < n; e += nt) {
+            const int ye = sY[e];
+            const double a = sA[e], v = svm_v(ye, sG[e]);
+            if (svm_in_up(ye, a, C) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
+            if (svm_in_low(ye, a, C) && v < vmin) vmin = v;
+        }
+        svm_reduce<true>(red, &vmax, &imax, &none);
+        int at = 0;
+        svm_reduce<false>(red, &vmin, &at, &none);
+        gmax = vmax; gmin = vmin;
+        if (__dsub_rn(gmax, gmin) <= eps) { done = 1; converged = 1; break; }
+        if (iter >= max_iter) { done = 1; break; }
+        const uint32_t i = (uint32_t)imax;
+        // ---- 2. j (row i stays in registers for step 4)
+        double kit[SVM_WG_ITEMS];
+        double obj = svm_inf();
+        int j = SVM_NONE;
+#pragma unroll
+        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
+            const uint32_t e = tid + (uint32_t)q * nt;
+            kit[q] = 0.0;
+            if (e < n) {
+                kit[q] = svm_cell(K, diag, i, e);
+                const int ye = sY[e];
+                double o;
+                if (svm_in_low(ye, sA[e], C) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
+            }
+        }
+        svm_reduce<false>(red, &obj, &j, &none);
+        // no candidate (LIBSVM's Gmin_idx == -1; only cells that are not numbers — a result with a zero diagonal — get here,
+        // a NaN objective wins no comparison): the solve ends, not converged, the step not taken
+        if (j == SVM_NONE) { done = 1; break; }
+        // ---- 3. the step, by every thread alike
+        const int yi = sY[i], yj = sY[j];
+        const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
+        double ai = ai0, aj = aj0;
+        svm_step(yi, yj, svm_cell(K, diag, i, (uint32_t)j), Gi, Gj, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
+        __syncthreads();  // (everybody has read alpha and G of i and j)
+        // ---- 4. G, alpha
+#pragma unroll
+        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
+            const uint32_t e = tid + (uint32_t)q * nt;
+            if (e < n) {
+                sG[e] = svm_new_G(sG[e], sY[e], yi, yj, kit[q], svm_cell(K, diag, (uint32_t)j, e), dai, daj);
+                if (e == i) sA[e] = ai;
+                if (e == (uint32_t)j) sA[e] = aj;
+            }
+        }
+        ++iter;
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < n; e += nt) { alpha[e] = sA[e]; G[e] = sG[e]; }
+    if (tid == 0) {
+        rec->iter = iter; rec->gmax = gmax; rec->gmin = gmin;
+        rec->done = done; rec->converged = converged; rec->pending = 0;
+    }
+}
+
+// =============================================================================================
+// TWO LAUNCHES AN ITERATION (any n): 256 threads a workgroup, one element a thread, no barrier across workgroups — what one
+// launch's workgroups tell each other travels through device memory to the NEXT launch, where every workgroup reduces the
+// per-workgroup candidates again (the same winner everywhere: the order is total).
+constexpr int SVM_THREADS = 256;
+
+// LAUNCH A: finish the pending step — j from the workgroups' candidates, the scalar step, this workgroup's slice of G, alpha
+// of i and j by the workgroups that hold them — then this workgroup's share of the next step 1.
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, const double* diag, uint32_t n, double C, double* alpha,
+                                                              double* G, const signed char* y, const double* krow,
+                                                              const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i,
+                                                              const SvmCandJ* cand_j, uint32_t n_wg) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (rb->done) {
+        if (blockIdx.x == 0 && tid == 0) { ra->iter = rb->iter; ra->done = 1; }
+        return;
+    }
+    long long iter = rb->iter;
+    const bool mine = t < n;
+    const int yt = mine ? (int)y[t] : 1;
+    double a = mine ? alpha[t] : 0.0, g = mine ? G[t] : 0.0;
+    if (rb->pending) {
+        double obj = svm_inf();
+        int j = SVM_NONE, w = 0;
+        for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+            const double o = cand_j[q].obj;
+            const int oj = cand_j[q].j;
+            if (svm_better_min(o, oj, obj, j)) { obj = o; j = oj; w = (int)q; }
+        }
+        svm_reduce<false>(red, &obj, &j, &w);
+        if (j == SVM_NONE) {  // no workgroup had a candidate: the solve ends here (launch B turns done = 2 into the host's done flag)
+            if (blockIdx.x == 0 && tid == 0) { ra->iter = iter; ra->done = 2; }
+            return;
+        }
+        const SvmCandJ cj = cand_j[w];
+        const int i = rb->i, yi = rb->yi;
+        double ai = rb->ai, aj = cj.aj;
+        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
+        if (mine) {
+            g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, (uint32_t)j, t), dai, daj);
+            G[t] = g;
+            if (t == (uint32_t)i) { a = ai; alpha[t] = a; }
+            if (t == (uint32_t)j) { a = aj; alpha[t] = a; }
+        }
+        ++iter;
+    }
+    const double v = svm_v(yt, g);
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    if (mine && svm_in_up(yt, a, C)) { vmax = v; imax = (int)t; }
+    if (mine && svm_in_low(yt, a, C)) vmin = v;
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    if (tid == 0) {
+        cand_i[blockIdx.x].vmax = vmax; cand_i[blockIdx.x].vmin = vmin; cand_i[blockIdx.x].imax = imax;
+        if (blockIdx.x == 0) { ra->iter = iter; ra->done = 0; }
+    }
+}
+
+// LAUNCH B: i, Gmax and Gmin from the workgroups' candidates; the stop tests; row i (kept in krow for launch A), this
+// workgroup's candidate for j.
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, const double* diag, uint32_t n, double C, double eps,
+                                                              long long max_iter, const double* alpha, const double* G,
+                                                              const signed char* y, double* krow, SvmRecB* rb, const SvmRecA* ra,
+                                                              const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (ra->done) {
+        // 2: launch A found no j candidate — the end of the solve, not converged (gmax, gmin stay those of the last selection)
+        if (ra->done == 2 && blockIdx.x == 0 && tid == 0) { rb->iter = ra->iter; rb->done = 1; rb->converged = 0; rb->pending = 0; }
+        return;
+    }
+    const long long iter = ra->iter;
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+        const double x = cand_i[q].vmax, m = cand_i[q].vmin;
+        const int xi = cand_i[q].imax;
+        if (svm_better_max(x, xi, vmax, imax)) { vmax = x; imax = xi; }
+        if (m < vmin) vmin = m;
+    }
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    const bool converged = __dsub_rn(vmax, vmin) <= eps;
+    if (converged || iter >= max_iter) {
+        if (blockIdx.x == 0 && tid == 0) {
+            rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+            rb->done = 1; rb->converged = converged ? 1 : 0; rb->pending = 0;
+        }
+        return;
+    }
+    const uint32_t i = (uint32_t)imax;
+    double obj = svm_inf(), kit = 0.0, a = 0.0, g = 0.0;
+    int j = SVM_NONE, yt = 1;
+    if (t < n) {
+        kit = svm_cell(K, diag, i, t);
+        krow[t] = kit;
+        yt = (int)y[t]; a = alpha[t]; g = G[t];
+        double o;
+        if (svm_in_low(yt, a, C) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
+    }
+    svm_reduce<false>(red, &obj, &j, &none);
+    if (j == SVM_NONE) {
+        if (tid == 0) { cand_j[blockIdx.x].obj = svm_inf(); cand_j[blockIdx.x].j = SVM_NONE; }
+    } else if (t == (uint32_t)j) {
+        SvmCandJ c;
+        c.obj = obj; c.aj = a; c.Gj = g; c.Kij = kit; c.j = j; c.yj = yt;
+        cand_j[blockIdx.x] = c;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+        rb->ai = alpha[i]; rb->Gi = G[i]; rb->i = (int)i; rb->yi = (int)y[i];
+        rb->done = 0; rb->converged = 0; rb->pending = 1;
+    }
+}
+
+// =============================================================================================
+// DECISION VALUES: out[r - r0] = sum_{i < n_train} coef_i K(r, i) - rho for rows [r0, r1) of the N-set, coef = alpha y. One
+// wave a row: a test row's train columns are contiguous in the triangle, a train row reads tri_index(r, 0..r) and then one
+// cell a triangle row. Never a test x test cell. A lane sums its columns (lane, lane + 64, ...) in order, then the wave's
+// lanes by xor shuffles; columns whose coefficient is zero are not read.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_decision(const SrcT* K, const double* diag, const double* coef, uint32_t n_train,
+                                                      uint32_t r0, uint32_t r1, double rho, double* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = r0 + blockIdx.x * 4u + (threadIdx.x >> 6);
+    const bool live = r < r1;  // (a dead wave still takes part in nothing: shuffles are per wave)
+    double acc = 0.0;
+    if (live)
+        for (uint32_t i = lane; i < n_train; i += 64u) {
+            const double c = coef[i];
+            if (c != 0.0) acc = __dadd_rn(acc, __dmul_rn(c, svm_cell(K, diag, r, i)));
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
+    if (live && lane == 0) out[r - r0] = __dsub_rn(acc, rho);
+}
+
+}  // namespace fsk

@@ -34,7 +34,8 @@ extern "C" {
                                  two dozen FSK_* switches);
                               5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
                                  (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers;
-                                  fsk_set_wildcards; fsk_set_center_weights) */
+                                  fsk_set_wildcards; fsk_set_center_weights;
+                                  fsk_svm_train, fsk_svm_get_model, fsk_svm_decision, fsk_svm_decision_device and fsk_svm_info) */
 
 enum {
     FSK_OK = 0,
@@ -395,6 +396,45 @@ int fsk_get_stdevs(fsk_engine* e, double* out, int32_t cap, int32_t* n);
 /* "%d:%e " text dump, one row per line, 1-based column ids: save_kernel (fastsk.cpp:223-237) */
 int fsk_save_kernel(fsk_engine* e, const char* path);
 int fsk_get_stats(fsk_engine* e, fsk_stats* out);
+
+/* ---- the SVM stage on the resident triangle: replaces FastSK::fit / FastSK::score (fastsk.cpp:239-530, LIBSVM on the host)
+ * for the sequences of ONE fsk_compute (or load / accumulate / finalize). Nothing leaves the device but three vectors.
+ *
+ * fsk_svm_train: a C-SVC (labels[t] in {-1, +1}, t < n = n_train) on the train x train part of the normalised result, solved
+ * in the dual by SMO with LIBSVM's second-order working-set selection, without shrinking: alpha = 0, G = -1; per iteration
+ * i = argmax of v_t = -y_t G_t over I_up, Gmax = v_i, Gmin = min v over I_low, stop when Gmax - Gmin <= eps; j = argmin over
+ * I_low, b_t = Gmax - v_t > 0, of -(b_t b_t) / a_t with a_t = K_ii + K_tt - 2 K_it = 2 - 2 K_it (1e-12 where that is <= 0); the
+ * two-variable step with its clips to [0, C]^2 in the order of LIBSVM's Solver::Solve (K_ii = 1); G_t += Q_it dalpha_i +
+ * Q_jt dalpha_j, Q_it = y_i y_t K_it. Ties go to the lowest index. Every K_it is the IEEE value fsk_get_train returns, every
+ * operation a single correctly rounded one, so alpha, rho and the iteration count do not depend on the form of the loop that
+ * ran (tuning svm_wg_max: up to that many rows one workgroup with the state in LDS, beyond it two launches an iteration), on
+ * tuning svm_chunk (iterations between two reads of the status record) or on the grid. rho is the mean of y_t G_t over the
+ * free support vectors (0 < alpha < C), the midpoint of its two bounds when there is none; the dual objective
+ * 1/2 sum alpha_t (G_t - 1); both summed on the host in index order, as LIBSVM does. max_iter < 0: 10,000,000; reaching
+ * max_iter is FSK_OK with fsk_svm_info.converged = 0, and so is a selection that finds no j (LIBSVM's Gmin_idx == -1; only a
+ * result whose normalised cells are not numbers, e.g. a zero diagonal, gets there): the step is not taken, the solve ends. A group handle trains on engine 0's reduced triangle.
+ * FSK_ESTATE before a finalized result; FSK_EINVAL when n != n_train, a label is not -1 or +1, only one class is present, or
+ * C or eps is not a positive finite number. The model belongs to the result: fsk_compute, fsk_load_sequences, an accumulate or
+ * a reset drops it, and the calls below then return FSK_ESTATE. */
+typedef struct fsk_svm_info {
+    int64_t iterations;      /* two-variable steps taken                                                    */
+    double gap;              /* Gmax - Gmin of the last selection                                           */
+    double objective;        /* dual objective 1/2 sum alpha_t (G_t - 1)                                    */
+    int64_t n_sv, n_bsv;     /* alpha_t > 0; alpha_t >= C                                                   */
+    int32_t converged;       /* 1: gap <= eps; 0: max_iter reached first                                    */
+    int32_t form;            /* 1: one workgroup (k_svm_wg); 2: two launches an iteration                   */
+    int64_t launches;        /* kernel launches of the solve                                                */
+    double ms;               /* host time of fsk_svm_train                                                  */
+    double reserved[4];
+} fsk_svm_info;
+int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, double eps, int64_t max_iter);
+/* alpha[n_train] (may be NULL), *rho and *info (either may be NULL) of the last fsk_svm_train */
+int fsk_svm_get_model(fsk_engine* e, double* alpha, double* rho, fsk_svm_info* info);
+/* out[r - r0] = sum_{i < n_train} alpha_i y_i K(r, i) - rho for rows r0 <= r < r1 <= N of the sequences (train rows first): the
+ * decision values of the model, read from the triangle in place. Only cells with a train column are read, so the values of
+ * test rows are whole under fsk_config.skip_test_block too. The _device form writes to DEVICE memory owned by the caller. */
+int fsk_svm_decision(fsk_engine* e, int64_t r0, int64_t r1, double* out);
+int fsk_svm_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_out);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
