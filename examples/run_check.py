@@ -3,7 +3,7 @@
 test/run_check.py:37-64): gapped-k-mer kernel on the GPU -> LinearSVC + 5-fold calibration ->
 test AUC >= 0.9 on EP300. Same user code as the reference; only the import resolves to the
 MI355X engine (this repo's `fastsk/` alias package). Then the same data through the resident pipeline
-(`fit_svm` + `decision_function_np`), which the reference does not have.
+(`cross_validate_svm` + `fit_svm` + `decision_function_np`), which the reference does not have.
 
     python examples/run_check.py --train EP300.train.fasta --test EP300.test.fasta
 """
@@ -47,17 +47,20 @@ def main():
     if auc < 0.9:  # the reference's acceptance threshold (test/run_check.py:64)
         raise SystemExit("test AUC %.4f is below 0.9" % auc)
 
-    # beside it, the resident pipeline: a C-SVC trained and applied on the triangle the compute call left on the GPU — no kernel
-    # matrix crosses to the host (fit_svm wants labels -1 / +1)
+    # beside it, the resident pipeline: a C-SVC cross-validated over 5 folds x 3 values of C in one batch, refitted at the best C
+    # and applied, all on the triangle the compute call left on the GPU — no kernel matrix crosses to the host (labels -1 / +1)
     t0 = time.time()
-    info = k.fit_svm(np.where(np.array(Ytrain) > 0, 1, -1), C=1.0, eps=1e-3)
+    labels = np.where(np.array(Ytrain) > 0, 1, -1)
+    cv = k.cross_validate_svm(labels, Cs=(0.1, 1.0, 10.0), folds=5, eps=1e-3, refit=True)
+    info = cv["refit"]
+    print("5 folds x 3 C side by side (%s, %d launches, %.1f ms): out-of-fold AUC %s, best C %g"
+          % (cv["form"], cv["launches"], cv["ms"], ", ".join("%.4f" % a for a in cv["auc"]), cv["best_C"]))
     dec = k.decision_function_np("test")
     auc_svm = roc_auc_score(Ytest, dec)
-    print("C-SVC on the resident triangle: %d iterations (%s), %d support vectors, fit + decision values in %.3f s, test AUC %.4f"
-          % (info["iterations"], info["form"], info["n_sv"], time.time() - t0, auc_svm))
+    print("C-SVC on the resident triangle at C = %g: %d iterations (%s), %d support vectors, sweep + fit + decision values in %.3f s, test AUC %.4f"
+          % (cv["best_C"], info["iterations"], info["form"], info["n_sv"], time.time() - t0, auc_svm))
     if auc_svm < 0.9:
         raise SystemExit("test AUC %.4f of the resident SVM is below 0.9" % auc_svm)
-
 
 if __name__ == "__main__":
     main()

@@ -2,7 +2,7 @@
 ``FastSK(g, m, ...).compute_kernel(Xtrain, Xtest)`` path)."""
 from .utils import FastaUtility, Vocabulary  # noqa: F401
 
-__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile"]
+__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile", "stratified_folds"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "center_profile":  # (host only, pure Python)
         from ._native import center_profile
         return center_profile
+    if name == "stratified_folds":  # (host only, pure Python)
+        from ._native import stratified_folds
+        return stratified_folds
     raise AttributeError(name)

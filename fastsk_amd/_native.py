@@ -61,8 +61,31 @@ class SvmInfo(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["converged"] = bool(d["converged"])
-        d["form"] = {1: "workgroup", 2: "two-launch"}.get(d["form"], "none")
+        d["form"] = _FORMS.get(d["form"], "none")
         return d
+
+
+_FORMS = {1: "workgroup", 2: "two-launch"}
+
+
+class SvmCvProblem(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("iterations", C.c_int64), ("gap", C.c_double), ("objective", C.c_double),
+                ("rho", C.c_double), ("C", C.c_double), ("n_sv", C.c_int64), ("n_bsv", C.c_int64), ("converged", C.c_int32),
+                ("fold", C.c_int32), ("reserved", C.c_double * 2)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["converged"] = bool(d["converged"])
+        return d
+
+
+class SvmCvScore(C.Structure):
+    _fields_ = [("C", C.c_double), ("auc", C.c_double), ("accuracy", C.c_double), ("reserved", C.c_double)]
+
+
+class SvmCvInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_folds", C.c_int32), ("n_C", C.c_int32), ("form", C.c_int32), ("reserved0", C.c_int32),
+                ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
 
 
 class MultiInfo(C.Structure):
@@ -90,7 +113,7 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
            "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
            "fsk_set_wildcards", "fsk_set_center_weights", "fsk_svm_train", "fsk_svm_get_model", "fsk_svm_decision",
-           "fsk_svm_decision_device"]
+           "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha"]
 
 
 _hip_shared = False
@@ -233,6 +256,9 @@ class Library:
             "fsk_svm_get_model": ([vp, vp, C.POINTER(C.c_double), C.POINTER(SvmInfo)], C.c_int),
             "fsk_svm_decision": ([vp, i64, i64, vp], C.c_int),
             "fsk_svm_decision_device": ([vp, i64, i64, vp], C.c_int),
+            "fsk_svm_cv": ([vp, vp, i64, vp, i32, vp, i32, C.c_double, i64], C.c_int),
+            "fsk_svm_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
+            "fsk_svm_cv_get_alpha": ([vp, i32, vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -359,6 +385,24 @@ def center_weight_array(center_weights):
     if out and out[0] == 0:
         raise ValueError("center_weights: the first entry (the centre's weight) must be at least 1")
     return np.array(out, dtype=np.uint32)
+
+
+def stratified_folds(labels, k, seed=0):
+    """Fold ids 0..k-1 for ``cross_validate_svm`` (host only), stratified by label: walk the rows in the order
+    ``np.random.Generator(np.random.PCG64(seed)).permutation(n)``; the c-th row met of a class (c = 0, 1, ...) gets fold
+    ``c % k``. Every fold so holds its share of each class to within one row. -> int32 array [n]."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1:
+        raise ValueError("stratified_folds: labels must be 1-D")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+        raise ValueError("stratified_folds: k must be an integer of at least 2")
+    fold = np.zeros(len(labels), dtype=np.int32)
+    met = {}
+    for t in np.random.Generator(np.random.PCG64(seed)).permutation(len(labels)).tolist():
+        c = met.get(labels[t].item(), 0)
+        fold[t] = c % k
+        met[labels[t].item()] = c + 1
+    return fold
 
 
 def center_profile(plateau, halflife, levels=8, floor=0):
@@ -802,6 +846,35 @@ class Engine:
         """Decision values of rows [r0, r1) of the sequences (train rows first)."""
         out = np.empty(max(r1 - r0, 0), dtype=np.float64)
         self._ck(self.lib.L.fsk_svm_decision(self.h, r0, r1, out.ctypes.data))
+        return out
+
+    def svm_cv(self, labels, fold, Cs, eps=1e-3, max_iter=-1, n_folds=None):
+        """``fsk_svm_cv``: the C-SVC cross-validated over the folds ``fold[t]`` (0..F-1; F = ``n_folds``, the largest id + 1 when None) and the values ``Cs``,
+        every (C, fold) problem solved side by side. Returns ``decision`` [n_C, n_train] (out-of-fold), ``auc`` and
+        ``accuracy`` [n_C], ``problems`` (problem ``c * F + f``: C index c, fold f held out), ``form``, ``launches``, ``ms``."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        Cs = np.ascontiguousarray(Cs, dtype=np.float64)
+        if labels.ndim != 1 or fold.ndim != 1 or Cs.ndim != 1:
+            raise ValueError("labels, fold and Cs must be 1-D")
+        if len(fold) != len(labels):
+            raise ValueError("%d fold ids for %d labels" % (len(fold), len(labels)))
+        if n_folds is None:
+            n_folds = int(fold.max()) + 1 if len(fold) else 0
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        self._ck(self.lib.L.fsk_svm_cv(self.h, ptr(labels), len(labels), ptr(fold), n_folds, ptr(Cs), len(Cs), float(eps), int(max_iter)))
+        n, P = len(labels), len(Cs) * n_folds
+        oof = np.empty((len(Cs), n), dtype=np.float64)
+        scores, problems, info = (SvmCvScore * len(Cs))(), (SvmCvProblem * P)(), SvmCvInfo()
+        self._ck(self.lib.L.fsk_svm_cv_get(self.h, oof.ctypes.data, C.addressof(scores), C.addressof(problems), C.byref(info)))
+        return {"decision": oof, "auc": np.array([s.auc for s in scores]), "accuracy": np.array([s.accuracy for s in scores]),
+                "problems": [q.as_dict() for q in problems], "form": _FORMS.get(info.form, "none"), "launches": info.launches,
+                "ms": info.ms}
+
+    def svm_cv_alpha(self, p):
+        """alpha[n_train] of problem ``p`` of the last ``svm_cv``, zero at its held-out rows."""
+        out = np.empty(self.n_train, dtype=np.float64)
+        self._ck(self.lib.L.fsk_svm_cv_get_alpha(self.h, int(p), out.ctypes.data))
         return out
 
     def stats(self):

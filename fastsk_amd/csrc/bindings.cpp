@@ -8,7 +8,8 @@
 //   - fit() / score() (LIBSVM, fastsk.cpp:239-530) are outside this path and raise
 //     NotImplementedError (they are unusable from Python in the reference as well); the SVM stage is additive instead:
 //     fit_svm(labels, C, eps, max_iter), get_dual_coef_np(), get_intercept(), decision_function_np / _dlpack(which) train
-//     and score a C-SVC on the triangle the compute call left on the device (fsk_svm_train / fsk_svm_decision);
+//     and score a C-SVC on the triangle the compute call left on the device (fsk_svm_train / fsk_svm_decision), and
+//     cross_validate_svm(labels, Cs, folds, ...) cross-validates it over folds and values of C in one batch (fsk_svm_cv);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
@@ -594,6 +595,60 @@ public:
         d["ms"] = s.ms;
         return d;
     }
+    // cross-validation of the C-SVC over folds and values of C, every problem solved side by side (fsk_svm_cv). folds: an int
+    // (fastsk_amd.stratified_folds(labels, folds, seed)) or an array of fold ids 0..F-1. best_C: the C of the highest
+    // out-of-fold AUC, the smallest of equals; refit=True then trains the model of fit_svm(labels, C=best_C, eps).
+    py::dict cross_validate_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
+                                py::array_t<double, py::array::c_style | py::array::forcecast> Cs, py::object folds, double eps,
+                                int64_t max_iter, uint64_t seed, bool refit) {
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
+        if (Cs.ndim() != 1) throw py::value_error("Cs must be 1-D");
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
+        int32_t n_folds = 0;
+        if (py::isinstance<py::int_>(folds) && !py::isinstance<py::bool_>(folds)) {
+            n_folds = folds.cast<int32_t>();
+            fold = py::module_::import("fastsk_amd._native").attr("stratified_folds")(labels, folds, seed);
+        } else {
+            fold = folds.cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+            if (fold.ndim() != 1 || fold.shape(0) != labels.shape(0)) throw py::value_error("folds must be an int or one fold id per label");
+            for (py::ssize_t t = 0; t < fold.shape(0); ++t) n_folds = std::max(n_folds, fold.data()[t] + 1);
+        }
+        const int64_t n = (int64_t)labels.shape(0);
+        const int32_t n_C = (int32_t)Cs.shape(0);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svm_cv(h_, labels.data(), n, fold.data(), n_folds, Cs.data(), n_C, eps, max_iter);
+        }
+        check(rc);
+        const int64_t P = (int64_t)n_C * n_folds;
+        py::array_t<double> oof({(py::ssize_t)n_C, (py::ssize_t)n}), auc((py::ssize_t)n_C), acc((py::ssize_t)n_C);
+        std::vector<fsk_svm_cv_score> scores((size_t)n_C);
+        std::vector<fsk_svm_cv_problem> probs((size_t)P);
+        fsk_svm_cv_info info;
+        check(fsk_svm_cv_get(h_, oof.mutable_data(), scores.data(), probs.data(), &info));
+        int32_t best = 0;
+        for (int32_t c = 0; c < n_C; ++c) {
+            auc.mutable_data()[c] = scores[(size_t)c].auc;
+            acc.mutable_data()[c] = scores[(size_t)c].accuracy;
+            const fsk_svm_cv_score &x = scores[(size_t)c], &b = scores[(size_t)best];
+            if (x.auc > b.auc || (x.auc == b.auc && x.C < b.C)) best = c;
+        }
+        py::list problems;
+        for (const fsk_svm_cv_problem& q : probs) {
+            py::dict d;
+            d["n_rows"] = q.n_rows; d["iterations"] = q.iterations; d["converged"] = (bool)q.converged; d["gap"] = q.gap;
+            d["objective"] = q.objective; d["rho"] = q.rho; d["n_sv"] = q.n_sv; d["n_bsv"] = q.n_bsv; d["C"] = q.C; d["fold"] = q.fold;
+            problems.append(d);
+        }
+        py::dict d;
+        d["decision"] = oof; d["auc"] = auc; d["accuracy"] = acc; d["problems"] = problems;
+        d["form"] = info.form == 1 ? "workgroup" : "two-launch"; d["launches"] = info.launches; d["ms"] = info.ms;
+        d["fold"] = fold; d["best_C"] = scores[(size_t)best].C;
+        if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter);
+        return d;
+    }
     py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
         py::array_t<double> out((py::ssize_t)n_train_);
         check(fsk_svm_get_model(h_, out.mutable_data(), nullptr, nullptr));
@@ -700,6 +755,8 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("set_combo_order", &FastSK::set_combo_order, py::arg("order"))
         .def("mismatch_info", &FastSK::mismatch_info)
         .def("fit_svm", &FastSK::fit_svm, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3, py::arg("max_iter") = -1)
+        .def("cross_validate_svm", &FastSK::cross_validate_svm, py::arg("labels"), py::arg("Cs") = std::vector<double>{1.0},
+             py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1, py::arg("seed") = 0, py::arg("refit") = false)
         .def("get_dual_coef_np", &FastSK::get_dual_coef_np)
         .def("get_intercept", &FastSK::get_intercept)
         .def("decision_function_np", &FastSK::decision_function_np, py::arg("which") = "test")

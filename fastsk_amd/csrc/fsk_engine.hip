@@ -293,7 +293,7 @@ int make_diag(fsk_engine* e) {
         FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_diag<u64>), dim3(blocks), dim3(256), 0, e->stream, e->d_K, e->d_diag.p, (uint32_t)e->N);
     FSK_HIP(hipStreamSynchronize(e->stream));
     e->finalized = true;
-    e->svm.valid = false;  // (a model belongs to the result it was trained on)
+    e->svm.valid = e->svm.cv.valid = false;  // (a model and a cross-validation belong to the result they were computed on)
     return FSK_OK;
 }
 

@@ -191,8 +191,31 @@ struct ShiftPlan {
 
 // The SVM stage (fsk_engine_svm.hip): the model of the last fsk_svm_train on this result and the solver's device state. A new
 // result (make_diag) drops the model; whatever makes the result stale (load, accumulate, reset: finalized = false) hides it.
+// The result of the last fsk_svm_cv on this result (host copies) and the device state of its batch of problems; valid under
+// the same rules as the model.
+struct SvmCvState {
+    bool valid = false;
+    std::vector<double> oof;                     // [n_C][n]
+    std::vector<fsk_svm_cv_score> scores;        // [n_C]
+    std::vector<fsk_svm_cv_problem> problems;    // [n_C n_folds]
+    std::vector<double> alpha;                   // the problems' slices, one after another
+    std::vector<uint32_t> idx;                   // the folds' training rows, one list after another
+    std::vector<u64> st_off, idx_off;            // [problems]: where a problem's alpha and rows start
+    fsk_svm_cv_info info{};
+    DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_rho, d_oof;
+    DevBuf<uint32_t> d_idx;
+    DevBuf<int32_t> d_fold;
+    DevBuf<signed char> d_y;
+    DevBuf<unsigned char> d_prob, d_rec;         // fsk::SvmProb [problems]; the records and candidate slots
+    void release() {
+        d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_rho.release(); d_oof.release();
+        d_idx.release(); d_fold.release(); d_y.release(); d_prob.release(); d_rec.release();
+    }
+};
+
 struct SvmState {
     bool valid = false;
+    SvmCvState cv;
     std::vector<double> alpha;       // [n_train]
     std::vector<signed char> y;      // [n_train], -1 / +1
     double rho = 0;
@@ -200,7 +223,7 @@ struct SvmState {
     DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_out;
     DevBuf<signed char> d_y;
     DevBuf<unsigned char> d_rec;     // the records the launches of a solve hand each other (fsk_kernels_svm.h)
-    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); }
+    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); cv.release(); }
     SvmState() = default;
     SvmState(const SvmState&) = delete;
     SvmState& operator=(const SvmState&) = delete;

@@ -1,7 +1,7 @@
 // fsk_engine_svm.hip — the SVM stage on the resident result triangle: fsk_svm_train, fsk_svm_get_model, fsk_svm_decision(_device)
-// of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host (fastsk.cpp:239-530), for the
-// sequences of one compute call and without the kernel matrix ever leaving the device: the engine's consumer is an SVM, and
-// the triangle it needs is 40 GB at 100,000 sequences.
+// and fsk_svm_cv, fsk_svm_cv_get(_alpha) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
+// (fastsk.cpp:239-530), for the sequences of one compute call and without the kernel matrix ever leaving the device: the
+// engine's consumer is an SVM, and the triangle it needs is 40 GB at 100,000 sequences.
 //
 // The solver (fsk_kernels_svm.h) reads the triangle in place, whichever it is — u64 counts with the raw diagonal, the fp64
 // triangle of variance mode, the folded W of the mismatch-weighted mode (u64 as well) — through normalised_cell. Two forms of
@@ -105,6 +105,32 @@ int solve(fsk_engine* e, const SrcT* K, uint32_t n, double C, double eps, int64_
                      : solve_two_launch<SrcT>(e, K, n, C, eps, max_iter, chunk, R, n_wg, status, launches);
 }
 
+// rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in element order; coef[t] = alpha_t y_t
+struct SvmFinish {
+    double rho, objective;
+    int64_t n_sv, n_bsv;
+};
+SvmFinish svm_finish(const double* alpha, const double* G, const signed char* y, uint32_t n, double C, double* coef) {
+    double ub = HUGE_VAL, lb = -HUGE_VAL, sum_free = 0.0, obj = 0.0;
+    int64_t n_free = 0, n_sv = 0, n_bsv = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const double a = alpha[t], yG = y[t] > 0 ? G[t] : -G[t];
+        if (a >= C) {
+            if (y[t] < 0) ub = std::min(ub, yG); else lb = std::max(lb, yG);
+        } else if (a <= 0.0) {
+            if (y[t] > 0) ub = std::min(ub, yG); else lb = std::max(lb, yG);
+        } else {
+            ++n_free;
+            sum_free += yG;
+        }
+        obj += a * (G[t] - 1.0);
+        n_sv += a > 0.0;
+        n_bsv += a >= C;
+        coef[t] = y[t] > 0 ? a : -a;
+    }
+    return {n_free > 0 ? sum_free / (double)n_free : (ub + lb) / 2.0, obj / 2.0, n_sv, n_bsv};
+}
+
 int model_ready(fsk_engine* e) {
     if (!e->finalized || !e->svm.valid) return e->fail(FSK_ESTATE, "no model: call fsk_svm_train on a finalized result first");
     return FSK_OK;
@@ -128,6 +154,92 @@ int decision_args(fsk_engine* e, int64_t r0, int64_t r1, const double* out) {
     if (rc) return rc;
     if (r0 < 0 || r1 > e->N || r0 > r1) return e->fail(FSK_EINVAL, "rows out of range");
     if (r1 > r0 && !out) return e->fail(FSK_EINVAL, "null output");
+    return FSK_OK;
+}
+
+// ---- the batch of fsk_svm_cv ------------------------------------------------------------------------------------------------
+// BYTES AN ITERATION OF A BATCH (the one statement; DESIGN.md and tools/bench_svm_cv.py refer to it). Problem p of n_p rows moves
+// what a single solve of n_p rows moves, and 4 n_p bytes of row numbers for every pass over its elements that reads cells.
+// Workgroup form (alpha, G and y in LDS): the cells of rows i and j, 16 n_p, and the row numbers once (kept in registers from
+// step 2 to step 4): 20 n_p. Two-launch form: 74 n_p as above and the row numbers in either launch: 82 n_p. A row of cells is
+// no longer contiguous where rows are held out, but touches no 64-byte line the full row does not. The batch moves the sum
+// over its live problems; a problem that is done costs one record a workgroup of every further launch.
+struct SvmBatch {
+    uint32_t P, max_n, max_wg, total_wg;
+    const fsk::SvmProb* probs;
+    const uint32_t* idx;
+    const signed char* y;
+    double *alpha, *G, *krow;
+    fsk::SvmRecB* rb;   // [P], read by the host in one copy
+    fsk::SvmRecA* ra;   // [P]
+    fsk::SvmCandI* ci;  // [total_wg]
+    fsk::SvmCandJ* cj;
+};
+size_t svm_batch_record_bytes(uint32_t P, uint32_t total_wg) {
+    return (size_t)P * (sizeof(fsk::SvmRecB) + sizeof(fsk::SvmRecA)) + (size_t)total_wg * (sizeof(fsk::SvmCandI) + sizeof(fsk::SvmCandJ));
+}
+static_assert(sizeof(fsk::SvmRecB) % 8 == 0 && sizeof(fsk::SvmRecA) % 8 == 0 && sizeof(fsk::SvmProb) == 32, "batch record layout");
+
+// enqueue `chunk` iterations for every problem, read the P status records in one copy, until every problem is done
+template <typename SrcT>
+int solve_batch(fsk_engine* e, const SrcT* K, const SvmBatch& B, double eps, int64_t max_iter, int form, uint32_t chunk,
+                std::vector<fsk::SvmRecB>& status, int64_t* launches) {
+    const double* diag = e->d_diag.p;
+    const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (B.max_n + 63u) & ~63u);
+    const size_t lds = fsk::svm_wg_lds(B.max_n, nt);
+    if (form == 1) {
+        if (lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svm_wg_batch needs %zu bytes of LDS for %u rows", lds, B.max_n);
+        FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svm_wg_batch<SrcT>, lds));
+    }
+    for (;;) {
+        if (form == 1) {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg_batch<SrcT>), dim3(B.P), dim3(nt), lds, e->stream, K, diag, B.probs, B.idx, B.y, eps,
+                       (long long)max_iter, chunk, B.alpha, B.G, B.rb);
+            ++*launches;
+        } else {
+            for (uint32_t c = 0; c < chunk; ++c) {
+                FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                           B.probs, B.idx, B.y, B.alpha, B.G, (const double*)B.krow, (const fsk::SvmRecB*)B.rb, B.ra, B.ci,
+                           (const fsk::SvmCandJ*)B.cj);
+                FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                           B.probs, B.idx, B.y, eps, (long long)max_iter, (const double*)B.alpha, (const double*)B.G, B.krow, B.rb,
+                           (const fsk::SvmRecA*)B.ra, (const fsk::SvmCandI*)B.ci, B.cj);
+                *launches += 2;
+            }
+        }
+        FSK_HIP(hipMemcpyAsync(status.data(), B.rb, (size_t)B.P * sizeof(fsk::SvmRecB), hipMemcpyDeviceToHost, e->stream));
+        FSK_HIP(hipStreamSynchronize(e->stream));
+        FSK_HIP(hipGetLastError());
+        bool all = true;
+        for (uint32_t p = 0; p < B.P; ++p) all = all && status[p].done;
+        if (all) return FSK_OK;
+    }
+}
+
+// (#{pos > neg} + 0.5 #{pos == neg}) / (n_pos n_neg) and the share of rows on the right side of zero
+void cv_metrics(const double* oof, const int32_t* labels, int64_t n, double* auc, double* accuracy) {
+    std::vector<double> pos, neg;
+    int64_t right = 0;
+    bool numbers = true;
+    for (int64_t t = 0; t < n; ++t) {
+        (labels[t] > 0 ? pos : neg).push_back(oof[t]);
+        right += (oof[t] > 0.0) == (labels[t] > 0);
+        numbers = numbers && !std::isnan(oof[t]);
+    }
+    *accuracy = (double)right / (double)n;
+    if (!numbers) { *auc = NAN; return; }  // (no order to count in)
+    std::sort(neg.begin(), neg.end());
+    int64_t above = 0, level = 0;
+    for (double v : pos) {
+        const auto lo = std::lower_bound(neg.begin(), neg.end(), v), hi = std::upper_bound(lo, neg.end(), v);
+        above += lo - neg.begin();
+        level += hi - lo;
+    }
+    *auc = ((double)above + 0.5 * (double)level) / (double)((int64_t)pos.size() * (int64_t)neg.size());
+}
+
+int cv_ready(fsk_engine* e) {
+    if (!e->finalized || !e->svm.cv.valid) return e->fail(FSK_ESTATE, "no cross-validation: call fsk_svm_cv on a finalized result first");
     return FSK_OK;
 }
 
@@ -186,34 +298,17 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
     FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     FSK_HIP(hipStreamSynchronize(e->stream));
 
-    // rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in index order
-    double ub = HUGE_VAL, lb = -HUGE_VAL, sum_free = 0.0, obj = 0.0;
-    int64_t n_free = 0, n_sv = 0, n_bsv = 0;
     std::vector<double> coef(nn);
-    for (uint32_t t = 0; t < nn; ++t) {
-        const double a = S.alpha[t], yG = S.y[t] > 0 ? G[t] : -G[t];
-        if (a >= C) {
-            if (S.y[t] < 0) ub = std::min(ub, yG); else lb = std::max(lb, yG);
-        } else if (a <= 0.0) {
-            if (S.y[t] > 0) ub = std::min(ub, yG); else lb = std::max(lb, yG);
-        } else {
-            ++n_free;
-            sum_free += yG;
-        }
-        obj += a * (G[t] - 1.0);
-        n_sv += a > 0.0;
-        n_bsv += a >= C;
-        coef[t] = S.y[t] > 0 ? a : -a;
-    }
-    S.rho = n_free > 0 ? sum_free / (double)n_free : (ub + lb) / 2.0;
+    const SvmFinish fin = svm_finish(S.alpha.data(), G.data(), S.y.data(), nn, C, coef.data());
+    S.rho = fin.rho;
     FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice, e->stream));
     FSK_HIP(hipStreamSynchronize(e->stream));
     S.info = fsk_svm_info{};
     S.info.iterations = status.iter;
     S.info.gap = status.gmax - status.gmin;
-    S.info.objective = obj / 2.0;
-    S.info.n_sv = n_sv;
-    S.info.n_bsv = n_bsv;
+    S.info.objective = fin.objective;
+    S.info.n_sv = fin.n_sv;
+    S.info.n_bsv = fin.n_bsv;
     S.info.converged = status.converged;
     S.info.form = form;
     S.info.launches = launches;
@@ -253,6 +348,192 @@ int fsk_svm_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* devic
     rc = launch_decision(e, r0, r1, device_out);
     if (rc) return rc;
     FSK_HIP(hipStreamSynchronize(e->stream));
+    return FSK_OK;
+}
+
+int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+               double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
+    if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
+    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);
+    if (!labels || !fold || !Cs) return e->fail(FSK_EINVAL, "null labels, fold or Cs");
+    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
+    if ((int64_t)n_C * n_folds > FSK_SVM_CV_MAX_PROBLEMS)
+        return e->fail(FSK_EINVAL, "%d folds x %d values of C are more than %d problems", n_folds, n_C, FSK_SVM_CV_MAX_PROBLEMS);
+    for (int32_t c = 0; c < n_C; ++c)
+        if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
+    const uint32_t F = (uint32_t)n_folds, nC = (uint32_t)n_C, P = F * nC, nn = (uint32_t)n;
+    std::vector<int64_t> rows(F, 0), rows_pos(F, 0);
+    int64_t n_pos = 0;
+    for (int64_t t = 0; t < n; ++t) {
+        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
+        if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
+        ++rows[fold[t]];
+        rows_pos[fold[t]] += labels[t] > 0;
+        n_pos += labels[t] > 0;
+    }
+    for (uint32_t f = 0; f < F; ++f) {
+        if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
+        const int64_t train = n - rows[f], train_pos = n_pos - rows_pos[f];
+        if (train_pos == 0 || train_pos == train) return e->fail(FSK_EINVAL, "the training rows of fold %u are of one class only", f);
+    }
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+
+    // the problems: fold f's training rows once (idx, y), a slice of state for every (C, f)
+    std::vector<uint32_t> idx;
+    std::vector<signed char> y;
+    std::vector<u64> fold_off(F), st_off(P), idx_off(P);
+    idx.reserve((size_t)(F - 1) * nn);
+    y.reserve((size_t)(F - 1) * nn);
+    for (uint32_t f = 0; f < F; ++f) {
+        fold_off[f] = idx.size();
+        for (uint32_t t = 0; t < nn; ++t)
+            if ((uint32_t)fold[t] != f) { idx.push_back(t); y.push_back((signed char)labels[t]); }
+    }
+    std::vector<fsk::SvmProb> probs(P);
+    uint32_t max_n = 0, total_wg = 0;
+    u64 total = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t f = p % F, np = (uint32_t)(n - rows[f]);
+        probs[p].C = Cs[p / F];
+        probs[p].idx_off = idx_off[p] = fold_off[f];
+        probs[p].st_off = st_off[p] = total;
+        probs[p].n = np;
+        probs[p].wg_off = total_wg;
+        total += np;
+        total_wg += (np + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
+        max_n = std::max(max_n, np);
+    }
+    const int form = (int64_t)max_n <= e->tune.svm_wg_max ? 1 : 2;
+    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
+
+    SvmCvState& S = e->svm.cv;
+    const size_t rec_bytes = svm_batch_record_bytes(P, total_wg);
+    FSK_HIP(S.d_alpha.reserve(total));
+    FSK_HIP(S.d_G.reserve(total));
+    if (form == 2) FSK_HIP(S.d_krow.reserve(total));
+    FSK_HIP(S.d_idx.reserve(idx.size()));
+    FSK_HIP(S.d_y.reserve(y.size()));
+    FSK_HIP(S.d_prob.reserve((size_t)P * sizeof(fsk::SvmProb)));
+    FSK_HIP(S.d_rec.reserve(rec_bytes));
+    FSK_HIP(S.d_coef.reserve((size_t)P * nn));
+    FSK_HIP(S.d_rho.reserve(P));
+    FSK_HIP(S.d_fold.reserve(nn));
+    FSK_HIP(S.d_oof.reserve((size_t)nC * nn));
+    S.valid = false;  // (from here on the earlier result's buffers are written)
+
+    SvmBatch B;
+    B.P = P; B.max_n = max_n; B.max_wg = (max_n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS; B.total_wg = total_wg;
+    B.probs = reinterpret_cast<const fsk::SvmProb*>(S.d_prob.p);
+    B.idx = S.d_idx.p; B.y = S.d_y.p; B.alpha = S.d_alpha.p; B.G = S.d_G.p; B.krow = S.d_krow.p;
+    B.rb = reinterpret_cast<fsk::SvmRecB*>(S.d_rec.p);
+    B.ra = reinterpret_cast<fsk::SvmRecA*>(B.rb + P);
+    B.ci = reinterpret_cast<fsk::SvmCandI*>(B.ra + P);
+    B.cj = reinterpret_cast<fsk::SvmCandJ*>(B.ci + total_wg);
+
+    std::vector<double> G(total, -1.0);
+    FSK_HIP(hipMemcpyAsync(S.d_prob.p, probs.data(), (size_t)P * sizeof(fsk::SvmProb), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_y.p, y.data(), y.size(), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_G.p, G.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_alpha.p, 0, total * sizeof(double), e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_rec.p, 0, rec_bytes, e->stream));  // iter = 0, nothing pending, nobody done
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+
+    std::vector<fsk::SvmRecB> status(P);
+    int64_t launches = 0;
+    const int rc = e->result_f64 ? solve_batch<double>(e, e->d_Kf64.p, B, eps, max_iter, form, chunk, status, &launches)
+                                 : solve_batch<u64>(e, e->d_K, B, eps, max_iter, form, chunk, status, &launches);
+    if (rc) return rc;
+    S.alpha.resize(total);
+    FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+
+    // per problem: rho and the objective in element order, the coefficients at full length
+    std::vector<double> coef((size_t)P * nn, 0.0), rho(P), part;
+    S.problems.assign(P, fsk_svm_cv_problem{});
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t np = probs[p].n;
+        part.resize(np);
+        const SvmFinish fin = svm_finish(S.alpha.data() + st_off[p], G.data() + st_off[p], y.data() + idx_off[p], np, probs[p].C, part.data());
+        for (uint32_t q = 0; q < np; ++q) coef[(size_t)p * nn + idx[idx_off[p] + q]] = part[q];
+        rho[p] = fin.rho;
+        fsk_svm_cv_problem& o = S.problems[p];
+        o.n_rows = np;
+        o.iterations = status[p].iter;
+        o.gap = status[p].gmax - status[p].gmin;
+        o.objective = fin.objective;
+        o.rho = fin.rho;
+        o.C = probs[p].C;
+        o.n_sv = fin.n_sv;
+        o.n_bsv = fin.n_bsv;
+        o.converged = status[p].converged;
+        o.fold = (int32_t)(p % F);
+    }
+    FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    {
+        const dim3 grid((nn + 3) / 4, nC);
+        const double *diag = e->d_diag.p, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = e->d_Kf64.p;
+        const int32_t* df = S.d_fold.p;
+        const u64* Ku = e->d_K;
+        double* out = S.d_oof.p;
+        if (e->result_f64)
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<double>), grid, dim3(256), 0, e->stream, Kf, diag, dc, dr, df, F, nn, out);
+        else
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<u64>), grid, dim3(256), 0, e->stream, Ku, diag, dc, dr, df, F, nn, out);
+    }
+    S.oof.resize((size_t)nC * nn);
+    FSK_HIP(hipMemcpyAsync(S.oof.data(), S.d_oof.p, S.oof.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+    S.scores.assign(nC, fsk_svm_cv_score{});
+    for (uint32_t c = 0; c < nC; ++c) {
+        S.scores[c].C = Cs[c];
+        cv_metrics(S.oof.data() + (size_t)c * nn, labels, n, &S.scores[c].auc, &S.scores[c].accuracy);
+    }
+    S.idx.swap(idx);
+    S.st_off.swap(st_off);
+    S.idx_off.swap(idx_off);
+    S.info = fsk_svm_cv_info{};
+    S.info.n = n;
+    S.info.n_folds = n_folds;
+    S.info.n_C = n_C;
+    S.info.form = form;
+    S.info.launches = launches;
+    S.info.ms = now_ms() - t0;
+    S.valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_cv_get(fsk_engine* e, double* oof, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info) {
+    if (!e) return FSK_EINVAL;
+    int rc = cv_ready(e);
+    if (rc) return rc;
+    const SvmCvState& S = e->svm.cv;
+    if (oof) memcpy(oof, S.oof.data(), S.oof.size() * sizeof(double));
+    if (scores) memcpy(scores, S.scores.data(), S.scores.size() * sizeof(fsk_svm_cv_score));
+    if (problems) memcpy(problems, S.problems.data(), S.problems.size() * sizeof(fsk_svm_cv_problem));
+    if (info) *info = S.info;
+    return FSK_OK;
+}
+
+int fsk_svm_cv_get_alpha(fsk_engine* e, int32_t p, double* alpha) {
+    if (!e) return FSK_EINVAL;
+    int rc = cv_ready(e);
+    if (rc) return rc;
+    const SvmCvState& S = e->svm.cv;
+    if (p < 0 || (size_t)p >= S.problems.size()) return e->fail(FSK_EINVAL, "problem %d of %zu", p, S.problems.size());
+    if (!alpha) return e->fail(FSK_EINVAL, "null output");
+    std::fill(alpha, alpha + S.info.n, 0.0);
+    for (int64_t q = 0; q < S.problems[p].n_rows; ++q) alpha[S.idx[S.idx_off[p] + q]] = S.alpha[S.st_off[p] + q];
     return FSK_OK;
 }
 

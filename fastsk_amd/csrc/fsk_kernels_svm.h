@@ -409,4 +409,283 @@ __global__ __launch_bounds__(256) void k_svm_decision(const SrcT* K, const doubl
     if (live && lane == 0) out[r - r0] = __dsub_rn(acc, rho);
 }
 
+// =============================================================================================
+// A BATCH OF PROBLEMS ON ONE TRIANGLE (fsk_svm_cv: folds x values of C). Problem p is n of the training rows — element e is
+// row idx[e], the list strictly ascending, so the lowest element is the lowest row and every tie falls as in the single
+// solve on the sub-matrix — with labels and C of its own. The kernels below are the three above with the problem as one
+// more grid dimension and every cell read through idx; the arithmetic of an iteration is the same to the operation. They
+// are kernels of their own, not a mode of the single-problem ones: those keep their code and their launches.
+struct SvmProb {
+    double C;
+    unsigned long long idx_off;  // idx and y of the problem start here (the problems of one fold share them)
+    unsigned long long st_off;   // alpha, G and the kept row of the problem start here
+    uint32_t n;                  // elements
+    uint32_t wg_off;             // two-launch form: the first of its ceil(n / 256) candidate slots
+};
+
+// One workgroup a problem (blockIdx.x), alpha, G and y of ITS problem in LDS laid out as in k_svm_wg for its own n; the launch's
+// LDS and thread count are those of the largest problem (n <= 8 blockDim.x for every problem of the launch). A workgroup
+// whose record says done returns before it touches anything: the alpha and G of a finished problem are written once.
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, const double* diag, const SvmProb* probs,
+                                                                 const uint32_t* idx_all, const signed char* y_all, double eps,
+                                                                 long long max_iter, uint32_t chunk, double* alpha_all, double* G_all,
+                                                                 SvmRecB* recs) {
+    FSK_DYN_SHARED(unsigned char, smem);
+    SvmRecB* rec = recs + blockIdx.x;
+    if (rec->done) return;  // (the whole workgroup: nobody writes the record before the end of the launch)
+    const SvmProb pr = probs[blockIdx.x];
+    const uint32_t tid = threadIdx.x, nt = blockDim.x, n = pr.n;
+    const double C = pr.C;
+    const uint32_t* idx = idx_all + pr.idx_off;
+    const signed char* y = y_all + pr.idx_off;
+    double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
+    const size_t n8 = ((size_t)n + 7) & ~(size_t)7;
+    double* sA = reinterpret_cast<double*>(smem);
+    double* sG = sA + n8;
+    SvmRed red;
+    red.v = sG + n8;
+    red.pv = red.v + nt;
+    red.i = reinterpret_cast<int*>(red.pv + SVM_PART);
+    red.w = red.i + nt;
+    red.pi = red.w + nt;
+    red.pw = red.pi + SVM_PART;
+    signed char* sY = reinterpret_cast<signed char*>(red.pw + SVM_PART);
+
+    for (uint32_t e = tid; e < n; e += nt) { sA[e] = alpha[e]; sG[e] = G[e]; sY[e] = y[e]; }
+    long long iter = rec->iter;
+    double gmax = rec->gmax, gmin = rec->gmin;
+    int done = 0, converged = 0;
+    __syncthreads();
+
+    for (uint32_t c = 0; c < chunk; ++c) {
+        // ---- 1. i, Gmax, Gmin
+        double vmax = -svm_inf(), vmin = svm_inf();
+        int imax = SVM_NONE, none = 0;
+        for (uint32_t e = tid; e < n; e += nt) {
+            const int ye = sY[e];
+            const double a = sA[e], v = svm_v(ye, sG[e]);
+            if (svm_in_up(ye, a, C) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
+            if (svm_in_low(ye, a, C) && v < vmin) vmin = v;
+        }
+        svm_reduce<true>(red, &vmax, &imax, &none);
+        int at = 0;
+        svm_reduce<false>(red, &vmin, &at, &none);
+        gmax = vmax; gmin = vmin;
+        if (__dsub_rn(gmax, gmin) <= eps) { done = 1; converged = 1; break; }
+        if (iter >= max_iter) { done = 1; break; }
+        const uint32_t i = (uint32_t)imax, ri = idx[i];
+        // ---- 2. j (row i and the elements' rows stay in registers for step 4)
+        double kit[SVM_WG_ITEMS];
+        uint32_t row[SVM_WG_ITEMS];
+        double obj = svm_inf();
+        int j = SVM_NONE;
+#pragma unroll
+        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
+            const uint32_t e = tid + (uint32_t)q * nt;
+            kit[q] = 0.0;
+            row[q] = 0;
+            if (e < n) {
+                row[q] = idx[e];
+                kit[q] = svm_cell(K, diag, ri, row[q]);
+                const int ye = sY[e];
+                double o;
+                if (svm_in_low(ye, sA[e], C) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
+            }
+        }
+        svm_reduce<false>(red, &obj, &j, &none);
+        if (j == SVM_NONE) { done = 1; break; }  // no candidate: as in k_svm_wg
+        // ---- 3. the step, by every thread alike
+        const uint32_t rj = idx[j];
+        const int yi = sY[i], yj = sY[j];
+        const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
+        double ai = ai0, aj = aj0;
+        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
+        __syncthreads();  // (everybody has read alpha and G of i and j)
+        // ---- 4. G, alpha
+#pragma unroll
+        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
+            const uint32_t e = tid + (uint32_t)q * nt;
+            if (e < n) {
+                sG[e] = svm_new_G(sG[e], sY[e], yi, yj, kit[q], svm_cell(K, diag, rj, row[q]), dai, daj);
+                if (e == i) sA[e] = ai;
+                if (e == (uint32_t)j) sA[e] = aj;
+            }
+        }
+        ++iter;
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < n; e += nt) { alpha[e] = sA[e]; G[e] = sG[e]; }
+    if (tid == 0) {
+        rec->iter = iter; rec->gmax = gmax; rec->gmin = gmin;
+        rec->done = done; rec->converged = converged; rec->pending = 0;
+    }
+}
+
+// The two launches with the problem in blockIdx.y: the grid is (the largest problem's workgroups, problems), and a workgroup
+// beyond its own problem's ceil(n / 256) returns at once — it writes no candidate slot and no reduction reads one of its
+// (every reduction runs over the problem's own count). Records, candidate slots, the kept row, alpha and G are the
+// problem's own, so "no launch reads a record that one of its own workgroups writes" holds problem by problem.
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i_batch(const SrcT* K, const double* diag, const SvmProb* probs,
+                                                                    const uint32_t* idx_all, const signed char* y_all, double* alpha_all,
+                                                                    double* G_all, const double* krow_all, const SvmRecB* rbs, SvmRecA* ras,
+                                                                    SvmCandI* cand_i_all, const SvmCandJ* cand_j_all) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const SvmProb pr = probs[blockIdx.y];
+    const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
+    if (blockIdx.x >= n_wg) return;
+    const double C = pr.C;
+    const uint32_t* idx = idx_all + pr.idx_off;
+    const signed char* y = y_all + pr.idx_off;
+    double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
+    const double* krow = krow_all + pr.st_off;
+    const SvmRecB* rb = rbs + blockIdx.y;
+    SvmRecA* ra = ras + blockIdx.y;
+    SvmCandI* cand_i = cand_i_all + pr.wg_off;
+    const SvmCandJ* cand_j = cand_j_all + pr.wg_off;
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (rb->done) {
+        if (blockIdx.x == 0 && tid == 0) { ra->iter = rb->iter; ra->done = 1; }
+        return;
+    }
+    long long iter = rb->iter;
+    const bool mine = t < n;
+    const int yt = mine ? (int)y[t] : 1;
+    double a = mine ? alpha[t] : 0.0, g = mine ? G[t] : 0.0;
+    if (rb->pending) {
+        double obj = svm_inf();
+        int j = SVM_NONE, w = 0;
+        for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+            const double o = cand_j[q].obj;
+            const int oj = cand_j[q].j;
+            if (svm_better_min(o, oj, obj, j)) { obj = o; j = oj; w = (int)q; }
+        }
+        svm_reduce<false>(red, &obj, &j, &w);
+        if (j == SVM_NONE) {  // no workgroup had a candidate: as in k_svm_select_i
+            if (blockIdx.x == 0 && tid == 0) { ra->iter = iter; ra->done = 2; }
+            return;
+        }
+        const SvmCandJ cj = cand_j[w];
+        const int i = rb->i, yi = rb->yi;
+        double ai = rb->ai, aj = cj.aj;
+        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
+        if (mine) {
+            g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, idx[j], idx[t]), dai, daj);
+            G[t] = g;
+            if (t == (uint32_t)i) { a = ai; alpha[t] = a; }
+            if (t == (uint32_t)j) { a = aj; alpha[t] = a; }
+        }
+        ++iter;
+    }
+    const double v = svm_v(yt, g);
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    if (mine && svm_in_up(yt, a, C)) { vmax = v; imax = (int)t; }
+    if (mine && svm_in_low(yt, a, C)) vmin = v;
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    if (tid == 0) {
+        cand_i[blockIdx.x].vmax = vmax; cand_i[blockIdx.x].vmin = vmin; cand_i[blockIdx.x].imax = imax;
+        if (blockIdx.x == 0) { ra->iter = iter; ra->done = 0; }
+    }
+}
+
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j_batch(const SrcT* K, const double* diag, const SvmProb* probs,
+                                                                    const uint32_t* idx_all, const signed char* y_all, double eps,
+                                                                    long long max_iter, const double* alpha_all, const double* G_all,
+                                                                    double* krow_all, SvmRecB* rbs, const SvmRecA* ras,
+                                                                    const SvmCandI* cand_i_all, SvmCandJ* cand_j_all) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const SvmProb pr = probs[blockIdx.y];
+    const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
+    if (blockIdx.x >= n_wg) return;
+    const double C = pr.C;
+    const uint32_t* idx = idx_all + pr.idx_off;
+    const signed char* y = y_all + pr.idx_off;
+    const double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
+    double* krow = krow_all + pr.st_off;
+    SvmRecB* rb = rbs + blockIdx.y;
+    const SvmRecA* ra = ras + blockIdx.y;
+    const SvmCandI* cand_i = cand_i_all + pr.wg_off;
+    SvmCandJ* cand_j = cand_j_all + pr.wg_off;
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (ra->done) {
+        if (ra->done == 2 && blockIdx.x == 0 && tid == 0) { rb->iter = ra->iter; rb->done = 1; rb->converged = 0; rb->pending = 0; }
+        return;
+    }
+    const long long iter = ra->iter;
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+        const double x = cand_i[q].vmax, m = cand_i[q].vmin;
+        const int xi = cand_i[q].imax;
+        if (svm_better_max(x, xi, vmax, imax)) { vmax = x; imax = xi; }
+        if (m < vmin) vmin = m;
+    }
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    const bool converged = __dsub_rn(vmax, vmin) <= eps;
+    if (converged || iter >= max_iter) {
+        if (blockIdx.x == 0 && tid == 0) {
+            rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+            rb->done = 1; rb->converged = converged ? 1 : 0; rb->pending = 0;
+        }
+        return;
+    }
+    const uint32_t i = (uint32_t)imax;
+    double obj = svm_inf(), kit = 0.0, a = 0.0, g = 0.0;
+    int j = SVM_NONE, yt = 1;
+    if (t < n) {
+        kit = svm_cell(K, diag, idx[i], idx[t]);
+        krow[t] = kit;
+        yt = (int)y[t]; a = alpha[t]; g = G[t];
+        double o;
+        if (svm_in_low(yt, a, C) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
+    }
+    svm_reduce<false>(red, &obj, &j, &none);
+    if (j == SVM_NONE) {
+        if (tid == 0) { cand_j[blockIdx.x].obj = svm_inf(); cand_j[blockIdx.x].j = SVM_NONE; }
+    } else if (t == (uint32_t)j) {
+        SvmCandJ c;
+        c.obj = obj; c.aj = a; c.Gj = g; c.Kij = kit; c.j = j; c.yj = yt;
+        cand_j[blockIdx.x] = c;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+        rb->ai = alpha[i]; rb->Gi = G[i]; rb->i = (int)i; rb->yi = (int)y[i];
+        rb->done = 0; rb->converged = 0; rb->pending = 1;
+    }
+}
+
+// OUT-OF-FOLD DECISION VALUES: for the value of C blockIdx.y and training row t, out[c][t] = sum_i coef_p[i] K(t, i) - rho_p
+// with p = c n_folds + fold[t], the one problem of that C which did not train on t. coef_p is alpha y at full length
+// (n_train, zero at the problem's held-out rows), so the sum and its order are those of k_svm_decision: one wave a row, a
+// lane its columns lane, lane + 64, ... in order, zero coefficients skipped, then the xor shuffles. Train x train cells only.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_decision_oof(const SrcT* K, const double* diag, const double* coef, const double* rho,
+                                                          const int32_t* fold, uint32_t n_folds, uint32_t n_train, double* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const bool live = t < n_train;
+    const uint32_t p = blockIdx.y * n_folds + (live ? (uint32_t)fold[t] : 0u);
+    const double* cp = coef + (size_t)p * n_train;
+    double acc = 0.0;
+    if (live)
+        for (uint32_t i = lane; i < n_train; i += 64u) {
+            const double c = cp[i];
+            if (c != 0.0) acc = __dadd_rn(acc, __dmul_rn(c, svm_cell(K, diag, t, i)));
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
+    if (live && lane == 0) out[(size_t)blockIdx.y * n_train + t] = __dsub_rn(acc, rho[p]);
+}
+
 }  // namespace fsk

@@ -35,7 +35,8 @@ extern "C" {
                               5: fsk_seed_order; fsk_set_seed draws the reference's own std::shuffle order
                                  (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers;
                                   fsk_set_wildcards; fsk_set_center_weights;
-                                  fsk_svm_train, fsk_svm_get_model, fsk_svm_decision, fsk_svm_decision_device and fsk_svm_info) */
+                                  fsk_svm_train, fsk_svm_get_model, fsk_svm_decision, fsk_svm_decision_device and fsk_svm_info;
+                                  fsk_svm_cv, fsk_svm_cv_get, fsk_svm_cv_get_alpha and their three structs) */
 
 enum {
     FSK_OK = 0,
@@ -435,6 +436,53 @@ int fsk_svm_get_model(fsk_engine* e, double* alpha, double* rho, fsk_svm_info* i
  * test rows are whole under fsk_config.skip_test_block too. The _device form writes to DEVICE memory owned by the caller. */
 int fsk_svm_decision(fsk_engine* e, int64_t r0, int64_t r1, double* out);
 int fsk_svm_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_out);
+
+/* ---- cross-validation of the C-SVC over folds and a grid of C, every problem solved side by side on the resident triangle.
+ *
+ * fsk_svm_cv: fold[t] in [0, n_folds) for the n = n_train training rows; problem p = c n_folds + f trains, at Cs[c], on the rows
+ * with fold[t] != f (in row order) — fsk_svm_train's algorithm on that sub-matrix, to the bit: alpha, rho, the objective, the
+ * gap and the iteration count of a problem are those of a single solve of its rows, whichever form ran (one workgroup a
+ * problem with its state in LDS while the largest training set has at most svm_wg_max rows, two launches an iteration over
+ * (workgroups, problems) beyond; svm_chunk iterations between two reads of the problems' status records). Then the
+ * out-of-fold decision values oof[c n + t] = sum_i alpha_i y_i K(t, i) - rho of problem c n_folds + fold[t], summed as
+ * fsk_svm_decision sums, and from them on the host, per value of C,
+ *   auc = (#{(pos, neg): oof_pos > oof_neg} + 0.5 #{oof_pos == oof_neg}) / (n_pos n_neg)   (integer counts; one multiply,
+ *         one add, one divide in double),
+ *   accuracy = the share of rows with (oof > 0) == (label > 0)   (LIBSVM's sign rule).
+ * max_iter as for fsk_svm_train, for every problem alike. FSK_ESTATE before a finalized result. FSK_EINVAL, the message
+ * naming the row, fold or C: n != n_train, a label that is not -1 or +1, a fold id out of range, a fold without rows, a fold
+ * whose training rows are of one class, n_folds < 2, n_C < 1, a C or eps that is not a positive finite number, more than
+ * FSK_SVM_CV_MAX_PROBLEMS problems. A refused call leaves an earlier result as it was. The result belongs to the finalized
+ * kernel as the model does (a new or stale kernel: FSK_ESTATE); it neither needs nor touches the model of fsk_svm_train. A
+ * group handle works on engine 0's reduced triangle. */
+#define FSK_SVM_CV_MAX_PROBLEMS 65535
+typedef struct fsk_svm_cv_problem {
+    int64_t n_rows;          /* training rows of the problem                                                */
+    int64_t iterations;
+    double gap, objective, rho, C;
+    int64_t n_sv, n_bsv;
+    int32_t converged, fold; /* fold: the one held out                                                      */
+    double reserved[2];
+} fsk_svm_cv_problem;
+typedef struct fsk_svm_cv_score {
+    double C, auc, accuracy;
+    double reserved;
+} fsk_svm_cv_score;
+typedef struct fsk_svm_cv_info {
+    int64_t n;               /* training rows                                                               */
+    int32_t n_folds, n_C;
+    int32_t form;            /* 1: one workgroup a problem (k_svm_wg_batch); 2: two launches an iteration   */
+    int32_t reserved0;
+    int64_t launches;        /* kernel launches of the solves (the out-of-fold launch not counted)          */
+    double ms;               /* host time of fsk_svm_cv                                                     */
+    double reserved[4];
+} fsk_svm_cv_info;
+int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+               double eps, int64_t max_iter);
+/* oof[n_C n], scores[n_C], problems[n_C n_folds], *info of the last fsk_svm_cv: every one may be NULL */
+int fsk_svm_cv_get(fsk_engine* e, double* oof, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info);
+/* alpha[n_train] of problem p, zero at its held-out rows */
+int fsk_svm_cv_get_alpha(fsk_engine* e, int32_t p, double* alpha);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
