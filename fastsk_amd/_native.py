@@ -67,6 +67,18 @@ class SvmInfo(C.Structure):
 
 _FORMS = {1: "workgroup", 2: "two-launch"}
 
+SVM_KERNEL_RESULT, SVM_KERNEL_ROWS = 0, 1   # fsk_svm_set_kernel
+_SVM_KERNELS = {"fastsk": SVM_KERNEL_RESULT, "result": SVM_KERNEL_RESULT, "linear": SVM_KERNEL_ROWS, "rows": SVM_KERNEL_ROWS}
+
+
+class RowsInfo(C.Structure):
+    _fields_ = [("n_train", C.c_int64), ("n_seq", C.c_int64), ("tile", C.c_int32), ("panel", C.c_int32), ("tiles", C.c_int64),
+                ("builds", C.c_int64), ("scratch_bytes", C.c_int64), ("resident_bytes", C.c_int64), ("ms_scratch", C.c_double),
+                ("ms_product", C.c_double), ("reserved", C.c_double * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
 
 class SvmCvProblem(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("iterations", C.c_int64), ("gap", C.c_double), ("objective", C.c_double),
@@ -113,7 +125,8 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_get_triangle_device", "fsk_alloc_triangle_device", "fsk_set_tuning", "fsk_get_tuning", "fsk_tuning_keys", "fsk_seed_order",
            "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
            "fsk_set_wildcards", "fsk_set_center_weights", "fsk_svm_train", "fsk_svm_get_model", "fsk_svm_decision",
-           "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha"]
+           "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha", "fsk_rows_build", "fsk_rows_get_block",
+           "fsk_rows_get_block_device", "fsk_rows_get_info", "fsk_svm_set_kernel", "fsk_svm_get_kernel"]
 
 
 _hip_shared = False
@@ -259,6 +272,12 @@ class Library:
             "fsk_svm_cv": ([vp, vp, i64, vp, i32, vp, i32, C.c_double, i64], C.c_int),
             "fsk_svm_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
             "fsk_svm_cv_get_alpha": ([vp, i32, vp], C.c_int),
+            "fsk_rows_build": ([vp], C.c_int),
+            "fsk_rows_get_block": ([vp, i64, i64, i64, i64, i32, vp], C.c_int),
+            "fsk_rows_get_block_device": ([vp, i64, i64, i64, i64, i32, vp], C.c_int),
+            "fsk_rows_get_info": ([vp, C.POINTER(RowsInfo)], C.c_int),
+            "fsk_svm_set_kernel": ([vp, i32], C.c_int),
+            "fsk_svm_get_kernel": ([vp, C.POINTER(i32)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             fn = getattr(L, name)
@@ -870,6 +889,37 @@ class Engine:
         return {"decision": oof, "auc": np.array([s.auc for s in scores]), "accuracy": np.array([s.accuracy for s in scores]),
                 "problems": [q.as_dict() for q in problems], "form": _FORMS.get(info.form, "none"), "launches": info.launches,
                 "ms": info.ms}
+
+    # ---- the rows kernel: L(r, c) = <K(r, train), K(c, train)> of the finalized result, K2 its cosine normalisation
+    def rows_build(self):
+        """``fsk_rows_build``: build the rows kernel of the finalized result (nothing when it is there). Returns ``rows_info()``."""
+        self._ck(self.lib.L.fsk_rows_build(self.h))
+        return self.rows_info()
+
+    def rows_block(self, i0, i1, j0, j1, raw=False):
+        """Cells [i0, i1) x [j0, j1) of the rows kernel, either order of (r, c): L when ``raw``, else K2. Does not build."""
+        out = np.empty((max(i1 - i0, 0), max(j1 - j0, 0)), dtype=np.float64)
+        self._ck(self.lib.L.fsk_rows_get_block(self.h, i0, i1, j0, j1, int(bool(raw)), out.ctypes.data))
+        return out
+
+    def rows_info(self):
+        info = RowsInfo()
+        self._ck(self.lib.L.fsk_rows_get_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def svm_set_kernel(self, kind):
+        """What ``svm_train`` / ``svm_cv`` solve on: ``SVM_KERNEL_RESULT`` / "fastsk" (the default) or ``SVM_KERNEL_ROWS`` /
+        "linear". A change drops the model and the cross-validation result."""
+        if isinstance(kind, str):
+            if kind not in _SVM_KERNELS:
+                raise ValueError("kernel kind %r: one of %s" % (kind, sorted(_SVM_KERNELS)))
+            kind = _SVM_KERNELS[kind]
+        self._ck(self.lib.L.fsk_svm_set_kernel(self.h, int(kind)))
+
+    def svm_get_kernel(self):
+        v = C.c_int32(0)
+        self._ck(self.lib.L.fsk_svm_get_kernel(self.h, C.byref(v)))
+        return int(v.value)
 
     def svm_cv_alpha(self, p):
         """alpha[n_train] of problem ``p`` of the last ``svm_cv``, zero at its held-out rows."""

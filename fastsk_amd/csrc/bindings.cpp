@@ -10,6 +10,8 @@
 //     fit_svm(labels, C, eps, max_iter), get_dual_coef_np(), get_intercept(), decision_function_np / _dlpack(which) train
 //     and score a C-SVC on the triangle the compute call left on the device (fsk_svm_train / fsk_svm_decision), and
 //     cross_validate_svm(labels, Cs, folds, ...) cross-validates it over folds and values of C in one batch (fsk_svm_cv);
+//     both take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
+//     the kernel, through the rows kernel (fsk_rows_build; get_rows_kernel_block_np, rows_kernel_info);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
 //     the reference parallelises the same call over t host threads (fastsk_kernel.cpp:54-93).
@@ -577,9 +579,20 @@ public:
     }
     // ---- additive: the SVM stage on the resident triangle (fsk_svm_train / fsk_svm_decision). fit() / score() stay the
     // reference's stubs; these train and score on the result compute_kernel / compute_train has left on the device.
-    py::dict fit_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter) {
+    // kernel_type: "fastsk" — the gapped-k-mer kernel itself; "linear" — its rows as feature vectors, the reference's default
+    // (fastsk.cpp:239-291) through the rows kernel K2 (fsk_rows_build); "rbf" is not built
+    static int32_t parse_kernel_type(const std::string& kt) {
+        if (kt == "fastsk") return FSK_SVM_KERNEL_RESULT;
+        if (kt == "linear") return FSK_SVM_KERNEL_ROWS;
+        if (kt == "rbf") throw py::value_error("kernel_type=\"rbf\" is not built: a device exp cannot be restated bit for bit; use \"fastsk\" or \"linear\"");
+        throw py::value_error("kernel_type must be \"fastsk\" or \"linear\"");
+    }
+    py::dict fit_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter,
+                     const std::string& kernel_type) {
+        const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
+        check(fsk_svm_set_kernel(h_, kind));
         int rc;
         {
             py::gil_scoped_release nogil;
@@ -592,7 +605,30 @@ public:
         py::dict d;
         d["iterations"] = s.iterations; d["gap"] = s.gap; d["objective"] = s.objective; d["n_sv"] = s.n_sv; d["n_bsv"] = s.n_bsv;
         d["converged"] = (bool)s.converged; d["form"] = s.form == 1 ? "workgroup" : "two-launch"; d["launches"] = s.launches;
-        d["ms"] = s.ms;
+        d["ms"] = s.ms; d["kernel_type"] = kernel_type;
+        return d;
+    }
+    // cells [i0, i1) x [j0, j1) of the rows kernel (built if it is not there): L when raw, else K2. Only cells of the result
+    // with a train column are read: nothing here asks for the test x test block.
+    py::array_t<double> get_rows_kernel_block_np(int64_t i0, int64_t i1, int64_t j0, int64_t j1, bool raw) {
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (i1 < i0 || j1 < j0) throw py::value_error("empty block");
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_rows_build(h_);
+        }
+        check(rc);
+        py::array_t<double> out({(py::ssize_t)(i1 - i0), (py::ssize_t)(j1 - j0)});
+        check(fsk_rows_get_block(h_, i0, i1, j0, j1, raw ? 1 : 0, out.mutable_data()));
+        return out;
+    }
+    py::dict rows_kernel_info() const {
+        fsk_rows_info s;
+        check(fsk_rows_get_info(h_, &s));
+        py::dict d;
+        d["n_train"] = s.n_train; d["n_seq"] = s.n_seq; d["tile"] = s.tile; d["panel"] = s.panel; d["tiles"] = s.tiles; d["builds"] = s.builds;
+        d["scratch_bytes"] = s.scratch_bytes; d["resident_bytes"] = s.resident_bytes; d["ms_scratch"] = s.ms_scratch; d["ms_product"] = s.ms_product;
         return d;
     }
     // cross-validation of the C-SVC over folds and values of C, every problem solved side by side (fsk_svm_cv). folds: an int
@@ -600,7 +636,8 @@ public:
     // out-of-fold AUC, the smallest of equals; refit=True then trains the model of fit_svm(labels, C=best_C, eps).
     py::dict cross_validate_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
                                 py::array_t<double, py::array::c_style | py::array::forcecast> Cs, py::object folds, double eps,
-                                int64_t max_iter, uint64_t seed, bool refit) {
+                                int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type) {
+        const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
         if (Cs.ndim() != 1) throw py::value_error("Cs must be 1-D");
@@ -616,6 +653,7 @@ public:
         }
         const int64_t n = (int64_t)labels.shape(0);
         const int32_t n_C = (int32_t)Cs.shape(0);
+        check(fsk_svm_set_kernel(h_, kind));
         int rc;
         {
             py::gil_scoped_release nogil;
@@ -645,8 +683,8 @@ public:
         py::dict d;
         d["decision"] = oof; d["auc"] = auc; d["accuracy"] = acc; d["problems"] = problems;
         d["form"] = info.form == 1 ? "workgroup" : "two-launch"; d["launches"] = info.launches; d["ms"] = info.ms;
-        d["fold"] = fold; d["best_C"] = scores[(size_t)best].C;
-        if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter);
+        d["fold"] = fold; d["best_C"] = scores[(size_t)best].C; d["kernel_type"] = kernel_type;
+        if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter, kernel_type);
         return d;
     }
     py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
@@ -754,9 +792,14 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("get_triangle_dlpack", &FastSK::get_triangle_dlpack)
         .def("set_combo_order", &FastSK::set_combo_order, py::arg("order"))
         .def("mismatch_info", &FastSK::mismatch_info)
-        .def("fit_svm", &FastSK::fit_svm, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3, py::arg("max_iter") = -1)
+        .def("fit_svm", &FastSK::fit_svm, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3, py::arg("max_iter") = -1,
+             py::arg("kernel_type") = "fastsk")
+        .def("get_rows_kernel_block_np", &FastSK::get_rows_kernel_block_np, py::arg("i0"), py::arg("i1"), py::arg("j0"), py::arg("j1"),
+             py::arg("raw") = false)
+        .def("rows_kernel_info", &FastSK::rows_kernel_info)
         .def("cross_validate_svm", &FastSK::cross_validate_svm, py::arg("labels"), py::arg("Cs") = std::vector<double>{1.0},
-             py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1, py::arg("seed") = 0, py::arg("refit") = false)
+             py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1, py::arg("seed") = 0, py::arg("refit") = false,
+             py::arg("kernel_type") = "fastsk")
         .def("get_dual_coef_np", &FastSK::get_dual_coef_np)
         .def("get_intercept", &FastSK::get_intercept)
         .def("decision_function_np", &FastSK::decision_function_np, py::arg("which") = "test")

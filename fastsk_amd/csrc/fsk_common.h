@@ -125,6 +125,18 @@ __device__ __forceinline__ T block_excl_scan(T v, T* tmp, T* total) {
     return base + x - v;
 }
 
+// the rows kernel (fsk_kernels_rows.h): tile edge T and panel depth P of k_rows_syrk, compile-time (the host reports them as
+// the read-only tuning keys rows_tile / rows_panel)
+#ifndef FSK_ROWS_TILE
+#define FSK_ROWS_TILE 64
+#endif
+#define FSK_ROWS_PANEL 16
+// waves a SIMD the register allocation of k_rows_syrk is held to (the second launch bound). Measured at N = n = 8000
+// (profiles/rows_kernel.json): T = 64 at 2 / 3 / 4 waves 48.9 / 36.9 / 50.7 ms, T = 128 at 1 / 2 waves 58.1 / 103.8 ms.
+#ifndef FSK_ROWS_WAVES
+#define FSK_ROWS_WAVES (FSK_ROWS_TILE == 128 ? 1 : 3)
+#endif
+
 constexpr int PANEL = 64;        // sequences per count panel (= one wave of lanes)
 constexpr int TILE = 128;        // K tile edge (2 panels)
 constexpr int STAGE_KQ = 32;     // key quads (4 keys = one dword of u8 counts) per LDS stage

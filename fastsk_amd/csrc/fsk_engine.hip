@@ -294,6 +294,7 @@ int make_diag(fsk_engine* e) {
     FSK_HIP(hipStreamSynchronize(e->stream));
     e->finalized = true;
     e->svm.valid = e->svm.cv.valid = false;  // (a model and a cross-validation belong to the result they were computed on)
+    e->rows.drop();                          // (and so does the rows kernel)
     return FSK_OK;
 }
 
@@ -1414,8 +1415,11 @@ int fsk_get_test(fsk_engine* e, double* out) {
     return fetch_block(e, e->n_train, e->N, 0, e->n_train, out);
 }
 
-// cells [c0, c0 + cnt) of the normalised triangle into device memory at `dst` (dst[0] = cell c0)
-static int launch_triangle(fsk_engine* e, u64 c0, u64 cnt, double* dst) {
+}  // extern "C"
+
+// cells [c0, c0 + cnt) of the normalised triangle into device memory at `dst` (dst[0] = cell c0); fsk_engine_rows.hip fills
+// its scratch with it
+int fsk_detail::launch_triangle(fsk_engine* e, u64 c0, u64 cnt, double* dst) {
     const u64 per_block = (u64)256 * fsk::TR_ITEMS;
     const uint32_t blocks = (uint32_t)((cnt + per_block - 1) / per_block);
     if (e->result_f64)
@@ -1424,6 +1428,8 @@ static int launch_triangle(fsk_engine* e, u64 c0, u64 cnt, double* dst) {
         FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_triangle<u64>), dim3(blocks), dim3(256), 0, e->stream, e->d_K, e->d_diag.p, c0, cnt, dst);
     return FSK_OK;
 }
+
+extern "C" {
 
 int fsk_get_triangle(fsk_engine* e, double* out) {
     if (!e) return FSK_EINVAL;

@@ -129,6 +129,8 @@ using fsk_detail::DevBuf;
     X(deadline_ms, 120000, -1, 86400000, "fsk_create_multi: the fail-fast bound when fsk_config.deadline_ms is 0 (negative: none)")   \
     X(svm_wg_max, 8192, 0, 8192, "fsk_svm_train: up to this many training rows the solver is one workgroup with alpha, G and y in LDS (k_svm_wg); beyond, two launches an iteration (k_svm_select_i / k_svm_select_j); 0 = always those") \
     X(svm_chunk, 256, 1, 65536, "fsk_svm_train: iterations enqueued between two reads of the solver's status record (k_svm_wg: iterations a launch)") \
+    X(rows_tile, FSK_ROWS_TILE, FSK_ROWS_TILE, FSK_ROWS_TILE, "fsk_rows_build, read-only: the edge T of k_rows_syrk's tile of the rows kernel (compiled in)") \
+    X(rows_panel, FSK_ROWS_PANEL, FSK_ROWS_PANEL, FSK_ROWS_PANEL, "fsk_rows_build, read-only: the consecutive train columns P a panel of k_rows_syrk stages in LDS (compiled in)") \
     FSK_TUNING_TEST_KEYS(X)
 // keys that exist in test builds only (-DFSK_TEST_HOOKS: the CPU emulation and tests/hooks' library; never the product):
 // engine fault_rank of a group is late by fault_ms before the collective of band fault_band — fault_kind 1: its worker
@@ -219,6 +221,7 @@ struct SvmState {
     std::vector<double> alpha;       // [n_train]
     std::vector<signed char> y;      // [n_train], -1 / +1
     double rho = 0;
+    int kernel = 0;                  // FSK_SVM_KERNEL_*: what fsk_svm_train / fsk_svm_cv solve on (fsk_svm_set_kernel)
     fsk_svm_info info{};
     DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_out;
     DevBuf<signed char> d_y;
@@ -228,6 +231,20 @@ struct SvmState {
     SvmState(const SvmState&) = delete;
     SvmState& operator=(const SvmState&) = delete;
     ~SvmState() { release(); }
+};
+
+// The rows kernel (fsk_engine_rows.hip): L(r, c) = <K(r, train), K(c, train)> of the finalized result as a packed fp64
+// triangle with its raw diagonal — the layout the SVM kernels read. It belongs to the result like the model: make_diag drops
+// it (and frees it: it is as large as the counts), whatever makes the result stale hides it.
+struct RowsState {
+    bool valid = false;
+    DevBuf<double> d_L, d_diag;
+    fsk_rows_info info{};
+    void drop() { valid = false; d_L.release(); d_diag.release(); }
+    RowsState() = default;
+    RowsState(const RowsState&) = delete;
+    RowsState& operator=(const RowsState&) = delete;
+    ~RowsState() { drop(); }
 };
 
 struct fsk_engine {
@@ -423,6 +440,7 @@ struct fsk_engine {
 
     fsk_stats st{};
     SvmState svm;
+    RowsState rows;
 
     int fail(int code, const char* fmt, ...) {
         char buf[512];
@@ -529,6 +547,10 @@ bool lazy_zero_possible(const fsk_engine* e);
 int do_accumulate(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_t row0 = 0, int64_t row1 = -1, u64 slot_stride = 0,
                   int defer = -1);
 int make_diag(fsk_engine* e);
+// cells [c0, c0 + cnt) of the normalised triangle into device memory at dst (the streaming pass of fsk_get_triangle_device)
+int launch_triangle(fsk_engine* e, u64 c0, u64 cnt, double* dst);
+// fsk_engine_rows.hip: the rows kernel of the result at hand, built if it is not there
+int rows_build(fsk_engine* e);
 void default_order(fsk_engine* e);
 void libstdcxx_shuffle_order(uint64_t seed, int64_t n, int32_t* out);
 

@@ -50,11 +50,10 @@ static_assert(sizeof(fsk::SvmRecB) <= 256 && sizeof(fsk::SvmRecA) <= 256 && size
 
 // one workgroup, alpha / G / y in LDS: launches of up to `chunk` iterations until the status record says done
 template <typename SrcT>
-int solve_wg(fsk_engine* e, const SrcT* K, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
+int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
              fsk::SvmRecB* status, int64_t* launches) {
     double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p;  // (plain pointers: a launch takes its arguments by value)
     const signed char* y = e->svm.d_y.p;
-    const double* diag = e->d_diag.p;
     fsk::SvmRecB* rb = R.rb;
     const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (n + 63u) & ~63u);
     const size_t lds = fsk::svm_wg_lds(n, nt);
@@ -73,11 +72,10 @@ int solve_wg(fsk_engine* e, const SrcT* K, uint32_t n, double C, double eps, int
 
 // two launches an iteration: `chunk` (A, B) pairs between two reads of the status record
 template <typename SrcT>
-int solve_two_launch(fsk_engine* e, const SrcT* K, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
+int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
                      uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
     double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p, *krow = e->svm.d_krow.p;  // (plain pointers: a launch takes its arguments by value)
     const signed char* y = e->svm.d_y.p;
-    const double* diag = e->d_diag.p;
     fsk::SvmRecB* rb = R.rb;
     fsk::SvmRecA* ra = R.ra;
     fsk::SvmCandI* ci = R.ci;
@@ -99,10 +97,10 @@ int solve_two_launch(fsk_engine* e, const SrcT* K, uint32_t n, double C, double 
 }
 
 template <typename SrcT>
-int solve(fsk_engine* e, const SrcT* K, uint32_t n, double C, double eps, int64_t max_iter, int form, uint32_t chunk, const SvmRecords& R,
+int solve(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, int form, uint32_t chunk, const SvmRecords& R,
           uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
-    return form == 1 ? solve_wg<SrcT>(e, K, n, C, eps, max_iter, chunk, R, status, launches)
-                     : solve_two_launch<SrcT>(e, K, n, C, eps, max_iter, chunk, R, n_wg, status, launches);
+    return form == 1 ? solve_wg<SrcT>(e, K, diag, n, C, eps, max_iter, chunk, R, status, launches)
+                     : solve_two_launch<SrcT>(e, K, diag, n, C, eps, max_iter, chunk, R, n_wg, status, launches);
 }
 
 // rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in element order; coef[t] = alpha_t y_t
@@ -131,6 +129,27 @@ SvmFinish svm_finish(const double* alpha, const double* G, const signed char* y,
     return {n_free > 0 ? sum_free / (double)n_free : (ub + lb) / 2.0, obj / 2.0, n_sv, n_bsv};
 }
 
+// THE place that chooses what the stage solves on and reads (fsk_svm_set_kernel): the normalised result — u64 counts or the
+// fp64 triangle, with the raw diagonal of make_diag — or the rows kernel, an fp64 triangle with its own raw diagonal
+// (fsk_engine_rows.hip), which the <double> instantiations read through the same normalised_cell. build: a train or a
+// cross-validation builds the rows kernel when it is not there; a decision needs a model, and a model of that kind has it.
+struct SvmSource {
+    bool f64;
+    const u64* Ku;
+    const double* Kf;
+    const double* diag;
+};
+int svm_source(fsk_engine* e, bool build, SvmSource* s) {
+    if (e->svm.kernel == FSK_SVM_KERNEL_ROWS) {
+        if (build) { int rc = rows_build(e); if (rc) return rc; }
+        else if (!e->rows.valid) return e->fail(FSK_ESTATE, "no rows kernel: the model's kernel is gone");
+        *s = SvmSource{true, nullptr, e->rows.d_L.p, e->rows.d_diag.p};
+    } else {
+        *s = SvmSource{e->result_f64, e->d_K, e->d_Kf64.p, e->d_diag.p};
+    }
+    return FSK_OK;
+}
+
 int model_ready(fsk_engine* e) {
     if (!e->finalized || !e->svm.valid) return e->fail(FSK_ESTATE, "no model: call fsk_svm_train on a finalized result first");
     return FSK_OK;
@@ -139,10 +158,12 @@ int model_ready(fsk_engine* e) {
 // the rows [r0, r1) into device memory at `dst`
 int launch_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dst) {
     const uint32_t blocks = (uint32_t)((r1 - r0 + 3) / 4), n_train = (uint32_t)e->n_train, a = (uint32_t)r0, b = (uint32_t)r1;
-    const double *diag = e->d_diag.p, *coef = e->svm.d_coef.p, *Kf = e->d_Kf64.p;
-    const u64* Ku = e->d_K;
+    SvmSource src;
+    { int rc = svm_source(e, false, &src); if (rc) return rc; }
+    const double *diag = src.diag, *coef = e->svm.d_coef.p, *Kf = src.Kf;
+    const u64* Ku = src.Ku;
     const double rho = e->svm.rho;
-    if (e->result_f64)
+    if (src.f64)
         FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision<double>), dim3(blocks), dim3(256), 0, e->stream, Kf, diag, coef, n_train, a, b, rho, dst);
     else
         FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision<u64>), dim3(blocks), dim3(256), 0, e->stream, Ku, diag, coef, n_train, a, b, rho, dst);
@@ -182,9 +203,8 @@ static_assert(sizeof(fsk::SvmRecB) % 8 == 0 && sizeof(fsk::SvmRecA) % 8 == 0 && 
 
 // enqueue `chunk` iterations for every problem, read the P status records in one copy, until every problem is done
 template <typename SrcT>
-int solve_batch(fsk_engine* e, const SrcT* K, const SvmBatch& B, double eps, int64_t max_iter, int form, uint32_t chunk,
+int solve_batch(fsk_engine* e, const SrcT* K, const double* diag, const SvmBatch& B, double eps, int64_t max_iter, int form, uint32_t chunk,
                 std::vector<fsk::SvmRecB>& status, int64_t* launches) {
-    const double* diag = e->d_diag.p;
     const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (B.max_n + 63u) & ~63u);
     const size_t lds = fsk::svm_wg_lds(B.max_n, nt);
     if (form == 1) {
@@ -264,6 +284,8 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
     if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
     FSK_ON_DEVICE(e);
     { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
 
     SvmState& S = e->svm;
     S.valid = false;
@@ -291,8 +313,8 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
 
     fsk::SvmRecB status{};
     int64_t launches = 0;
-    const int rc = e->result_f64 ? solve<double>(e, e->d_Kf64.p, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches)
-                                 : solve<u64>(e, e->d_K, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches);
+    const int rc = src.f64 ? solve<double>(e, src.Kf, src.diag, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches)
+                           : solve<u64>(e, src.Ku, src.diag, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches);
     if (rc) return rc;
     FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -383,6 +405,8 @@ int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* f
     if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
     FSK_ON_DEVICE(e);
     { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
 
     // the problems: fold f's training rows once (idx, y), a slice of state for every (C, f)
     std::vector<uint32_t> idx;
@@ -448,8 +472,8 @@ int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* f
 
     std::vector<fsk::SvmRecB> status(P);
     int64_t launches = 0;
-    const int rc = e->result_f64 ? solve_batch<double>(e, e->d_Kf64.p, B, eps, max_iter, form, chunk, status, &launches)
-                                 : solve_batch<u64>(e, e->d_K, B, eps, max_iter, form, chunk, status, &launches);
+    const int rc = src.f64 ? solve_batch<double>(e, src.Kf, src.diag, B, eps, max_iter, form, chunk, status, &launches)
+                           : solve_batch<u64>(e, src.Ku, src.diag, B, eps, max_iter, form, chunk, status, &launches);
     if (rc) return rc;
     S.alpha.resize(total);
     FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -481,11 +505,11 @@ int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* f
     FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
     {
         const dim3 grid((nn + 3) / 4, nC);
-        const double *diag = e->d_diag.p, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = e->d_Kf64.p;
+        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = src.Kf;
         const int32_t* df = S.d_fold.p;
-        const u64* Ku = e->d_K;
+        const u64* Ku = src.Ku;
         double* out = S.d_oof.p;
-        if (e->result_f64)
+        if (src.f64)
             FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<double>), grid, dim3(256), 0, e->stream, Kf, diag, dc, dr, df, F, nn, out);
         else
             FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<u64>), grid, dim3(256), 0, e->stream, Ku, diag, dc, dr, df, F, nn, out);

@@ -36,7 +36,9 @@ extern "C" {
                                  (added since, no layout changed: fsk_set_complement; fsk_set_mismatch_weights and its helpers;
                                   fsk_set_wildcards; fsk_set_center_weights;
                                   fsk_svm_train, fsk_svm_get_model, fsk_svm_decision, fsk_svm_decision_device and fsk_svm_info;
-                                  fsk_svm_cv, fsk_svm_cv_get, fsk_svm_cv_get_alpha and their three structs) */
+                                  fsk_svm_cv, fsk_svm_cv_get, fsk_svm_cv_get_alpha and their three structs;
+                                  fsk_rows_build, fsk_rows_get_block(_device), fsk_rows_get_info and fsk_rows_info,
+                                  fsk_svm_set_kernel / fsk_svm_get_kernel) */
 
 enum {
     FSK_OK = 0,
@@ -483,6 +485,49 @@ int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* f
 int fsk_svm_cv_get(fsk_engine* e, double* oof, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info);
 /* alpha[n_train] of problem p, zero at its held-out rows */
 int fsk_svm_cv_get_alpha(fsk_engine* e, int32_t p, double* alpha);
+
+/* ---- the rows kernel: the SVM on the ROWS of the kernel matrix (the reference's kernel_type = "linear", fastsk.cpp:318-333,
+ * and upstream's LinearSVC on Ktr: a linear model on the "empirical kernel map"), without the matrix leaving the device.
+ *
+ * With n = n_train and A(r, i) the normalised cell (r, i) of the finalized result — the IEEE value fsk_get_block returns,
+ * whichever triangle holds the result —
+ *   L(r, c)  = ((...((A(r,0) A(c,0)) + A(r,1) A(c,1)) + ...) + A(r,n-1) A(c,n-1))
+ *   K2(r, c) = L(r, c) / sqrt(L(r, r) L(c, c))   (the three operations of every getter; a diagonal cell: L / sqrt(L L))
+ * one accumulator a cell, summed in ascending i, every product and every sum a single correctly rounded fp64 operation (no
+ * fused multiply-add, no split of the sum). L is computed for every cell with a train column and for the diagonal of the
+ * test rows; an off-diagonal cell with both sequences in the test set is never computed and reads as 0.0. Only cells of the
+ * result with a train column are read, so the rows kernel is whole under fsk_config.skip_test_block.
+ *
+ * fsk_rows_build: builds L (a packed fp64 triangle of N (N + 1) / 2 cells and its diagonal, resident beside the result)
+ * from the finalized result; FSK_OK at once when it is there already. FSK_ESTATE before a finalized result; FSK_ENOMEM,
+ * the message naming the bytes asked for, when L or the build's scratch (the normalised cells with a train column as fp64,
+ * freed after the build) does not fit. A group handle works on engine 0's reduced triangle. The rows kernel belongs to the
+ * result: whatever drops the SVM model drops it, and the getters then return FSK_ESTATE.
+ * fsk_rows_get_block: cells [i0, i1) x [j0, j1) of the symmetric matrix, row-major, either order of (r, c): raw != 0 gives
+ * L, raw = 0 gives K2. Range errors as fsk_get_block; FSK_ESTATE when no rows kernel is there (it does not build one).
+ * fsk_svm_set_kernel: what fsk_svm_train and fsk_svm_cv solve on and fsk_svm_decision* read — FSK_SVM_KERNEL_RESULT (the
+ * default): the normalised result; FSK_SVM_KERNEL_ROWS: K2, built when a train or a cross-validation needs it. K2 has a unit
+ * diagonal, so the solver is the one of fsk_svm_train to the bit, fed K2; in a fold of fsk_svm_cv the held-out rows stay
+ * feature columns (as in upstream's CalibratedClassifierCV on Ktr): one L serves every problem. A change of kind drops the
+ * model and the cross-validation result; the kind stays with the handle. FSK_EINVAL on any other kind. */
+enum { FSK_SVM_KERNEL_RESULT = 0, FSK_SVM_KERNEL_ROWS = 1 };
+typedef struct fsk_rows_info {
+    int64_t n_train, n_seq;
+    int32_t tile, panel;     /* T and P of k_rows_syrk (the read-only tuning keys rows_tile, rows_panel)       */
+    int64_t tiles;           /* T x T tiles computed by all builds of this handle so far                      */
+    int64_t builds;          /* builds that launched                                                          */
+    int64_t scratch_bytes;   /* the last build's fp64 scratch (freed)                                         */
+    int64_t resident_bytes;  /* L and its diagonal                                                            */
+    double ms_scratch;       /* the last build: the normalising passes into the scratch                       */
+    double ms_product;       /*                 k_rows_syrk and k_rows_diag                                   */
+    double reserved[4];
+} fsk_rows_info;
+int fsk_rows_build(fsk_engine* e);
+int fsk_rows_get_block(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t raw, double* out);
+int fsk_rows_get_block_device(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int32_t raw, double* device_out);
+int fsk_rows_get_info(fsk_engine* e, fsk_rows_info* out);
+int fsk_svm_set_kernel(fsk_engine* e, int32_t kind);
+int fsk_svm_get_kernel(fsk_engine* e, int32_t* kind);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
