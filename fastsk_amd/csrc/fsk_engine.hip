@@ -8,6 +8,7 @@
 // loudly when no device is usable.
 #include "fsk_engine_internal.h"
 #include "fsk_kernels_result.h"
+#include "fsk_load_plan.h"
 
 using namespace fsk_detail;
 
@@ -109,70 +110,12 @@ void enumerate_combos(int g, int k, std::vector<uint8_t>& out) {
     }
 }
 
-// host-side helpers of fsk_load_sequences: contiguous ranges of [0, n) on a few threads
-int host_threads_for(int64_t work_items) {
-    if (work_items < ((int64_t)1 << 18)) return 1;
-    const unsigned hw = std::thread::hardware_concurrency();
-    // (a thread start costs ~50 us; the 3 * 10^7 tokens of the 100,000 x 300 workload are worth 32 of them)
-    const unsigned want = work_items < ((int64_t)1 << 20) ? 4u : work_items < ((int64_t)1 << 23) ? 8u : work_items < ((int64_t)1 << 24) ? 16u : 32u;
-    return (int)std::max(1u, std::min(want, hw ? hw : 1u));
-}
-template <typename F>
-void parallel_ranges(int64_t n, int nt, F&& fn) {
-    if (nt <= 1) { fn(0, (int64_t)0, n); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { fn(t, n * t / nt, n * (t + 1) / nt); });
-    for (auto& x : th) x.join();
-}
-
-// two phases over the same thread team with `between` run by one thread in the middle (one thread start
-// per call instead of two; a spinning barrier: the team is a handful of threads for a fraction of a millisecond)
-template <typename F1, typename FM, typename F2>
-void parallel_two_phase(int nt, F1&& phase1, FM&& between, F2&& phase2) {
-    if (nt <= 1) { phase1(0); between(); phase2(0); return; }
-    std::atomic<int> arrived{0}, go{0};
-    auto body = [&](int t) {
-        phase1(t);
-        if (arrived.fetch_add(1, std::memory_order_acq_rel) + 1 == nt) {
-            between();
-            go.store(1, std::memory_order_release);
-        } else {
-            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
-        }
-        phase2(t);
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(body, t);
-    body(0);
-    for (auto& x : th) x.join();
-}
-
-// one sequence's tokens, rank-remapped through `lut`, BITS per symbol into its own words
-template <int BITS>
-inline void pack_sequence(const int32_t* sq, uint32_t len, const uint8_t* lut, uint32_t* w) {
-    constexpr uint32_t PER = 32u / (uint32_t)BITS;
-    uint32_t p = 0;
-    for (; p + PER <= len; p += PER) {
-        uint32_t word = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < PER; ++q) word |= (uint32_t)lut[sq[p + q]] << (q * (uint32_t)BITS);
-        *w++ = word;
-    }
-    if (p < len) {
-        uint32_t word = 0;
-        for (uint32_t q = 0; p + q < len; ++q) word |= (uint32_t)lut[sq[p + q]] << (q * (uint32_t)BITS);
-        *w = word;
-    }
-}
-
 uint64_t splitmix64(uint64_t& s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-
-
 
 // Which dataflow is cheaper per combo (path = auto)? The dense one multiplies every pair of
 // sequences over the whole key space at the v_dot8 rate; the sparse one issues one scattered
@@ -241,10 +184,6 @@ int choose_path(fsk_engine* e) {
     return FSK_OK;
 }
 
-
-
-
-
 // rows that fsk_reset_counts left for a storing tile launch get their zeros now (anything but such
 // a launch is about to look at K)
 int materialise_zero(fsk_engine* e) {
@@ -257,8 +196,6 @@ int materialise_zero(fsk_engine* e) {
 bool lazy_zero_possible(const fsk_engine* e) {
     return e->path == FSK_PATH_DENSE && !e->compact && !(e->cfg.skip_test_block && e->n_test > 0);
 }
-
-
 
 int do_accumulate(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_t row0, int64_t row1, u64 slot_stride,
                   int defer) {
@@ -344,7 +281,6 @@ void default_order(fsk_engine* e) {
         std::swap(e->order[i], e->order[j]);
     }
 }
-
 
 int fetch_block(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0, int64_t j1, double* out) {
     { int rcz = materialise_zero(e); if (rcz) return rcz; }
@@ -601,391 +537,46 @@ int fsk_load_sequences(fsk_engine* e, const int32_t* tokens, const int64_t* offs
 
 }  // extern "C"
 
-int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test) {
-    if (!offsets || n_train <= 0 || n_test < 0) return e->fail(FSK_EINVAL, "need n_train >= 1, n_test >= 0 and offsets");
-    FSK_ON_DEVICE(e);
-    const int64_t N = n_train + n_test;
-    const int g = e->cfg.g;
-    if (N >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "more than 2^31 sequences");
-    if (offsets[0] < 0) return e->fail(FSK_EINVAL, "offsets[0] must be >= 0");
-    if (offsets[N] > offsets[0] && !tokens) return e->fail(FSK_EINVAL, "null tokens");
-    if (e->stage_in_flight) {  // the previous call's upload reads the pinned staging this call is about to refill
-        FSK_HIP(hipStreamSynchronize(e->stream));
-        e->stage_in_flight = false;
+// ---- fsk_load_sequences: fsk_load_plan.cpp makes the plan on the host (lengths, window census, alphabet, packed words in
+// the pinned staging); what follows commits it to the engine and the device
+namespace {
+
+using fsk_load::LoadPlan;
+
+// the plan's words and tables go into the engine's pinned staging, grown when it is too small
+uint32_t* grow_stage(fsk_engine* e, size_t need) {
+    if (need > e->h_stage_cap) {
+        if (e->h_stage) (void)hipHostFree(e->h_stage);
+        e->h_stage = nullptr; e->h_stage_cap = 0;
+        if (hipHostMalloc((void**)&e->h_stage, (need + need / 4) * sizeof(uint32_t)) != hipSuccess) return nullptr;
+        e->h_stage_cap = need + need / 4;
     }
-    const bool trace_load = e->trace();  // stderr: where the host time of the load goes
-    const auto tl0 = std::chrono::steady_clock::now();
-    auto tl_ms = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    double tl_lengths = 0, tl_pack = 0;
-    // only tokens[offsets[0] .. offsets[N]) belong to the call: everything below works on that window
-    tokens = tokens ? tokens + offsets[0] : tokens;
-    const int64_t off0 = offsets[0];
-    // ---- lengths (fastsk.cpp:32-58)
-    // reverse-complement mode: every sequence owns the windows of both its strands
-    const bool rc_on = !e->rc_tokens.empty();
-    const int64_t strands = rc_on ? 2 : 1;
-    // wildcard mode: a window that holds a wildcard is none. `wild_on`: some sequence really holds one (a set whose tokens do
-    // not occur leaves this load the plain one, to the launch)
-    const bool wild_set = !e->wild_tokens.empty();
-    uint8_t wild_small[256] = {0};
-    for (int32_t t : e->wild_tokens)
-        if (t >= 0 && t < 256) wild_small[t] = 1;
-    auto is_wild = [&](int32_t t) {
-        return (uint32_t)t < 256u ? wild_small[t] != 0 : std::binary_search(e->wild_tokens.begin(), e->wild_tokens.end(), t);
-    };
-    if (wild_set && rc_on)
-        for (size_t q = 0; q < e->rc_tokens.size(); ++q)
-            if (is_wild(e->rc_tokens[q]) && !is_wild(e->rc_comps[q]))
-                return e->fail(FSK_EINVAL, "wildcard token %d has the complement %d, which is not a wildcard", e->rc_tokens[q], e->rc_comps[q]);
-    int64_t shortest_train = INT64_MAX, shortest_test = INT64_MAX, longest = 0, nfeat = 0;
-    for (int64_t i = 0; i < N; ++i) {
-        const int64_t len = offsets[i + 1] - offsets[i];
-        if (len < 0) return e->fail(FSK_EINVAL, "offsets must be non-decreasing");
-        if (i < n_train) shortest_train = std::min(shortest_train, len);
-        else shortest_test = std::min(shortest_test, len);
-        longest = std::max(longest, len);
-        nfeat += len >= g ? strands * (len - g + 1) : 0;
-    }
-    if (g > shortest_train)
-        return e->fail(FSK_ESHORT, "g cannot be longer than the shortest sequence in a dataset. g = %d, but shortest train sequence has length %lld", g, (long long)shortest_train);
-    if (n_test > 0 && g > shortest_test)
-        return e->fail(FSK_ESHORT, "g cannot be longer than the shortest sequence in a dataset. g = %d, but shortest test sequence has length %lld", g, (long long)shortest_test);
-    if (nfeat >= ((int64_t)1 << 31) || longest >= ((int64_t)1 << 24)) return e->fail(FSK_EUNSUPPORTED, "input too large (g-mers >= 2^31 or a sequence >= 2^24)");
-    // wildcard mode: the windows free of wildcards, per sequence — their number (nvalid), one bit a window position
-    // (vbits, sequence i from word vstart[i]; bits past the last position stay zero) —, found with the length of the
-    // wildcard-free run that ends at every symbol: the window that ends there is valid when the run reaches g
-    //
-    // centre-weighted mode: window p of a sequence of nw windows lies d = |2 p - (nw - 1)| / 2 from its centre (2 p + g - len,
-    // halved downwards) and counts w[min(d, n - 1)] times. The distances the data reach are 0 .. (longest - g) / 2: `cw_on`
-    // when one of their weights is not 1 (else this load is the plain one, to the launch), and a weight of 0 among them
-    // clears windows in the validity bitmap as a wildcard does. nvalid, nfeat and most_valid are then SUMS OF WEIGHTS.
-    const std::vector<uint8_t>& cwp = e->cw_profile;
-    bool cw_on = false, cw_zero = false;
-    if (!cwp.empty() && longest >= g) {
-        const size_t reach = std::min<size_t>((size_t)((longest - g) / 2), cwp.size() - 1);
-        for (size_t d = 0; d <= reach; ++d) { cw_on = cw_on || cwp[d] != 1; cw_zero = cw_zero || cwp[d] == 0; }
-    }
-    auto cw_of = [&](int64_t p, int64_t nw) -> int64_t {
-        const int64_t t = 2 * p - (nw - 1);
-        return (int64_t)cwp[(size_t)std::min<int64_t>((t < 0 ? -t : t) / 2, (int64_t)cwp.size() - 1)];
-    };
-    bool wild_tok = false;  // some sequence really holds a wildcard
-    std::vector<uint32_t> nvalid, vstart, vbits;
-    int64_t most_valid = longest - g + 1;
-    if (wild_set) {
-        const int64_t total_tok = offsets[N] - off0;
-        for (int64_t i = 0; i < total_tok && !wild_tok; ++i) wild_tok = is_wild(tokens[i]);
-    }
-    const bool wild_on = wild_tok || cw_zero;
-    if (cw_on && !wild_on) {  // every window stays one: only the sums change
-        nvalid.resize((size_t)N);
-        nfeat = 0;
-        most_valid = 0;
-        for (int64_t i = 0; i < N; ++i) {
-            const int64_t nw = offsets[i + 1] - offsets[i] - g + 1;
-            int64_t nv = 0;
-            for (int64_t p = 0; p < nw; ++p) nv += cw_of(p, nw);
-            if (nv >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
-            nvalid[(size_t)i] = (uint32_t)nv;
-            nfeat += strands * nv;
-            most_valid = std::max(most_valid, nv);
-        }
-    }
-    if (wild_on) {
-        nvalid.resize((size_t)N);
-        vstart.resize((size_t)N + 1);
-        uint64_t vw = 0;
-        for (int64_t i = 0; i < N; ++i) {
-            vstart[(size_t)i] = (uint32_t)vw;
-            vw += (uint64_t)(offsets[i + 1] - offsets[i] - g + 1 + 31) / 32;
-        }
-        vstart[(size_t)N] = (uint32_t)vw;  // (fewer words than symbols: below 2^31)
-        vbits.assign((size_t)vw + 1, 0u);
-        nfeat = 0;
-        most_valid = 0;
-        for (int64_t i = 0; i < N; ++i) {
-            const int32_t* sq = tokens + (offsets[i] - off0);
-            const int64_t len = offsets[i + 1] - offsets[i];
-            uint32_t* vb = vbits.data() + vstart[(size_t)i];
-            int64_t run = 0, nv = 0;
-            for (int64_t p = 0; p < len; ++p) {
-                run = wild_tok && is_wild(sq[p]) ? 0 : run + 1;
-                if (run >= g) {
-                    const int64_t j = p - g + 1;
-                    const int64_t wgt = cw_on ? cw_of(j, len - g + 1) : 1;
-                    if (wgt == 0) continue;  // (a window of weight 0 is none)
-                    vb[j >> 5] |= 1u << (j & 31);
-                    nv += wgt;
-                }
-            }
-            if (nv == 0)
-                return e->fail(FSK_ESHORT, "sequence %lld has no window of length g = %d that is free of wildcards%s: it would have no features", (long long)i, g,
-                               cw_on ? " and has a center weight above 0" : "");
-            if (nv >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
-            nvalid[(size_t)i] = (uint32_t)nv;
-            nfeat += strands * nv;
-            most_valid = std::max(most_valid, nv);
-        }
-    }
-    // (the weighted features are the sort records and the 32-bit feature offsets: the bound again, now that they are known)
-    if (nfeat >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "input too large (weighted g-mers >= 2^31)");
-    tl_lengths = tl_ms(tl0);
-    // ---- alphabet: rank-remap the tokens that occur (equality preserving; the reference's
-    // dict_size = |{0} U tokens|, fastsk.cpp:70-85, only serves as its counting-sort radix), then pack,
-    // every sequence word-aligned.
-    const int64_t total = offsets[N] - off0;
-    std::vector<int32_t> distinct;
-    std::vector<int64_t> sym_freq(256, 0);
-    uint32_t sigma = 1;
-    int bits = 2, key_symbits = 0;
-    u64 V = 1;
-    std::vector<uint32_t> len32((size_t)N), fstart((size_t)N + 1);
-    std::vector<uint32_t> wstart_v, words_v;           // general path only
-    const uint32_t *p_words = nullptr, *p_wstart = nullptr;
-    size_t n_words_alloc = 0;
-    bool staged = false;                               // packed into the engine's pinned staging: asynchronous upload
-    {
-        uint32_t fcount = 0;
-        for (int64_t i = 0; i < N; ++i) {
-            const int64_t len = offsets[i + 1] - offsets[i];
-            len32[i] = (uint32_t)len;
-            fstart[i] = fcount;
-            fcount += (uint32_t)(strands * (wild_on || cw_on ? (int64_t)nvalid[(size_t)i] : len - g + 1));
-        }
-        fstart[N] = fcount;
-    }
-    // reverse-complement mode: `distinct` (the tokens present, ascending) becomes its closure under the map — data without
-    // a single 'g' still produce 'g' on their second strand —; a token the map does not list fails the load, named (the
-    // first one in the data: protein given to a DNA map must not be self-complemented silently)
-    auto rc_comp_of = [&](int32_t t, int32_t* out) {
-        const auto it = std::lower_bound(e->rc_tokens.begin(), e->rc_tokens.end(), t);
-        if (it == e->rc_tokens.end() || *it != t) return false;
-        *out = e->rc_comps[(size_t)(it - e->rc_tokens.begin())];
-        return true;
-    };
-    auto rc_close = [&]() -> int {
-        if (!rc_on) return FSK_OK;
-        const size_t present = distinct.size();
-        for (size_t q = 0; q < present; ++q) {
-            int32_t c = 0;
-            if (!rc_comp_of(distinct[q], &c)) {
-                int32_t first = distinct[q];
-                for (int64_t i = 0; i < total; ++i)
-                    if (!rc_comp_of(tokens[i], &c) && !(wild_tok && is_wild(tokens[i]))) { first = tokens[i]; break; }
-                return e->fail(FSK_EINVAL, "token %d occurs in the sequences but not in the complement map", first);
-            }
-            distinct.push_back(c);
-        }
-        std::sort(distinct.begin(), distinct.end());
-        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-        return FSK_OK;
-    };
-    // sigma, bits, V from `distinct`; where every sequence's words start
-    auto plan_words = [&](uint32_t* wstart, uint64_t* nwords_out) -> int {
-        // (cntsrtna's radix is the dictionary size, whatever it is — shared.cpp:156-191 — and its keys are tuples, never a
-        // number: up to 65536 symbols travel as 16-bit fields, and a k-mer space beyond 2^62 is keyed by the symbols' bit
-        // fields side by side instead of a mixed-radix number, see key_symbits)
-        if (distinct.size() > 65536) return e->fail(FSK_EUNSUPPORTED, "alphabet of %zu symbols (> 65536)", distinct.size());
-        sigma = (uint32_t)std::max<size_t>(1, distinct.size());
-        bits = sigma <= 4 ? 2 : sigma <= 16 ? 4 : sigma <= 256 ? 8 : 16;
-        V = 1;
-        key_symbits = 0;
-        for (int c = 0; c < e->k; ++c) {
-            if (V > (((u64)1 << 62) / sigma)) { key_symbits = 1; break; }
-            V *= sigma;
-        }
-        if (key_symbits) {
-            while (((u64)1 << key_symbits) < sigma) ++key_symbits;
-            V = (u64)1 << 62;  // (at least: the dense dataflow and the 24-bit fast paths are out of the question)
-            if ((int64_t)key_symbits * e->k > 96)
-                return e->fail(FSK_EUNSUPPORTED, "a k-mer of %d symbols of %d bits does not fit the 128-bit sort records", e->k, key_symbits);
-        }
-        uint64_t nwords = 0;
-        for (int64_t i = 0; i < N; ++i) {
-            wstart[i] = (uint32_t)nwords;
-            nwords += ((uint64_t)len32[i] * bits + 31) / 32;
-            if (nwords >= ((uint64_t)1 << 32)) return e->fail(FSK_EUNSUPPORTED, "packed sequences exceed 2^32 words");
-        }
-        *nwords_out = nwords;
-        return FSK_OK;
-    };
-    {
-        // Fast path — token ids below 256, every vocabulary in practice: ONE team of host threads counts the
-        // tokens of its share of the sequences (256 counters each), one of them turns the counts into the
-        // rank table and lays out the words in the engine's pinned staging, the team packs its sequences
-        // there; the upload is asynchronous. (At 100k x 300 tokens this is the load time.)
-        const int nt = host_threads_for(total);
-        std::vector<int64_t> bound((size_t)nt + 1, N);  // sequence ranges with about equal token counts
-        bound[0] = 0;
-        for (int t = 1; t < nt; ++t)
-            bound[(size_t)t] = std::lower_bound(offsets, offsets + N, off0 + total * t / nt) - offsets;
-        std::vector<std::array<int64_t, 256>> hist((size_t)nt);
-        std::vector<char> small((size_t)nt, 1);
-        uint8_t lut[256] = {0};
-        int rc_mid = FSK_OK;
-        bool all_small = true;
-        uint32_t* st_words = nullptr;
-        uint32_t* st_wstart = nullptr;
-        parallel_two_phase(
-            nt,
-            [&](int t) {
-                std::array<int64_t, 256>& h = hist[(size_t)t];
-                h.fill(0);
-                const int64_t lo = offsets[bound[(size_t)t]] - off0, hi = offsets[bound[(size_t)t + 1]] - off0;
-                // (four interleaved sets of counters: neighbouring tokens are often equal — DNA has four symbols —, and one
-                // counter incremented twice in a row waits for its own store: ~1.1 -> ~0.5 ns a token)
-                uint32_t h4[4][256];
-                memset(h4, 0, sizeof h4);
-                uint32_t big = 0;
-                int64_t i = lo;
-                for (; i + 4 <= hi; i += 4) {
-                    const uint32_t v0 = (uint32_t)tokens[i], v1 = (uint32_t)tokens[i + 1], v2 = (uint32_t)tokens[i + 2], v3 = (uint32_t)tokens[i + 3];
-                    big |= v0 | v1 | v2 | v3;
-                    h4[0][v0 & 255u]++; h4[1][v1 & 255u]++; h4[2][v2 & 255u]++; h4[3][v3 & 255u]++;
-                }
-                for (; i < hi; ++i) { const uint32_t v = (uint32_t)tokens[i]; big |= v; h4[0][v & 255u]++; }
-                if (big >= 256u) small[(size_t)t] = 0;  // (a token id beyond 255 somewhere: the general path below)
-                for (int v = 0; v < 256; ++v) h[(size_t)v] = (int64_t)h4[0][v] + h4[1][v] + h4[2][v] + h4[3][v];
-            },
-            [&] {
-                for (int t = 0; t < nt; ++t) all_small = all_small && small[(size_t)t];
-                if (!all_small) return;
-                int64_t cnt[256];
-                for (int v = 0; v < 256; ++v) {
-                    cnt[v] = 0;
-                    for (int t = 0; t < nt; ++t) cnt[v] += hist[(size_t)t][(size_t)v];
-                    if (cnt[v] && !(wild_tok && wild_small[v])) distinct.push_back(v);
-                }
-                rc_mid = rc_close();
-                if (rc_mid) return;
-                if (distinct.size() > 256) { all_small = false; distinct.clear(); return; }  // (complements beyond the byte table: the general path)
-                for (size_t r = 0; r < distinct.size(); ++r)
-                    if (distinct[r] >= 0 && distinct[r] < 256) { lut[distinct[r]] = (uint8_t)r; sym_freq[r] = cnt[distinct[r]]; }
-                // staging: [words + 4][wstart N][len N][fstart N + 1]
-                std::vector<uint32_t> ws((size_t)N);
-                uint64_t nwords = 0;
-                rc_mid = plan_words(ws.data(), &nwords);
-                if (rc_mid) return;
-                const size_t need = (size_t)nwords + 4 + 3 * (size_t)N + 1;
-                if (need > e->h_stage_cap) {
-                    if (e->h_stage) (void)hipHostFree(e->h_stage);
-                    e->h_stage = nullptr; e->h_stage_cap = 0;
-                    if (hipHostMalloc((void**)&e->h_stage, (need + need / 4) * sizeof(uint32_t)) != hipSuccess) {
-                        rc_mid = e->fail(FSK_ENOMEM, "cannot allocate %zu bytes of pinned staging", need * sizeof(uint32_t));
-                        return;
-                    }
-                    e->h_stage_cap = need + need / 4;
-                }
-                st_words = e->h_stage;
-                st_wstart = e->h_stage + (size_t)nwords + 4;
-                memcpy(st_wstart, ws.data(), (size_t)N * sizeof(uint32_t));
-                memcpy(st_wstart + N, len32.data(), (size_t)N * sizeof(uint32_t));
-                memcpy(st_wstart + 2 * N, fstart.data(), ((size_t)N + 1) * sizeof(uint32_t));
-                memset(st_words + nwords, 0, 4 * sizeof(uint32_t));
-                n_words_alloc = (size_t)nwords + 4;
-            },
-            [&](int t) {
-                if (!all_small || rc_mid) return;
-                for (int64_t i = bound[(size_t)t]; i < bound[(size_t)t + 1]; ++i) {  // a sequence's words are its own
-                    const int32_t* sq = tokens + (offsets[i] - off0);
-                    uint32_t* w = st_words + st_wstart[i];
-                    // (the symbol width as a compile-time constant: the 16 / 8 / 4 symbols of a word unroll)
-                    if (bits == 2) pack_sequence<2>(sq, len32[i], lut, w);
-                    else if (bits == 4) pack_sequence<4>(sq, len32[i], lut, w);
-                    else pack_sequence<8>(sq, len32[i], lut, w);
-                }
-            });
-        if (rc_mid) return rc_mid;
-        if (all_small) {
-            staged = true;
-            p_words = st_words;
-            p_wstart = st_wstart;
-        }
-    }
-    if (!staged) {
-        // General path (token values anywhere in int32): distinct values by sort or by a seen-table, ranks by
-        // table or binary search, one thread.
-        int32_t lo = INT32_MAX, hi = INT32_MIN;
-        for (int64_t i = 0; i < total; ++i) { lo = std::min(lo, tokens[i]); hi = std::max(hi, tokens[i]); }
-        if (total > 0 && lo >= 0 && hi < (1 << 20)) {
-            std::vector<char> seen((size_t)hi + 1, 0);
-            for (int64_t i = 0; i < total; ++i) seen[tokens[i]] = 1;
-            for (int32_t v = 0; v <= hi; ++v) if (seen[v]) distinct.push_back(v);
-        } else {
-            distinct.assign(tokens, tokens + total);
-            std::sort(distinct.begin(), distinct.end());
-            distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-        }
-        if (wild_tok) distinct.erase(std::remove_if(distinct.begin(), distinct.end(), is_wild), distinct.end());
-        { const int rc_cl = rc_close(); if (rc_cl) return rc_cl; }
-        if (distinct.size() > sym_freq.size()) sym_freq.assign(distinct.size(), 0);
-        wstart_v.resize((size_t)N);
-        uint64_t nwords = 0;
-        int rc_plan = plan_words(wstart_v.data(), &nwords);
-        if (rc_plan) return rc_plan;
-        words_v.assign((size_t)nwords + 4, 0u);
-        const int32_t base = distinct.empty() ? 0 : distinct.front();
-        const bool direct = !distinct.empty() && (int64_t)distinct.back() - base < (1 << 20);
-        std::vector<uint16_t> lut;
-        if (direct) {
-            lut.assign((size_t)(distinct.back() - base) + 1, 0);
-            for (size_t r = 0; r < distinct.size(); ++r) lut[(size_t)(distinct[r] - base)] = (uint16_t)r;
-        }
-        for (int64_t i = 0; i < N; ++i) {
-            const int32_t* sq = tokens + (offsets[i] - off0);
-            uint32_t* w = words_v.data() + wstart_v[i];
-            for (uint32_t p = 0; p < len32[i]; ++p) {
-                if (wild_tok && is_wild(sq[p])) continue;  // (rank 0 in the words, counted nowhere)
-                uint32_t r = direct ? lut[(size_t)(sq[p] - base)]
-                                    : (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), sq[p]) - distinct.begin());
-                const uint32_t bitpos = p * (uint32_t)bits;
-                w[bitpos >> 5] |= r << (bitpos & 31u);
-                sym_freq[r]++;
-            }
-        }
-        p_words = words_v.data();
-        p_wstart = wstart_v.data();
-        n_words_alloc = words_v.size();
-    }
-    // the complement of every rank; a symbol's frequency over both strands is its own plus its complement's
-    std::vector<uint16_t> comp_rank;
-    if (rc_on) {
-        comp_rank.resize(distinct.size());
-        for (size_t r = 0; r < distinct.size(); ++r) {
-            int32_t c = 0;
-            (void)rc_comp_of(distinct[r], &c);
-            comp_rank[r] = (uint16_t)(std::lower_bound(distinct.begin(), distinct.end(), c) - distinct.begin());
-        }
-        std::vector<int64_t> both(sym_freq);
-        for (size_t r = 0; r < distinct.size(); ++r) both[r] = sym_freq[r] + sym_freq[comp_rank[r]];
-        sym_freq.swap(both);
-    }
-    int64_t total_sym = strands * total;  // symbols counted, both strands
-    if (wild_tok) {
-        total_sym = 0;
-        for (size_t r = 0; r < distinct.size() && r < sym_freq.size(); ++r) total_sym += sym_freq[r];
-    }
-    tl_pack = tl_ms(tl0);
-    // ---- commit
+    return e->h_stage;
+}
+
+// the engine's view of the loaded set: sizes, modes, the sparse dataflow's hint and key widths, the dataflow
+int commit_load(fsk_engine* e, const LoadPlan& p, int64_t n_train, int64_t n_test) {
+    const int64_t N = p.N;
+    const uint32_t strands = p.rc_on ? 2u : 1u;
     // (the dense dataflow's tile table depends on the number of sequences and the train / test split alone: a set of the same
     // shape keeps the one on the device)
     if (e->N != N || e->n_train != n_train) e->tab_n = 0;
-    e->N = N; e->n_train = n_train; e->n_test = n_test; e->nfeat = nfeat;
+    e->N = N; e->n_train = n_train; e->n_test = n_test; e->nfeat = p.nfeat;
     e->pairs = N * (N + 1) / 2;
-    e->sigma = sigma; e->bits = bits; e->V = V; e->Vq = (uint32_t)((V + 3) / 4);
-    e->Lmax = (uint32_t)longest; e->Lmin = (uint32_t)std::min(shortest_train, n_test > 0 ? shortest_test : shortest_train);
-    e->maxW1 = (uint32_t)(longest - g + 1);
-    e->maxW = (uint32_t)strands * (uint32_t)most_valid;
-    e->revcomp = rc_on;
-    e->wild = wild_on;
-    e->cw = cw_on;
-    e->cw_n = cw_on ? (uint32_t)cwp.size() : 0u;
-    e->fwin_on = wild_on || cw_on;
+    e->sigma = p.sigma; e->bits = p.bits; e->V = p.V; e->Vq = (uint32_t)((p.V + 3) / 4);
+    e->Lmax = (uint32_t)p.longest; e->Lmin = (uint32_t)p.shortest;
+    e->maxW1 = (uint32_t)(p.longest - e->cfg.g + 1);
+    e->maxW = strands * (uint32_t)p.most_valid;
+    e->revcomp = p.rc_on;
+    e->wild = p.wild_on;
+    e->cw = p.cw_on;
+    e->cw_n = p.cw_on ? (uint32_t)e->cw_profile.size() : 0u;
+    e->fwin_on = p.wild_on || p.cw_on;
     e->n_panels = (uint32_t)((N + fsk::PANEL - 1) / fsk::PANEL);
-    e->h_len = len32; e->h_fstart = fstart; e->featseq_ready = false;
+    e->h_len = p.len32; e->h_fstart = p.fstart; e->featseq_ready = false;
     e->prep_valid = false; e->vc_sum = 0; e->vc_n = 0;
 
-    e->lazy_lo = e->lazy_hi = -1;  // (the triangle is zeroed, or promised to be, below)
+    e->lazy_lo = e->lazy_hi = -1;  // (the triangle is zeroed, or promised to be, by the caller)
     e->u_known = false; e->u_pending = false; e->u_extra = 0; e->u_value = 0;
     {
         // The update words per record seen on the previous set of sequences stay as a HINT when the new set has the same shape
@@ -993,107 +584,110 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         // enqueued under a guard like every later one instead of being capped at 2^25 records and waited for. A hint that is
         // too low costs what any overflowing guard costs — the batch leaves K alone and is redone sized exactly —, never a
         // result. Tuning sparse_hint = 0: every set of sequences starts from nothing (testing).
-        const bool same = e->tune.sparse_hint && e->loaded && e->sx_shape[0] == (u64)N && e->sx_shape[1] == (u64)nfeat && e->sx_shape[2] == (u64)sigma &&
-                          e->sx_shape[3] == (u64)longest;
+        const u64 shape[4] = {(u64)N, (u64)p.nfeat, (u64)p.sigma, (u64)p.longest};
+        const bool same = e->tune.sparse_hint && e->loaded && std::equal(shape, shape + 4, e->sx_shape);
         if (!same) { e->sx_wpr = 0; e->sx_ppr = 0; e->slots16_ok = true; }
-        e->sx_shape[0] = (u64)N; e->sx_shape[1] = (u64)nfeat; e->sx_shape[2] = (u64)sigma; e->sx_shape[3] = (u64)longest;
+        std::copy(shape, shape + 4, e->sx_shape);
     }
     for (auto& d : e->sx_defer) d.active = false;
     if (e->V > DENSE_MAX_KEYS) e->Vq = 1;  // unused on the sparse path
-    {   // sparse dataflow: sort record = (k-mer << sx_sb) | sequence id; owner bands of K
-        e->sx_sb = 1;
-        while (((int64_t)1 << e->sx_sb) < N) ++e->sx_sb;
-        e->sx_symbits = key_symbits;
-        e->sx_keybits = 1;
-        if (key_symbits) e->sx_keybits = key_symbits * e->k;
-        else while (e->sx_keybits < 62 && ((u64)1 << e->sx_keybits) < V) ++e->sx_keybits;
-        plan_owner_bands(e);
+    // sparse dataflow: sort record = (k-mer << sx_sb) | sequence id; owner bands of K
+    e->sx_sb = 1;
+    while (((int64_t)1 << e->sx_sb) < N) ++e->sx_sb;
+    e->sx_symbits = p.key_symbits;
+    e->sx_keybits = 1;
+    if (p.key_symbits) e->sx_keybits = p.key_symbits * e->k;
+    else while (e->sx_keybits < 62 && ((u64)1 << e->sx_keybits) < p.V) ++e->sx_keybits;
+    plan_owner_bands(e);
+    return choose_path(e);
+}
+
+// key compaction pays when a symbol is rare (DNA with a few 'n'): most of the sigma^k key
+// space is then empty and need not be multiplied
+struct Compaction { bool compact = false, compact_rare = false; uint32_t rare_mask = 0, rare_places = 0; };
+Compaction choose_compaction(const LoadPlan& p, const fsk_tuning& tune, int g, int k) {
+    Compaction c;
+    int64_t rarest = INT64_MAX;
+    for (uint32_t r = 0; r < p.sigma; ++r) rarest = std::min(rarest, p.sym_freq[r]);
+    c.compact = p.sigma >= 3 && p.V >= 64 && p.V <= 4096 && rarest * 50 < p.total_sym;
+    if (tune.compact >= 0) c.compact = tune.compact != 0 && p.V <= 4096;
+    // ... and the keys that occur follow from the places of the rare symbols when those are few (g windows per place
+    // and combo are marked instead of every window) and every key of common symbols can be taken as present (16
+    // windows per such key at least: one that is missing only costs an empty panel row)
+    int64_t places = 0;
+    uint32_t common = 0;
+    for (uint32_t r = 0; r < p.sigma && r < 32u; ++r) {
+        if (p.sym_freq[r] * 50 < p.total_sym) { c.rare_mask |= 1u << r; places += p.sym_freq[r]; }
+        else ++common;
     }
-    int rc = choose_path(e);
+    double common_keys = 1;
+    for (int i = 0; i < k; ++i) common_keys *= (double)common;
+    c.compact_rare = c.compact && p.sigma <= 32 && common >= 1 && places > 0 && places < ((int64_t)1 << 24) &&
+                     places * (int64_t)g * 8 < std::max<int64_t>(1, p.nfeat) && (double)p.nfeat >= 16.0 * common_keys;
+    if (tune.compact_rare >= 0) c.compact_rare = c.compact && tune.compact_rare != 0 && p.sigma <= 32 && places < ((int64_t)1 << 24);
+    // (reverse-complement mode: the rare symbols' places are listed on one strand only — the marking pass over every
+    // window of both strands, k_dense_count<true, ., true>, instead; wildcard mode likewise: the windows around a rare
+    // symbol's place may hold a wildcard, which the marking pass knows; centre-weighted mode likewise: the marking pass,
+    // whose keys are the counted ones)
+    if (p.rc_on || p.wild_on || p.cw_on) c.compact_rare = false;
+    c.rare_places = (uint32_t)places;
+    return c;
+}
+
+// the small side tables of the modes, then words, word starts, lengths and feature starts from the pinned staging: four
+// copies on the stream, nothing to wait for
+int upload_load(fsk_engine* e, const LoadPlan& p) {
+    const size_t N = (size_t)p.N, n_words = (size_t)p.n_words + 4;
+    FSK_HIP(e->d_words.reserve(n_words));
+    FSK_HIP(e->d_wstart.reserve(N));
+    FSK_HIP(e->d_len.reserve(N));
+    FSK_HIP(e->d_fstart.reserve(N + 1));
+    auto table = [](auto& dev, const auto& host) {  // a whole host vector into its device buffer, waited for
+        const hipError_t r = dev.reserve(std::max<size_t>(1, host.size()));
+        return r != hipSuccess ? r : hipMemcpy(dev.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice);
+    };
+    if (p.rc_on) FSK_HIP(table(e->d_comp, p.comp_rank));
+    if (p.wild_on || p.cw_on) FSK_HIP(table(e->d_fwin, p.fwin));
+    if (p.cw_on) FSK_HIP(table(e->d_cw, e->cw_profile));
+    if (p.wild_on) {
+        FSK_HIP(table(e->d_vbits, p.vbits));
+        FSK_HIP(table(e->d_vstart, p.vstart));
+    }
+    const uint32_t* tables = p.staging + n_words;  // [wstart N][len N][fstart N + 1]
+    FSK_HIP(hipMemcpyAsync(e->d_words.p, p.staging, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(e->d_wstart.p, tables, N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(e->d_len.p, tables + N, N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(e->d_fstart.p, tables + 2 * N, (N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    e->stage_in_flight = true;
+    return FSK_OK;
+}
+
+}  // namespace
+
+int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test) {
+    if (!offsets || n_train <= 0 || n_test < 0) return e->fail(FSK_EINVAL, "need n_train >= 1, n_test >= 0 and offsets");
+    FSK_ON_DEVICE(e);
+    const int64_t N = n_train + n_test;
+    if (N >= ((int64_t)1 << 31)) return e->fail(FSK_EUNSUPPORTED, "more than 2^31 sequences");
+    if (offsets[0] < 0) return e->fail(FSK_EINVAL, "offsets[0] must be >= 0");
+    if (offsets[N] > offsets[0] && !tokens) return e->fail(FSK_EINVAL, "null tokens");
+    if (e->stage_in_flight) {  // the previous call's upload reads the pinned staging this call is about to refill
+        FSK_HIP(hipStreamSynchronize(e->stream));
+        e->stage_in_flight = false;
+    }
+    const auto tl0 = std::chrono::steady_clock::now();  // (tuning trace = 1, stderr: where the host time of the load goes)
+    const fsk_load::LoadInput in{e->cfg.g, e->k, e->rc_tokens.data(), e->rc_comps.data(), e->rc_tokens.size(), e->wild_tokens.data(), e->wild_tokens.size(),
+                                 e->cw_profile.data(), e->cw_profile.size(), tokens, offsets, n_train, n_test};
+    LoadPlan plan;
+    fsk_load::make_load_plan(in, [e](size_t need) { return grow_stage(e, need); }, plan);
+    if (plan.code) return e->fail(plan.code, "%s", plan.msg.c_str());
+    int rc = commit_load(e, plan, n_train, n_test);
     if (rc) return rc;
-    {   // key compaction pays when a symbol is rare (DNA with a few 'n'): most of the sigma^k key
-        // space is then empty and need not be multiplied
-        int64_t rarest = INT64_MAX;
-        for (uint32_t r = 0; r < sigma; ++r) rarest = std::min(rarest, sym_freq[r]);
-        e->compact = sigma >= 3 && V >= 64 && V <= 4096 && rarest * 50 < total_sym;
-        if (e->tune.compact >= 0) e->compact = e->tune.compact != 0 && V <= 4096;
-        // ... and the keys that occur follow from the places of the rare symbols when those are few (g windows per place
-        // and combo are marked instead of every window) and every key of common symbols can be taken as present (16
-        // windows per such key at least: one that is missing only costs an empty panel row)
-        e->rare_mask = 0; e->rare_places = 0; e->rare_ready = false;
-        int64_t places = 0;
-        uint32_t common = 0;
-        for (uint32_t r = 0; r < sigma && r < 32u; ++r) {
-            if (sym_freq[r] * 50 < total_sym) { e->rare_mask |= 1u << r; places += sym_freq[r]; }
-            else ++common;
-        }
-        double common_keys = 1;
-        for (int c = 0; c < e->k; ++c) common_keys *= (double)common;
-        e->compact_rare = e->compact && sigma <= 32 && common >= 1 && places > 0 && places < ((int64_t)1 << 24) &&
-                          places * (int64_t)g * 8 < std::max<int64_t>(1, nfeat) && (double)nfeat >= 16.0 * common_keys;
-        if (e->tune.compact_rare >= 0) e->compact_rare = e->compact && e->tune.compact_rare != 0 && sigma <= 32 && places < ((int64_t)1 << 24);
-        // (reverse-complement mode: the rare symbols' places are listed on one strand only — the marking pass over every
-        // window of both strands, k_dense_count<true, ., true>, instead)
-        if (rc_on) e->compact_rare = false;
-        // (wildcard mode likewise: the windows around a rare symbol's place may hold a wildcard, which the marking pass knows)
-        if (wild_on) e->compact_rare = false;
-        // (centre-weighted mode likewise: the marking pass, whose keys are the counted ones)
-        if (cw_on) e->compact_rare = false;
-        e->rare_places = (uint32_t)places;
-    }
-    FSK_HIP(e->d_words.reserve(n_words_alloc));
-    FSK_HIP(e->d_wstart.reserve((size_t)N));
-    FSK_HIP(e->d_len.reserve((size_t)N));
-    FSK_HIP(e->d_fstart.reserve((size_t)N + 1));
-    if (rc_on) {
-        FSK_HIP(e->d_comp.reserve(comp_rank.size()));
-        FSK_HIP(hipMemcpy(e->d_comp.p, comp_rank.data(), comp_rank.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    if (wild_on || cw_on) {
-        // the window of every feature, for the sparse dataflow: a sequence's valid forward windows in order, then (second
-        // strand) window j' of rc(x), valid exactly when forward window (len - g) - j' is, as len - g + 1 + j'
-        // (centre-weighted mode: a window is listed as often as it weighs — w(j') = w(forward twin) — and so becomes that
-        // many equal sort records: the run length of the segment stage is the weighted multiplicity)
-        std::vector<uint32_t> fwin((size_t)nfeat);
-        for (int64_t i = 0; i < N; ++i) {
-            const uint32_t nw = len32[(size_t)i] - (uint32_t)g + 1u;
-            const uint32_t* vb = wild_on ? vbits.data() + vstart[(size_t)i] : nullptr;
-            uint32_t* out = fwin.data() + fstart[(size_t)i];
-            for (uint32_t j = 0; j < nw; ++j)
-                if (!vb || ((vb[j >> 5] >> (j & 31u)) & 1u))
-                    for (int64_t c = cw_on ? cw_of(j, nw) : 1; c > 0; --c) *out++ = j;
-            if (rc_on)
-                for (uint32_t j = 0; j < nw; ++j) {
-                    const uint32_t f = nw - 1u - j;
-                    if (!vb || ((vb[f >> 5] >> (f & 31u)) & 1u))
-                        for (int64_t c = cw_on ? cw_of(f, nw) : 1; c > 0; --c) *out++ = nw + j;
-                }
-        }
-        FSK_HIP(e->d_fwin.reserve(std::max<size_t>(1, fwin.size())));
-        FSK_HIP(hipMemcpy(e->d_fwin.p, fwin.data(), fwin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (cw_on) {
-        FSK_HIP(e->d_cw.reserve(cwp.size()));
-        FSK_HIP(hipMemcpy(e->d_cw.p, cwp.data(), cwp.size(), hipMemcpyHostToDevice));
-    }
-    if (wild_on) {
-        FSK_HIP(e->d_vbits.reserve(vbits.size()));
-        FSK_HIP(e->d_vstart.reserve(vstart.size()));
-        FSK_HIP(hipMemcpy(e->d_vbits.p, vbits.data(), vbits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        FSK_HIP(hipMemcpy(e->d_vstart.p, vstart.data(), vstart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (staged) {  // everything sits in pinned memory: four copies on the stream, nothing to wait for
-        FSK_HIP(hipMemcpyAsync(e->d_words.p, p_words, n_words_alloc * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        FSK_HIP(hipMemcpyAsync(e->d_wstart.p, p_wstart, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        FSK_HIP(hipMemcpyAsync(e->d_len.p, p_wstart + N, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        FSK_HIP(hipMemcpyAsync(e->d_fstart.p, p_wstart + 2 * N, ((size_t)N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        e->stage_in_flight = true;
-    } else {
-        FSK_HIP(hipMemcpy(e->d_words.p, p_words, n_words_alloc * sizeof(uint32_t), hipMemcpyHostToDevice));
-        FSK_HIP(hipMemcpy(e->d_wstart.p, p_wstart, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
-        FSK_HIP(hipMemcpy(e->d_len.p, e->h_len.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
-        FSK_HIP(hipMemcpy(e->d_fstart.p, e->h_fstart.data(), ((size_t)N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    const Compaction c = choose_compaction(plan, e->tune, e->cfg.g, e->k);
+    e->compact = c.compact; e->compact_rare = c.compact_rare; e->rare_mask = c.rare_mask; e->rare_places = c.rare_places;
+    e->rare_ready = false;
+    rc = upload_load(e, plan);
+    if (rc) return rc;
     if (e->d_K && !e->K_owned) {
         if (e->bound_cells != e->pairs) return e->fail(FSK_EINVAL, "bound counts buffer holds %lld cells, need %lld", (long long)e->bound_cells, (long long)e->pairs);
     } else {
@@ -1113,13 +707,14 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     e->stdevs.clear();
     fsk_stats& st = e->st;
     st = fsk_stats{};
-    st.n_seq = N; st.n_train = n_train; st.n_test = n_test; st.n_feat = nfeat; st.n_pairs = e->pairs;
-    st.alphabet = (int32_t)sigma; st.bits_per_symbol = bits; st.key_space = (int64_t)V; st.path_used = e->path;
+    st.n_seq = N; st.n_train = n_train; st.n_test = n_test; st.n_feat = plan.nfeat; st.n_pairs = e->pairs;
+    st.alphabet = (int32_t)plan.sigma; st.bits_per_symbol = plan.bits; st.key_space = (int64_t)plan.V; st.path_used = e->path;
     st.n_combos_total = (int32_t)e->ncomb;
     st.max_windows = (double)e->maxW;
-    if (trace_load)
-        fprintf(stderr, "[fsk] load: %lld tokens, lengths %.3f ms, alphabet + packing %.3f ms, plan + uploads enqueued %.3f ms\n", (long long)total,
-                tl_lengths, tl_pack - tl_lengths, tl_ms(tl0) - tl_pack);
+    if (e->trace())
+        fprintf(stderr, "[fsk] load: %lld tokens, lengths %.3f ms, alphabet + packing %.3f ms, plan + uploads enqueued %.3f ms\n", (long long)plan.total,
+                plan.ms_census, plan.ms_pack - plan.ms_census,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count() - plan.ms_pack);
     return FSK_OK;
 }
 
@@ -1540,7 +1135,6 @@ int fsk_get_counts_cells(fsk_engine* e, const int64_t* rows, const int64_t* cols
     }
     return FSK_OK;
 }
-
 
 int fsk_get_stdevs(fsk_engine* e, double* out, int32_t cap, int32_t* n) {
     if (!e || !n) return FSK_EINVAL;
