@@ -252,6 +252,16 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 // Keys are per lane. A wave is 8 row groups x 8 column groups, a 32-lane LDS service group 4 x 8: four (eight) keys of 8 (4)
 // adjacent dwords, which km_swizzle spreads over the banks by the keys' low three bits.
 //
+// Two waves a SIMD (a form of 512 threads with 8 x 4 cells a lane and four waves a SIMD was built and measured: more waves, more
+// instructions a cell, slower: profiles/dense_shift_waves_ab.txt). A wave of this kernel is parked at a wait or the barrier for a
+// third of its cycles, so the step is written for few stops and few instructions:
+//   - the 32 lookups stay in flight: the 16 of the row term are issued before anything is used, the column term's 16 while the
+//     row term is worked on, and each group of 8 is waited for once, with a count (fsk_hw::first_use): 4 waits a step;
+//   - the step table and the row masks of the NEXT step are loaded behind the step's last lookup (they are uniform; a scalar
+//     load in flight shares the LDS reads' counter, returns out of order and turns every wait for an LDS read into a drain);
+//   - (x & m) | 0x10101010 is one v_and_or_b32 (the masks live in registers: the instruction takes no literal), and the two
+//     offsets of a key pair leave their dword, with the lane's term and the stage's base, by one fsk_hw::xor_word each.
+//
 // Byte-parallel sums (m = 0x0f0f0f0f): ((s & m) | 0x10101010) - (d & m) holds four differences + 16, each in [1, 31], no borrow
 // between bytes; the odd nibbles the same after >> 4. Weights are prefix sums, not multiplies: inside a chain
 // sum_u (t1 - u) D_u = sum_r R_r with R_r = sum_{u <= r} D_u, and R stays packed in bytes (R += D': the stored R of step r of a
@@ -262,17 +272,18 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 // Counts above 15: a step runs a second, workgroup-uniform pass when the row mask of EITHER side is set, and that pass reads the
 // key-major HI planes of BOTH sides, staged over the buffer just used, nibble by nibble at 16 x the step's weight (exact, and
 // rare). The unflagged side contributes nothing: k_dense_count writes every hi plane, an unflagged panel's as zeros, and
-// k_dense_keymajor transposes the hi plane unconditionally, so its key-major form is zero too. Loads the compiler can see run one step ahead, as in
-// k_dense_shift_fix. The flush adds, per wave instruction, 8 runs of 8 adjacent cells of K.
+// k_dense_keymajor transposes the hi plane unconditionally, so its key-major form is zero too. The key offsets are loaded one step
+// ahead, as in k_dense_shift_fix. The flush adds, per wave instruction, 8 runs of 8 adjacent cells of K.
 __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* KM, const uint32_t* KMH, const uint32_t* rowmask, const uint32_t* tile_tab,
                                                                const uint32_t* steps, uint32_t n_steps, const uint32_t* offs, uint32_t np_seq,
                                                                int n_slots, uint32_t Vq8, uint32_t n_bases, uint32_t bias, uint32_t N, u64* K) {
     constexpr uint32_t SIDE = 256u * 16u;  // dwords of one staged plane (256 keys at most on this path)
     constexpr uint32_t PBUF = 2u * SIDE;   // dwords per stage buffer: A B
-    constexpr uint32_t M4 = 0x0f0f0f0fu, B4 = 0x10101010u;
     __shared__ __attribute__((aligned(1024))) uint32_t P[2 * PBUF];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+    // (the two masks in registers the compiler cannot see through, one of them scalar: see above)
+    const uint32_t M4 = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(0x0f0f0f0fu)), B4 = fsk_hw::vgpr_copy(0x10101010u);
     const uint32_t tr = (w >> 1) * 8u + (lane >> 3), tc = (w & 1u) * 8u + (lane & 7u);
     const uint32_t tile = tile_tab[blockIdx.x];
     const uint32_t ti = tile >> 16, tj = tile & 0xffffu;
@@ -300,29 +311,31 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
                     fsk_hw::panel_rows_to_lds(src, side_bytes, lds_wave + (buf * PBUF + side * SIDE + q * 1024u) * 4u, q * 4096u + tid * 16u);
         }
     };
-    // a step's key offsets of this lane's 8 rows (oR) and 8 columns (oC), and whether it has rows with counts above 15
-    auto load_meta = [&](uint32_t s, uint32_t sl, uint4 (&oR)[2], uint4 (&oC)[2], uint32_t& fl) {
+    // a step's key offsets of this lane's 8 rows (oR) and 8 columns (oC)
+    auto load_offs = [&](uint32_t s, uint4 (&oR)[2], uint4 (&oC)[2]) {
         const uint32_t* os = offs + (size_t)s * np_seq;
 #pragma unroll
         for (uint32_t h = 0; h < 2u; ++h) {
             oR[h] = *reinterpret_cast<const uint4*>(os + ti * TILE + h * PANEL + 4u * tr);
             oC[h] = *reinterpret_cast<const uint4*>(os + tj * TILE + h * PANEL + 4u * tc);
         }
+    };
+    // whether a step has rows with counts above 15 on either side
+    auto flagged = [&](uint32_t sl) {
         const uint32_t up = sl >> 16, lo = sl & 0xffffu;  // (Vq8 <= 32: one mask word a (panel, slot))
         const uint32_t mA = rowmask[(size_t)(ti * 2u) * n_slots + up] | rowmask[(size_t)(ti * 2u + 1u) * n_slots + up];
         const uint32_t mB = rowmask[(size_t)(tj * 2u) * n_slots + lo] | rowmask[(size_t)(tj * 2u + 1u) * n_slots + lo];
-        fl = mA | mB;
+        return mA | mB;
     };
     auto lds_at = [&](uint32_t byte_off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(P) + byte_off); };
 
-    uint32_t sl_cur = steps[0], wt_cur = steps[1];
-    uint32_t sl_nxt = n_steps > 1u ? steps[2] : 0u, wt_nxt = n_steps > 1u ? steps[3] : 0u;
+    // (the step table runs two steps ahead and the masks one, both loaded at the END of a step and landed by its barrier)
+    uint32_t sl = steps[0], wt = steps[1] & 255u, fl = flagged(sl);
+    uint32_t sn = n_steps > 1u ? steps[2] : 0u, wn = n_steps > 1u ? steps[3] : 0u;
     uint4 oR_n[2], oC_n[2];
-    uint32_t fl_n;
-    load_meta(0u, sl_cur, oR_n, oC_n, fl_n);
-    uint32_t sl_n2 = 0u, wt_n2 = 0u;
+    load_offs(0u, oR_n, oC_n);
     uint32_t buf = 0;
-    load_stage(KM, 0u, (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_cur)));
+    load_stage(KM, 0u, sl);
     fsk_hw::wait_panel_rows();
     __syncthreads();
     for (uint32_t s = 0; s < n_steps; ++s) {
@@ -334,47 +347,54 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             oC[4 * h] = fsk_hw::vgpr_copy(oC_n[h].x); oC[4 * h + 1] = fsk_hw::vgpr_copy(oC_n[h].y);
             oC[4 * h + 2] = fsk_hw::vgpr_copy(oC_n[h].z); oC[4 * h + 3] = fsk_hw::vgpr_copy(oC_n[h].w);
         }
-        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(fl_n));
-        const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_cur));
-        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(wt_cur)) & 255u;
         if (s + 1u < n_steps) {
-            const uint32_t sn = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(sl_nxt));
-            if (s + 2u < n_steps) {
-                sl_n2 = steps[2u * (s + 2u)];
-                wt_n2 = steps[2u * (s + 2u) + 1u];
-            }
-            load_meta(s + 1u, sn, oR_n, oC_n, fl_n);
+            load_offs(s + 1u, oR_n, oC_n);
             load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
         }
         if ((sl & 0xffffu) < n_bases) {  // a new chain: the prefix sums restart
 #pragma unroll
             for (int a = 0; a < 8; ++a) Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
         }
-        // (a staged plane's base inside P is a multiple of 16 KB and a key offset has 14 bits: one xor places both halves)
+        // (a staged plane's base inside P is a multiple of 16 KB and a key offset has 14 bits: the xor places it)
         const uint32_t baseA = buf * PBUF * 4u, baseB = baseA + SIDE * 4u;
-        const uint32_t xA = ((tr * 4u) | baseA) * 0x10001u, xB = ((tc * 4u) | baseB) * 0x10001u;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {  // row term: column ec = e of this lane, its 8 rows
-            const uint32_t x = oC[e] ^ xA;
-            const uint32_t d = lds_at(x & 0xffffu), sg = lds_at(x >> 16);
-            Rr[0][e] += ((sg & M4) | B4) - (d & M4);
-            Rr[1][e] += (((sg >> 4) & M4) | B4) - ((d >> 4) & M4);
+        const uint32_t xA = (tr * 4u) | baseA, xB = (tc * 4u) | baseB;
+        uint32_t dA[8], sA[8], dB[8], sB[8];  // the step's 32 lookups: A[delta], A[sigma] a column, B[delta], B[sigma] a row
+        auto read_A = [&](int e) { dA[e] = lds_at(fsk_hw::xor_word<0>(oC[e], xA)); sA[e] = lds_at(fsk_hw::xor_word<1>(oC[e], xA)); };
+        auto read_B = [&](int e) { dB[e] = lds_at(fsk_hw::xor_word<0>(oR[e], xB)); sB[e] = lds_at(fsk_hw::xor_word<1>(oR[e], xB)); };
+        auto row_term = [&](int e) {  // column ec = e of this lane, its 8 rows
+            Rr[0][e] += ((sA[e] & M4) | B4) - (dA[e] & M4);
+            Rr[1][e] += (((sA[e] >> 4) & M4) | B4) - ((dA[e] >> 4) & M4);
             acc[0][e] = fsk_hw::add_byte<0>(acc[0][e], Rr[0][e]); acc[1][e] = fsk_hw::add_byte<0>(acc[1][e], Rr[1][e]);
             acc[2][e] = fsk_hw::add_byte<1>(acc[2][e], Rr[0][e]); acc[3][e] = fsk_hw::add_byte<1>(acc[3][e], Rr[1][e]);
             acc[4][e] = fsk_hw::add_byte<2>(acc[4][e], Rr[0][e]); acc[5][e] = fsk_hw::add_byte<2>(acc[5][e], Rr[1][e]);
             acc[6][e] = fsk_hw::add_byte<3>(acc[6][e], Rr[0][e]); acc[7][e] = fsk_hw::add_byte<3>(acc[7][e], Rr[1][e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {  // column term: row er = e of this lane, its 8 columns
-            const uint32_t x = oR[e] ^ xB;
-            const uint32_t d = lds_at(x & 0xffffu), sg = lds_at(x >> 16);
-            Rc[0][e] += ((sg & M4) | B4) - (d & M4);
-            Rc[1][e] += (((sg >> 4) & M4) | B4) - ((d >> 4) & M4);
+        };
+        auto col_term = [&](int e) {  // row er = e of this lane, its 8 columns
+            Rc[0][e] += ((sB[e] & M4) | B4) - (dB[e] & M4);
+            Rc[1][e] += (((sB[e] >> 4) & M4) | B4) - ((dB[e] >> 4) & M4);
             acc[e][0] = fsk_hw::add_byte<0>(acc[e][0], Rc[0][e]); acc[e][1] = fsk_hw::add_byte<0>(acc[e][1], Rc[1][e]);
             acc[e][2] = fsk_hw::add_byte<1>(acc[e][2], Rc[0][e]); acc[e][3] = fsk_hw::add_byte<1>(acc[e][3], Rc[1][e]);
             acc[e][4] = fsk_hw::add_byte<2>(acc[e][4], Rc[0][e]); acc[e][5] = fsk_hw::add_byte<2>(acc[e][5], Rc[1][e]);
             acc[e][6] = fsk_hw::add_byte<3>(acc[e][6], Rc[0][e]); acc[e][7] = fsk_hw::add_byte<3>(acc[e][7], Rc[1][e]);
-        }
+        };
+#pragma unroll
+        for (int e = 0; e < 8; ++e) read_A(e);
+        fsk_hw::first_use(dA[0], sA[0], dA[1], sA[1], dA[2], sA[2], dA[3], sA[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) read_B(e);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) row_term(e);
+        fsk_hw::first_use(dA[4], sA[4], dA[5], sA[5], dA[6], sA[6], dA[7], sA[7]);
+#pragma unroll
+        for (int e = 4; e < 8; ++e) read_B(e);
+#pragma unroll
+        for (int e = 4; e < 8; ++e) row_term(e);
+        fsk_hw::first_use(dB[0], sB[0], dB[1], sB[1], dB[2], sB[2], dB[3], sB[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) col_term(e);
+        fsk_hw::first_use(dB[4], sB[4], dB[5], sB[5], dB[6], sB[6], dB[7], sB[7]);
+#pragma unroll
+        for (int e = 4; e < 8; ++e) col_term(e);
         if (fl != 0u) {  // the hi planes over the buffer just used, at 16 x the weight
             __syncthreads();  // everyone is done with the lo planes
             load_stage(KMH, buf, sl);
@@ -383,19 +403,27 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             const uint32_t mul = 16u * wt;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const uint32_t x = oC[e] ^ xA, y = oR[e] ^ xB;
-                const uint32_t dA = lds_at(x & 0xffffu), sA = lds_at(x >> 16), dB = lds_at(y & 0xffffu), sB = lds_at(y >> 16);
+                read_A(e);
+                read_B(e);
 #pragma unroll
                 for (int n = 0; n < 8; ++n) {
-                    acc[n][e] += (((sA >> (4 * n)) & 15u) - ((dA >> (4 * n)) & 15u)) * mul;
-                    acc[e][n] += (((sB >> (4 * n)) & 15u) - ((dB >> (4 * n)) & 15u)) * mul;
+                    acc[n][e] += (((sA[e] >> (4 * n)) & 15u) - ((dA[e] >> (4 * n)) & 15u)) * mul;
+                    acc[e][n] += (((sB[e] >> (4 * n)) & 15u) - ((dB[e] >> (4 * n)) & 15u)) * mul;
                 }
+            }
+        }
+        uint32_t fl_n = 0u, sl_n2 = 0u, wt_n2 = 0u;
+        if (s + 1u < n_steps) {
+            fl_n = flagged(sn);
+            if (s + 2u < n_steps) {
+                sl_n2 = steps[2u * (s + 2u)];
+                wt_n2 = steps[2u * (s + 2u) + 1u];
             }
         }
         fsk_hw::wait_panel_rows();  // this wave's part of the next stage has landed (and every load of this trip)
         __syncthreads();            // ... everyone's has, and everyone is done with the current buffer
-        sl_cur = sl_nxt; wt_cur = wt_nxt;
-        sl_nxt = sl_n2; wt_nxt = wt_n2;
+        sl = sn; wt = wn & 255u; fl = fl_n;
+        sn = sl_n2; wn = wt_n2;
         buf ^= 1u;
     }
 #pragma unroll
