@@ -100,6 +100,16 @@ class SvmCvInfo(C.Structure):
                 ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
 
 
+class SvmPlattInfo(C.Structure):
+    _fields_ = [("A", C.c_double), ("B", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32), ("n_folds", C.c_int32),
+                ("form", C.c_int32), ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["form"] = _FORMS.get(d["form"], "none")
+        return d
+
+
 class MultiInfo(C.Structure):
     _fields_ = [("ndev", C.c_int32), ("devices", C.c_int32 * 16), ("collective", C.c_int32), ("comm_ranks", C.c_int32),
                 ("bands", C.c_int32), ("narrow", C.c_int32), ("reduce_bytes", C.c_int64),
@@ -126,7 +136,9 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_set_complement", "fsk_set_mismatch_weights", "fsk_get_mismatch_info", "fsk_get_mismatch_times", "fsk_mismatch_levels",
            "fsk_set_wildcards", "fsk_set_center_weights", "fsk_svm_train", "fsk_svm_get_model", "fsk_svm_decision",
            "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha", "fsk_rows_build", "fsk_rows_get_block",
-           "fsk_rows_get_block_device", "fsk_rows_get_info", "fsk_svm_set_kernel", "fsk_svm_get_kernel"]
+           "fsk_rows_get_block_device", "fsk_rows_get_info", "fsk_svm_set_kernel", "fsk_svm_get_kernel",
+           "fsk_svm_set_class_weights", "fsk_svm_get_class_weights", "fsk_svm_platt_fit", "fsk_svm_calibrate",
+           "fsk_svm_get_calibration", "fsk_svm_proba"]
 
 
 _hip_shared = False
@@ -191,7 +203,9 @@ def check_single_hip_runtime():
 class Library:
     """The loaded shared library with typed entry points."""
 
-    def __init__(self, path=None):
+    def __init__(self, path=None, optional=()):
+        """``optional``: symbols that an older build of the library may lack (tools that load such a build beside this one);
+        they are left unbound, every other symbol must be there."""
         if path is None:
             share_hip_runtime_with_torch()  # the product library; an explicit path is the CPU emulation of the tests
         path = path or LIB_PATH
@@ -278,8 +292,16 @@ class Library:
             "fsk_rows_get_info": ([vp, C.POINTER(RowsInfo)], C.c_int),
             "fsk_svm_set_kernel": ([vp, i32], C.c_int),
             "fsk_svm_get_kernel": ([vp, C.POINTER(i32)], C.c_int),
+            "fsk_svm_set_class_weights": ([vp, C.c_double, C.c_double], C.c_int),
+            "fsk_svm_get_class_weights": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+            "fsk_svm_platt_fit": ([vp, vp, i64, C.POINTER(SvmPlattInfo)], C.c_int),
+            "fsk_svm_calibrate": ([vp, vp, i32], C.c_int),
+            "fsk_svm_get_calibration": ([vp, vp, C.POINTER(SvmPlattInfo)], C.c_int),
+            "fsk_svm_proba": ([vp, i64, i64, vp], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
+            if name in optional and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = restype
@@ -315,6 +337,26 @@ class Library:
         if rc:
             raise FskError(rc, (self.L.fsk_last_error(None) or b"").decode())
         return [int(v) for v in a[:n.value]]
+
+    def platt_fit(self, dec, labels):
+        """``fsk_svm_platt_fit``: LIBSVM's sigmoid_train on decision values and labels in {-1, +1} (host only). Returns
+        ``A``, ``B`` (P(y = +1 | f) = 1 / (1 + exp(A f + B))), ``iterations`` and ``status`` (0: the gradient fell below 1e-5;
+        1: 100 iterations; 2: the line search failed)."""
+        dec = np.ascontiguousarray(dec, dtype=np.float64)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if dec.ndim != 1 or labels.ndim != 1 or len(dec) != len(labels):
+            raise ValueError("dec and labels must be 1-D and of one length")
+        if len(dec) < 1:
+            raise ValueError("platt_fit: at least one decision value")
+        wrong = np.flatnonzero((labels != 1) & (labels != -1))
+        if len(wrong):
+            raise ValueError("platt_fit: label %d is %d: labels must be -1 or +1" % (wrong[0], labels[wrong[0]]))
+        info = SvmPlattInfo()
+        rc = self.L.fsk_svm_platt_fit(dec.ctypes.data if len(dec) else None, labels.ctypes.data if len(labels) else None, len(dec),
+                                      C.byref(info))
+        if rc:
+            raise FskError(rc, "fsk_svm_platt_fit refused its arguments")
+        return {"A": info.A, "B": info.B, "iterations": info.iterations, "status": info.status}
 
     def tuning_keys(self):
         """{key: (default, lowest, highest, what it does)} — every knob fsk_set_tuning / FSK_TUNING takes."""
@@ -422,6 +464,36 @@ def stratified_folds(labels, k, seed=0):
         fold[t] = c % k
         met[labels[t].item()] = c + 1
     return fold
+
+
+def class_weights(labels, spec):
+    """The ``class_weight=`` keyword -> ``(w_pos, w_neg)`` for ``fsk_svm_set_class_weights`` (host only). ``None``: (1, 1).
+    ``"balanced"``: ``n / (2 n_pos)``, ``n / (2 n_neg)`` as scikit-learn's, computed ONCE from all training labels: the folds
+    of a cross-validation or a calibration solve with these same two weights, they are not recomputed per fold. A pair
+    ``(w_pos, w_neg)``, or a dict keyed by 1 and -1 (a missing key is 1). ``ValueError`` unless both are positive finite
+    numbers."""
+    if spec is None:
+        return 1.0, 1.0
+    if isinstance(spec, str):
+        if spec != "balanced":
+            raise ValueError("class_weight %r: None, \"balanced\", a pair (w_pos, w_neg) or a dict keyed by 1 / -1" % (spec,))
+        labels = np.asarray(labels)
+        n, n_pos = len(labels), int((labels > 0).sum())
+        if n_pos == 0 or n_pos == n:
+            raise ValueError("class_weight=\"balanced\": only one class is present")
+        w = (n / (2.0 * n_pos), n / (2.0 * (n - n_pos)))
+    elif hasattr(spec, "items"):
+        if not set(spec) <= {1, -1}:
+            raise ValueError("class_weight: a dict is keyed by 1 and -1")
+        w = (spec.get(1, 1.0), spec.get(-1, 1.0))
+    else:
+        w = tuple(spec)
+        if len(w) != 2:
+            raise ValueError("class_weight: a pair (w_pos, w_neg)")
+    w = (float(w[0]), float(w[1]))
+    if not all(np.isfinite(x) and x > 0.0 for x in w):
+        raise ValueError("class_weight: the weights must be positive finite numbers, got %r" % (w,))
+    return w
 
 
 def center_profile(plateau, halflife, levels=8, floor=0):
@@ -920,6 +992,45 @@ class Engine:
         v = C.c_int32(0)
         self._ck(self.lib.L.fsk_svm_get_kernel(self.h, C.byref(v)))
         return int(v.value)
+
+    def svm_set_class_weights(self, w_pos, w_neg):
+        """``fsk_svm_set_class_weights``: from now on ``svm_train`` and ``svm_cv`` solve with the boxes ``C w_pos`` for the rows
+        of label +1 and ``C w_neg`` for label -1 (``class_weights(labels, spec)`` makes the pair). A change drops the model,
+        the cross-validation result and the calibration; the weights stay with the handle."""
+        self._ck(self.lib.L.fsk_svm_set_class_weights(self.h, float(w_pos), float(w_neg)))
+
+    def svm_get_class_weights(self):
+        wp, wn = C.c_double(0.0), C.c_double(0.0)
+        self._ck(self.lib.L.fsk_svm_get_class_weights(self.h, C.byref(wp), C.byref(wn)))
+        return wp.value, wn.value
+
+    def svm_calibrate(self, fold, n_folds=None):
+        """``fsk_svm_calibrate``: Platt's sigmoid for the model of ``svm_train``, fitted on the out-of-fold decision values of
+        the folds ``fold[t]`` (0..F-1; F = ``n_folds``, the largest id + 1 when None) solved side by side with the model's C,
+        eps, max_iter, class weights and kernel kind. Returns ``svm_calibration()[1]``."""
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if fold.ndim != 1:
+            raise ValueError("fold must be 1-D")
+        if n_folds is None:
+            n_folds = int(fold.max()) + 1 if len(fold) else 0
+        if len(fold) != self.n_train:
+            raise ValueError("%d fold ids for %d training sequences" % (len(fold), self.n_train))
+        self._ck(self.lib.L.fsk_svm_calibrate(self.h, fold.ctypes.data if len(fold) else None, int(n_folds)))
+        return self.svm_calibration()[1]
+
+    def svm_calibration(self):
+        """(the out-of-fold decision values [n_train], the fit: ``A``, ``B``, ``iterations``, ``status``, ``n_folds``,
+        ``form``, ``launches``, ``ms``) of the last ``svm_calibrate``."""
+        oof = np.empty(self.n_train, dtype=np.float64)
+        info = SvmPlattInfo()
+        self._ck(self.lib.L.fsk_svm_get_calibration(self.h, oof.ctypes.data, C.byref(info)))
+        return oof, info.as_dict()
+
+    def svm_proba(self, r0, r1):
+        """P(y = +1) of rows [r0, r1) of the sequences (train rows first): the calibration's sigmoid of ``svm_decision``."""
+        out = np.empty(max(r1 - r0, 0), dtype=np.float64)
+        self._ck(self.lib.L.fsk_svm_proba(self.h, r0, r1, out.ctypes.data))
+        return out
 
     def svm_cv_alpha(self, p):
         """alpha[n_train] of problem ``p`` of the last ``svm_cv``, zero at its held-out rows."""

@@ -10,6 +10,8 @@
 //     fit_svm(labels, C, eps, max_iter), get_dual_coef_np(), get_intercept(), decision_function_np / _dlpack(which) train
 //     and score a C-SVC on the triangle the compute call left on the device (fsk_svm_train / fsk_svm_decision), and
 //     cross_validate_svm(labels, Cs, folds, ...) cross-validates it over folds and values of C in one batch (fsk_svm_cv);
+//     class_weight= on both gives LIBSVM's weighted C-SVC (fsk_svm_set_class_weights), fit_svm(probability=True) and
+//     predict_proba_np(which) Platt's probabilities (fsk_svm_calibrate / fsk_svm_proba);
 //     both take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
 //     the kernel, through the rows kernel (fsk_rows_build; get_rows_kernel_block_np, rows_kernel_info);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
@@ -587,12 +589,22 @@ public:
         if (kt == "rbf") throw py::value_error("kernel_type=\"rbf\" is not built: a device exp cannot be restated bit for bit; use \"fastsk\" or \"linear\"");
         throw py::value_error("kernel_type must be \"fastsk\" or \"linear\"");
     }
+    // class_weight: None, "balanced" (n / (2 n_pos), n / (2 n_neg), from all the labels, once), a pair (w_pos, w_neg) or a dict
+    // keyed by 1 / -1 (fastsk_amd.class_weights). probability=True: Platt's sigmoid on the out-of-fold decision values of
+    // stratified_folds(labels, calibration_folds, seed) (fsk_svm_calibrate); predict_proba_np then gives P(y = +1).
+    static std::pair<double, double> parse_class_weight(const py::object& labels, const py::object& spec) {
+        return py::module_::import("fastsk_amd._native").attr("class_weights")(labels, spec).cast<std::pair<double, double>>();
+    }
     py::dict fit_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter,
-                     const std::string& kernel_type) {
+                     const std::string& kernel_type, py::object class_weight, bool probability, int32_t calibration_folds, uint64_t seed) {
         const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
+        const std::pair<double, double> w = parse_class_weight(labels, class_weight);
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
+        if (probability) fold = py::module_::import("fastsk_amd._native").attr("stratified_folds")(labels, calibration_folds, seed);
         check(fsk_svm_set_kernel(h_, kind));
+        check(fsk_svm_set_class_weights(h_, w.first, w.second));
         int rc;
         {
             py::gil_scoped_release nogil;
@@ -605,7 +617,21 @@ public:
         py::dict d;
         d["iterations"] = s.iterations; d["gap"] = s.gap; d["objective"] = s.objective; d["n_sv"] = s.n_sv; d["n_bsv"] = s.n_bsv;
         d["converged"] = (bool)s.converged; d["form"] = s.form == 1 ? "workgroup" : "two-launch"; d["launches"] = s.launches;
-        d["ms"] = s.ms; d["kernel_type"] = kernel_type;
+        d["ms"] = s.ms; d["kernel_type"] = kernel_type; d["class_weight"] = py::make_tuple(w.first, w.second);
+        if (probability) {
+            if (fold.ndim() != 1 || fold.shape(0) != labels.shape(0)) throw py::value_error("one fold id per label");
+            {
+                py::gil_scoped_release nogil;
+                rc = fsk_svm_calibrate(h_, fold.data(), calibration_folds);
+            }
+            check(rc);
+            fsk_svm_platt_info q;
+            check(fsk_svm_get_calibration(h_, nullptr, &q));
+            py::dict pl;
+            pl["A"] = q.A; pl["B"] = q.B; pl["iterations"] = q.iterations; pl["status"] = q.status; pl["n_folds"] = q.n_folds;
+            pl["form"] = q.form == 1 ? "workgroup" : "two-launch"; pl["launches"] = q.launches; pl["ms"] = q.ms;
+            d["platt"] = pl;
+        }
         return d;
     }
     // cells [i0, i1) x [j0, j1) of the rows kernel (built if it is not there): L when raw, else K2. Only cells of the result
@@ -636,11 +662,12 @@ public:
     // out-of-fold AUC, the smallest of equals; refit=True then trains the model of fit_svm(labels, C=best_C, eps).
     py::dict cross_validate_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
                                 py::array_t<double, py::array::c_style | py::array::forcecast> Cs, py::object folds, double eps,
-                                int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type) {
+                                int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type, py::object class_weight) {
         const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one of -1 / +1 per training sequence");
         if (Cs.ndim() != 1) throw py::value_error("Cs must be 1-D");
+        const std::pair<double, double> w = parse_class_weight(labels, class_weight);
         py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
         int32_t n_folds = 0;
         if (py::isinstance<py::int_>(folds) && !py::isinstance<py::bool_>(folds)) {
@@ -654,6 +681,7 @@ public:
         const int64_t n = (int64_t)labels.shape(0);
         const int32_t n_C = (int32_t)Cs.shape(0);
         check(fsk_svm_set_kernel(h_, kind));
+        check(fsk_svm_set_class_weights(h_, w.first, w.second));
         int rc;
         {
             py::gil_scoped_release nogil;
@@ -684,7 +712,8 @@ public:
         d["decision"] = oof; d["auc"] = auc; d["accuracy"] = acc; d["problems"] = problems;
         d["form"] = info.form == 1 ? "workgroup" : "two-launch"; d["launches"] = info.launches; d["ms"] = info.ms;
         d["fold"] = fold; d["best_C"] = scores[(size_t)best].C; d["kernel_type"] = kernel_type;
-        if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter, kernel_type);
+        d["class_weight"] = py::make_tuple(w.first, w.second);
+        if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter, kernel_type, py::make_tuple(w.first, w.second), false, 5, 0);
         return d;
     }
     py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
@@ -712,6 +741,14 @@ public:
         decision_rows(which, &r0, &r1);
         py::array_t<double> out((py::ssize_t)(r1 - r0));
         check(fsk_svm_decision(h_, r0, r1, out.mutable_data()));
+        return out;
+    }
+    // P(y = +1) of the test (or train) rows: the calibration's sigmoid of the decision values (fsk_svm_proba), a host array
+    py::array_t<double> predict_proba_np(const std::string& which) const {
+        int64_t r0, r1;
+        decision_rows(which, &r0, &r1);
+        py::array_t<double> out((py::ssize_t)(r1 - r0));
+        check(fsk_svm_proba(h_, r0, r1, out.mutable_data()));
         return out;
     }
     py::capsule decision_function_dlpack(const std::string& which) {
@@ -793,17 +830,19 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("set_combo_order", &FastSK::set_combo_order, py::arg("order"))
         .def("mismatch_info", &FastSK::mismatch_info)
         .def("fit_svm", &FastSK::fit_svm, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3, py::arg("max_iter") = -1,
-             py::arg("kernel_type") = "fastsk")
+             py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none(), py::arg("probability") = false,
+             py::arg("calibration_folds") = 5, py::arg("seed") = 0)
         .def("get_rows_kernel_block_np", &FastSK::get_rows_kernel_block_np, py::arg("i0"), py::arg("i1"), py::arg("j0"), py::arg("j1"),
              py::arg("raw") = false)
         .def("rows_kernel_info", &FastSK::rows_kernel_info)
         .def("cross_validate_svm", &FastSK::cross_validate_svm, py::arg("labels"), py::arg("Cs") = std::vector<double>{1.0},
              py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1, py::arg("seed") = 0, py::arg("refit") = false,
-             py::arg("kernel_type") = "fastsk")
+             py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none())
         .def("get_dual_coef_np", &FastSK::get_dual_coef_np)
         .def("get_intercept", &FastSK::get_intercept)
         .def("decision_function_np", &FastSK::decision_function_np, py::arg("which") = "test")
         .def("decision_function_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
+        .def("predict_proba_np", &FastSK::predict_proba_np, py::arg("which") = "test")
         .def("stats", &FastSK::stats);
     // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
     m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {

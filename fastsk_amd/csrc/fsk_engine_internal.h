@@ -222,11 +222,20 @@ struct SvmState {
     std::vector<signed char> y;      // [n_train], -1 / +1
     double rho = 0;
     int kernel = 0;                  // FSK_SVM_KERNEL_*: what fsk_svm_train / fsk_svm_cv solve on (fsk_svm_set_kernel)
+    double w_pos = 1.0, w_neg = 1.0; // fsk_svm_set_class_weights: every solve's boxes are C w_pos / C w_neg; they stay with the handle
+    double C = 0, eps = 0;           // of the model (fsk_svm_calibrate solves its folds with them)
+    int64_t max_iter = 0;
+    // The calibration of the model (fsk_svm_calibrate): the fold solves' state — a batch like cv's, of its own, so that neither
+    // touches the other — and Platt's sigmoid fitted on its out-of-fold values. It belongs to the model: valid only while the
+    // model is, and a new fsk_svm_train drops it.
+    SvmCvState cal;
+    bool platt_valid = false;
+    fsk_svm_platt_info platt{};
     fsk_svm_info info{};
     DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_out;
     DevBuf<signed char> d_y;
     DevBuf<unsigned char> d_rec;     // the records the launches of a solve hand each other (fsk_kernels_svm.h)
-    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); cv.release(); }
+    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); cv.release(); cal.release(); }
     SvmState() = default;
     SvmState(const SvmState&) = delete;
     SvmState& operator=(const SvmState&) = delete;

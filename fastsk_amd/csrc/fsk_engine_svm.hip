@@ -1,5 +1,6 @@
-// fsk_engine_svm.hip — the SVM stage on the resident result triangle: fsk_svm_train, fsk_svm_get_model, fsk_svm_decision(_device)
-// and fsk_svm_cv, fsk_svm_cv_get(_alpha) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
+// fsk_engine_svm.hip — the SVM stage on the resident result triangle: fsk_svm_train, fsk_svm_get_model, fsk_svm_decision(_device),
+// fsk_svm_cv, fsk_svm_cv_get(_alpha), the class weights (fsk_svm_set_class_weights) and the Platt calibration
+// (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
 // (fastsk.cpp:239-530), for the sequences of one compute call and without the kernel matrix ever leaving the device: the
 // engine's consumer is an SVM, and the triangle it needs is 40 GB at 100,000 sequences.
 //
@@ -50,7 +51,7 @@ static_assert(sizeof(fsk::SvmRecB) <= 256 && sizeof(fsk::SvmRecA) <= 256 && size
 
 // one workgroup, alpha / G / y in LDS: launches of up to `chunk` iterations until the status record says done
 template <typename SrcT>
-int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
+int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
              fsk::SvmRecB* status, int64_t* launches) {
     double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p;  // (plain pointers: a launch takes its arguments by value)
     const signed char* y = e->svm.d_y.p;
@@ -60,7 +61,7 @@ int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, doubl
     if (lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svm_wg needs %zu bytes of LDS for %u rows", lds, n);
     FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svm_wg<SrcT>, lds));
     for (;;) {
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg<SrcT>), dim3(1), dim3(nt), lds, e->stream, K, diag, n, C, eps, (long long)max_iter, chunk,
+        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg<SrcT>), dim3(1), dim3(nt), lds, e->stream, K, diag, n, Cp, Cn, eps, (long long)max_iter, chunk,
                    alpha, G, y, rb);
         ++*launches;
         FSK_HIP(hipMemcpyAsync(status, rb, sizeof *status, hipMemcpyDeviceToHost, e->stream));
@@ -72,7 +73,7 @@ int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, doubl
 
 // two launches an iteration: `chunk` (A, B) pairs between two reads of the status record
 template <typename SrcT>
-int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
+int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
                      uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
     double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p, *krow = e->svm.d_krow.p;  // (plain pointers: a launch takes its arguments by value)
     const signed char* y = e->svm.d_y.p;
@@ -82,9 +83,9 @@ int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t 
     fsk::SvmCandJ* cj = R.cj;
     for (;;) {
         for (uint32_t c = 0; c < chunk; ++c) {
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, C, alpha, G, y,
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, alpha, G, y,
                        (const double*)krow, (const fsk::SvmRecB*)rb, ra, ci, (const fsk::SvmCandJ*)cj, n_wg);
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, C, eps,
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, eps,
                        (long long)max_iter, (const double*)alpha, (const double*)G, y, krow, rb, (const fsk::SvmRecA*)ra,
                        (const fsk::SvmCandI*)ci, cj, n_wg);
             *launches += 2;
@@ -97,22 +98,23 @@ int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t 
 }
 
 template <typename SrcT>
-int solve(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, int form, uint32_t chunk, const SvmRecords& R,
+int solve(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, int form, uint32_t chunk, const SvmRecords& R,
           uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
-    return form == 1 ? solve_wg<SrcT>(e, K, diag, n, C, eps, max_iter, chunk, R, status, launches)
-                     : solve_two_launch<SrcT>(e, K, diag, n, C, eps, max_iter, chunk, R, n_wg, status, launches);
+    return form == 1 ? solve_wg<SrcT>(e, K, diag, n, Cp, Cn, eps, max_iter, chunk, R, status, launches)
+                     : solve_two_launch<SrcT>(e, K, diag, n, Cp, Cn, eps, max_iter, chunk, R, n_wg, status, launches);
 }
 
-// rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in element order; coef[t] = alpha_t y_t
+// rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in element order, the box of an element by its
+// class (Cp, Cn); coef[t] = alpha_t y_t
 struct SvmFinish {
     double rho, objective;
     int64_t n_sv, n_bsv;
 };
-SvmFinish svm_finish(const double* alpha, const double* G, const signed char* y, uint32_t n, double C, double* coef) {
+SvmFinish svm_finish(const double* alpha, const double* G, const signed char* y, uint32_t n, double Cp, double Cn, double* coef) {
     double ub = HUGE_VAL, lb = -HUGE_VAL, sum_free = 0.0, obj = 0.0;
     int64_t n_free = 0, n_sv = 0, n_bsv = 0;
     for (uint32_t t = 0; t < n; ++t) {
-        const double a = alpha[t], yG = y[t] > 0 ? G[t] : -G[t];
+        const double a = alpha[t], yG = y[t] > 0 ? G[t] : -G[t], C = y[t] > 0 ? Cp : Cn;
         if (a >= C) {
             if (y[t] < 0) ub = std::min(ub, yG); else lb = std::max(lb, yG);
         } else if (a <= 0.0) {
@@ -199,7 +201,7 @@ struct SvmBatch {
 size_t svm_batch_record_bytes(uint32_t P, uint32_t total_wg) {
     return (size_t)P * (sizeof(fsk::SvmRecB) + sizeof(fsk::SvmRecA)) + (size_t)total_wg * (sizeof(fsk::SvmCandI) + sizeof(fsk::SvmCandJ));
 }
-static_assert(sizeof(fsk::SvmRecB) % 8 == 0 && sizeof(fsk::SvmRecA) % 8 == 0 && sizeof(fsk::SvmProb) == 32, "batch record layout");
+static_assert(sizeof(fsk::SvmRecB) % 8 == 0 && sizeof(fsk::SvmRecA) % 8 == 0 && sizeof(fsk::SvmProb) == 40, "batch record layout");
 
 // enqueue `chunk` iterations for every problem, read the P status records in one copy, until every problem is done
 template <typename SrcT>
@@ -263,6 +265,253 @@ int cv_ready(fsk_engine* e) {
     return FSK_OK;
 }
 
+// What fsk_svm_cv and fsk_svm_calibrate share — everything but where the result is kept: the checks, the problems
+// p = c n_folds + f ("train at Cs[c] on the rows with fold[t] != f", boxes Cs[c] w_pos / Cs[c] w_neg of the handle's class
+// weights), the batch solved side by side, each problem finished on the host, the out-of-fold decision values and the
+// metrics, all into S. A refused call leaves S as it was.
+int cv_run(fsk_engine* e, SvmCvState& S, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+           double eps, int64_t max_iter) {
+    const double t0 = now_ms();
+    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
+    if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
+    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);
+    if (!labels || !fold || !Cs) return e->fail(FSK_EINVAL, "null labels, fold or Cs");
+    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
+    if ((int64_t)n_C * n_folds > FSK_SVM_CV_MAX_PROBLEMS)
+        return e->fail(FSK_EINVAL, "%d folds x %d values of C are more than %d problems", n_folds, n_C, FSK_SVM_CV_MAX_PROBLEMS);
+    for (int32_t c = 0; c < n_C; ++c)
+        if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
+    const uint32_t F = (uint32_t)n_folds, nC = (uint32_t)n_C, P = F * nC, nn = (uint32_t)n;
+    std::vector<int64_t> rows(F, 0), rows_pos(F, 0);
+    int64_t n_pos = 0;
+    for (int64_t t = 0; t < n; ++t) {
+        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
+        if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
+        ++rows[fold[t]];
+        rows_pos[fold[t]] += labels[t] > 0;
+        n_pos += labels[t] > 0;
+    }
+    for (uint32_t f = 0; f < F; ++f) {
+        if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
+        const int64_t train = n - rows[f], train_pos = n_pos - rows_pos[f];
+        if (train_pos == 0 || train_pos == train) return e->fail(FSK_EINVAL, "the training rows of fold %u are of one class only", f);
+    }
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
+
+    // the problems: fold f's training rows once (idx, y), a slice of state for every (C, f)
+    std::vector<uint32_t> idx;
+    std::vector<signed char> y;
+    std::vector<u64> fold_off(F), st_off(P), idx_off(P);
+    idx.reserve((size_t)(F - 1) * nn);
+    y.reserve((size_t)(F - 1) * nn);
+    for (uint32_t f = 0; f < F; ++f) {
+        fold_off[f] = idx.size();
+        for (uint32_t t = 0; t < nn; ++t)
+            if ((uint32_t)fold[t] != f) { idx.push_back(t); y.push_back((signed char)labels[t]); }
+    }
+    std::vector<fsk::SvmProb> probs(P);
+    uint32_t max_n = 0, total_wg = 0;
+    u64 total = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t f = p % F, np = (uint32_t)(n - rows[f]);
+        probs[p].Cp = Cs[p / F] * e->svm.w_pos;  // (each product once, one rounding)
+        probs[p].Cn = Cs[p / F] * e->svm.w_neg;
+        probs[p].idx_off = idx_off[p] = fold_off[f];
+        probs[p].st_off = st_off[p] = total;
+        probs[p].n = np;
+        probs[p].wg_off = total_wg;
+        total += np;
+        total_wg += (np + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
+        max_n = std::max(max_n, np);
+    }
+    const int form = (int64_t)max_n <= e->tune.svm_wg_max ? 1 : 2;
+    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
+
+    const size_t rec_bytes = svm_batch_record_bytes(P, total_wg);
+    FSK_HIP(S.d_alpha.reserve(total));
+    FSK_HIP(S.d_G.reserve(total));
+    if (form == 2) FSK_HIP(S.d_krow.reserve(total));
+    FSK_HIP(S.d_idx.reserve(idx.size()));
+    FSK_HIP(S.d_y.reserve(y.size()));
+    FSK_HIP(S.d_prob.reserve((size_t)P * sizeof(fsk::SvmProb)));
+    FSK_HIP(S.d_rec.reserve(rec_bytes));
+    FSK_HIP(S.d_coef.reserve((size_t)P * nn));
+    FSK_HIP(S.d_rho.reserve(P));
+    FSK_HIP(S.d_fold.reserve(nn));
+    FSK_HIP(S.d_oof.reserve((size_t)nC * nn));
+    S.valid = false;  // (from here on the earlier result's buffers are written)
+
+    SvmBatch B;
+    B.P = P; B.max_n = max_n; B.max_wg = (max_n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS; B.total_wg = total_wg;
+    B.probs = reinterpret_cast<const fsk::SvmProb*>(S.d_prob.p);
+    B.idx = S.d_idx.p; B.y = S.d_y.p; B.alpha = S.d_alpha.p; B.G = S.d_G.p; B.krow = S.d_krow.p;
+    B.rb = reinterpret_cast<fsk::SvmRecB*>(S.d_rec.p);
+    B.ra = reinterpret_cast<fsk::SvmRecA*>(B.rb + P);
+    B.ci = reinterpret_cast<fsk::SvmCandI*>(B.ra + P);
+    B.cj = reinterpret_cast<fsk::SvmCandJ*>(B.ci + total_wg);
+
+    std::vector<double> G(total, -1.0);
+    FSK_HIP(hipMemcpyAsync(S.d_prob.p, probs.data(), (size_t)P * sizeof(fsk::SvmProb), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_y.p, y.data(), y.size(), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_G.p, G.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_alpha.p, 0, total * sizeof(double), e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_rec.p, 0, rec_bytes, e->stream));  // iter = 0, nothing pending, nobody done
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+
+    std::vector<fsk::SvmRecB> status(P);
+    int64_t launches = 0;
+    const int rc = src.f64 ? solve_batch<double>(e, src.Kf, src.diag, B, eps, max_iter, form, chunk, status, &launches)
+                           : solve_batch<u64>(e, src.Ku, src.diag, B, eps, max_iter, form, chunk, status, &launches);
+    if (rc) return rc;
+    S.alpha.resize(total);
+    FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+
+    // per problem: rho and the objective in element order, the coefficients at full length
+    std::vector<double> coef((size_t)P * nn, 0.0), rho(P), part;
+    S.problems.assign(P, fsk_svm_cv_problem{});
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t np = probs[p].n;
+        part.resize(np);
+        const SvmFinish fin = svm_finish(S.alpha.data() + st_off[p], G.data() + st_off[p], y.data() + idx_off[p], np, probs[p].Cp, probs[p].Cn, part.data());
+        for (uint32_t q = 0; q < np; ++q) coef[(size_t)p * nn + idx[idx_off[p] + q]] = part[q];
+        rho[p] = fin.rho;
+        fsk_svm_cv_problem& o = S.problems[p];
+        o.n_rows = np;
+        o.iterations = status[p].iter;
+        o.gap = status[p].gmax - status[p].gmin;
+        o.objective = fin.objective;
+        o.rho = fin.rho;
+        o.C = Cs[p / F];
+        o.n_sv = fin.n_sv;
+        o.n_bsv = fin.n_bsv;
+        o.converged = status[p].converged;
+        o.fold = (int32_t)(p % F);
+    }
+    FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    {
+        const dim3 grid((nn + 3) / 4, nC);
+        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = src.Kf;
+        const int32_t* df = S.d_fold.p;
+        const u64* Ku = src.Ku;
+        double* out = S.d_oof.p;
+        if (src.f64)
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<double>), grid, dim3(256), 0, e->stream, Kf, diag, dc, dr, df, F, nn, out);
+        else
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<u64>), grid, dim3(256), 0, e->stream, Ku, diag, dc, dr, df, F, nn, out);
+    }
+    S.oof.resize((size_t)nC * nn);
+    FSK_HIP(hipMemcpyAsync(S.oof.data(), S.d_oof.p, S.oof.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+    S.scores.assign(nC, fsk_svm_cv_score{});
+    for (uint32_t c = 0; c < nC; ++c) {
+        S.scores[c].C = Cs[c];
+        cv_metrics(S.oof.data() + (size_t)c * nn, labels, n, &S.scores[c].auc, &S.scores[c].accuracy);
+    }
+    S.idx.swap(idx);
+    S.st_off.swap(st_off);
+    S.idx_off.swap(idx_off);
+    S.info = fsk_svm_cv_info{};
+    S.info.n = n;
+    S.info.n_folds = n_folds;
+    S.info.n_C = n_C;
+    S.info.form = form;
+    S.info.launches = launches;
+    S.info.ms = now_ms() - t0;
+    S.valid = true;
+    return FSK_OK;
+}
+
+// LIBSVM's sigmoid_predict, oriented to P(y = +1): both branches, so that neither exp overflows
+double platt_predict(double f, double A, double B) {
+    const double fApB = f * A + B;
+    if (fApB >= 0) return std::exp(-fApB) / (1.0 + std::exp(-fApB));
+    return 1.0 / (1.0 + std::exp(fApB));
+}
+
+// LIBSVM's sigmoid_train, operation for operation (this file is built without contraction: a * b + c is two roundings)
+void platt_fit(const double* dec, const int32_t* labels, int64_t l, fsk_svm_platt_info* out) {
+    double prior1 = 0, prior0 = 0;
+    for (int64_t i = 0; i < l; ++i) {
+        if (labels[i] > 0) prior1 += 1; else prior0 += 1;
+    }
+    const int max_iter = 100;
+    const double min_step = 1e-10, sigma = 1e-12, eps = 1e-5;
+    const double hiTarget = (prior1 + 1.0) / (prior1 + 2.0), loTarget = 1 / (prior0 + 2.0);
+    std::vector<double> t((size_t)l);
+    double A = 0.0, B = std::log((prior0 + 1.0) / (prior1 + 1.0)), fval = 0.0;
+    for (int64_t i = 0; i < l; ++i) {
+        t[i] = labels[i] > 0 ? hiTarget : loTarget;
+        const double fApB = dec[i] * A + B;
+        if (fApB >= 0) fval += t[i] * fApB + std::log(1 + std::exp(-fApB));
+        else fval += (t[i] - 1) * fApB + std::log(1 + std::exp(fApB));
+    }
+    int iter = 0, status = 1;
+    for (; iter < max_iter; ++iter) {
+        double h11 = sigma, h22 = sigma, h21 = 0.0, g1 = 0.0, g2 = 0.0;
+        for (int64_t i = 0; i < l; ++i) {
+            const double fApB = dec[i] * A + B;
+            double p, q;
+            if (fApB >= 0) {
+                p = std::exp(-fApB) / (1.0 + std::exp(-fApB));
+                q = 1.0 / (1.0 + std::exp(-fApB));
+            } else {
+                p = 1.0 / (1.0 + std::exp(fApB));
+                q = std::exp(fApB) / (1.0 + std::exp(fApB));
+            }
+            const double d2 = p * q;
+            h11 += dec[i] * dec[i] * d2;
+            h22 += d2;
+            h21 += dec[i] * d2;
+            const double d1 = t[i] - p;
+            g1 += dec[i] * d1;
+            g2 += d1;
+        }
+        if (std::fabs(g1) < eps && std::fabs(g2) < eps) { status = 0; break; }
+        const double det = h11 * h22 - h21 * h21;
+        const double dA = -(h22 * g1 - h21 * g2) / det;
+        const double dB = -(-h21 * g1 + h11 * g2) / det;
+        const double gd = g1 * dA + g2 * dB;
+        double stepsize = 1;
+        while (stepsize >= min_step) {
+            const double newA = A + stepsize * dA, newB = B + stepsize * dB;
+            double newf = 0.0;
+            for (int64_t i = 0; i < l; ++i) {
+                const double fApB = dec[i] * newA + newB;
+                if (fApB >= 0) newf += t[i] * fApB + std::log(1 + std::exp(-fApB));
+                else newf += (t[i] - 1) * fApB + std::log(1 + std::exp(fApB));
+            }
+            if (newf < fval + 0.0001 * stepsize * gd) {
+                A = newA; B = newB; fval = newf;
+                break;
+            }
+            stepsize = stepsize / 2.0;
+        }
+        if (stepsize < min_step) { status = 2; break; }
+    }
+    *out = fsk_svm_platt_info{};
+    out->A = A; out->B = B;
+    out->iterations = iter;
+    out->status = status;
+}
+
+int calibration_ready(fsk_engine* e) {
+    int rc = model_ready(e);
+    if (rc) return rc;
+    if (!e->svm.cal.valid || !e->svm.platt_valid) return e->fail(FSK_ESTATE, "no calibration: call fsk_svm_calibrate on the model first");
+    return FSK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -289,6 +538,8 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
 
     SvmState& S = e->svm;
     S.valid = false;
+    S.cal.valid = S.platt_valid = false;  // (the calibration belongs to the model)
+    const double Cp = C * S.w_pos, Cn = C * S.w_neg;  // (each product once, one rounding)
     const uint32_t nn = (uint32_t)n;
     const int form = (int64_t)nn <= e->tune.svm_wg_max ? 1 : 2;
     const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
@@ -313,16 +564,17 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
 
     fsk::SvmRecB status{};
     int64_t launches = 0;
-    const int rc = src.f64 ? solve<double>(e, src.Kf, src.diag, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches)
-                           : solve<u64>(e, src.Ku, src.diag, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches);
+    const int rc = src.f64 ? solve<double>(e, src.Kf, src.diag, nn, Cp, Cn, eps, max_iter, form, chunk, R, n_wg, &status, &launches)
+                           : solve<u64>(e, src.Ku, src.diag, nn, Cp, Cn, eps, max_iter, form, chunk, R, n_wg, &status, &launches);
     if (rc) return rc;
     FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     FSK_HIP(hipStreamSynchronize(e->stream));
 
     std::vector<double> coef(nn);
-    const SvmFinish fin = svm_finish(S.alpha.data(), G.data(), S.y.data(), nn, C, coef.data());
+    const SvmFinish fin = svm_finish(S.alpha.data(), G.data(), S.y.data(), nn, Cp, Cn, coef.data());
     S.rho = fin.rho;
+    S.C = C; S.eps = eps; S.max_iter = max_iter;
     FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice, e->stream));
     FSK_HIP(hipStreamSynchronize(e->stream));
     S.info = fsk_svm_info{};
@@ -376,165 +628,7 @@ int fsk_svm_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* devic
 int fsk_svm_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
                double eps, int64_t max_iter) {
     if (!e) return FSK_EINVAL;
-    const double t0 = now_ms();
-    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
-    if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
-    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);
-    if (!labels || !fold || !Cs) return e->fail(FSK_EINVAL, "null labels, fold or Cs");
-    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
-    if ((int64_t)n_C * n_folds > FSK_SVM_CV_MAX_PROBLEMS)
-        return e->fail(FSK_EINVAL, "%d folds x %d values of C are more than %d problems", n_folds, n_C, FSK_SVM_CV_MAX_PROBLEMS);
-    for (int32_t c = 0; c < n_C; ++c)
-        if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
-    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
-    const uint32_t F = (uint32_t)n_folds, nC = (uint32_t)n_C, P = F * nC, nn = (uint32_t)n;
-    std::vector<int64_t> rows(F, 0), rows_pos(F, 0);
-    int64_t n_pos = 0;
-    for (int64_t t = 0; t < n; ++t) {
-        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
-        if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
-        ++rows[fold[t]];
-        rows_pos[fold[t]] += labels[t] > 0;
-        n_pos += labels[t] > 0;
-    }
-    for (uint32_t f = 0; f < F; ++f) {
-        if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
-        const int64_t train = n - rows[f], train_pos = n_pos - rows_pos[f];
-        if (train_pos == 0 || train_pos == train) return e->fail(FSK_EINVAL, "the training rows of fold %u are of one class only", f);
-    }
-    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
-    FSK_ON_DEVICE(e);
-    { int rcz = materialise_zero(e); if (rcz) return rcz; }
-    SvmSource src;
-    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
-
-    // the problems: fold f's training rows once (idx, y), a slice of state for every (C, f)
-    std::vector<uint32_t> idx;
-    std::vector<signed char> y;
-    std::vector<u64> fold_off(F), st_off(P), idx_off(P);
-    idx.reserve((size_t)(F - 1) * nn);
-    y.reserve((size_t)(F - 1) * nn);
-    for (uint32_t f = 0; f < F; ++f) {
-        fold_off[f] = idx.size();
-        for (uint32_t t = 0; t < nn; ++t)
-            if ((uint32_t)fold[t] != f) { idx.push_back(t); y.push_back((signed char)labels[t]); }
-    }
-    std::vector<fsk::SvmProb> probs(P);
-    uint32_t max_n = 0, total_wg = 0;
-    u64 total = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        const uint32_t f = p % F, np = (uint32_t)(n - rows[f]);
-        probs[p].C = Cs[p / F];
-        probs[p].idx_off = idx_off[p] = fold_off[f];
-        probs[p].st_off = st_off[p] = total;
-        probs[p].n = np;
-        probs[p].wg_off = total_wg;
-        total += np;
-        total_wg += (np + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
-        max_n = std::max(max_n, np);
-    }
-    const int form = (int64_t)max_n <= e->tune.svm_wg_max ? 1 : 2;
-    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
-
-    SvmCvState& S = e->svm.cv;
-    const size_t rec_bytes = svm_batch_record_bytes(P, total_wg);
-    FSK_HIP(S.d_alpha.reserve(total));
-    FSK_HIP(S.d_G.reserve(total));
-    if (form == 2) FSK_HIP(S.d_krow.reserve(total));
-    FSK_HIP(S.d_idx.reserve(idx.size()));
-    FSK_HIP(S.d_y.reserve(y.size()));
-    FSK_HIP(S.d_prob.reserve((size_t)P * sizeof(fsk::SvmProb)));
-    FSK_HIP(S.d_rec.reserve(rec_bytes));
-    FSK_HIP(S.d_coef.reserve((size_t)P * nn));
-    FSK_HIP(S.d_rho.reserve(P));
-    FSK_HIP(S.d_fold.reserve(nn));
-    FSK_HIP(S.d_oof.reserve((size_t)nC * nn));
-    S.valid = false;  // (from here on the earlier result's buffers are written)
-
-    SvmBatch B;
-    B.P = P; B.max_n = max_n; B.max_wg = (max_n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS; B.total_wg = total_wg;
-    B.probs = reinterpret_cast<const fsk::SvmProb*>(S.d_prob.p);
-    B.idx = S.d_idx.p; B.y = S.d_y.p; B.alpha = S.d_alpha.p; B.G = S.d_G.p; B.krow = S.d_krow.p;
-    B.rb = reinterpret_cast<fsk::SvmRecB*>(S.d_rec.p);
-    B.ra = reinterpret_cast<fsk::SvmRecA*>(B.rb + P);
-    B.ci = reinterpret_cast<fsk::SvmCandI*>(B.ra + P);
-    B.cj = reinterpret_cast<fsk::SvmCandJ*>(B.ci + total_wg);
-
-    std::vector<double> G(total, -1.0);
-    FSK_HIP(hipMemcpyAsync(S.d_prob.p, probs.data(), (size_t)P * sizeof(fsk::SvmProb), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemcpyAsync(S.d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemcpyAsync(S.d_y.p, y.data(), y.size(), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemcpyAsync(S.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemcpyAsync(S.d_G.p, G.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemsetAsync(S.d_alpha.p, 0, total * sizeof(double), e->stream));
-    FSK_HIP(hipMemsetAsync(S.d_rec.p, 0, rec_bytes, e->stream));  // iter = 0, nothing pending, nobody done
-    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
-
-    std::vector<fsk::SvmRecB> status(P);
-    int64_t launches = 0;
-    const int rc = src.f64 ? solve_batch<double>(e, src.Kf, src.diag, B, eps, max_iter, form, chunk, status, &launches)
-                           : solve_batch<u64>(e, src.Ku, src.diag, B, eps, max_iter, form, chunk, status, &launches);
-    if (rc) return rc;
-    S.alpha.resize(total);
-    FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    FSK_HIP(hipStreamSynchronize(e->stream));
-
-    // per problem: rho and the objective in element order, the coefficients at full length
-    std::vector<double> coef((size_t)P * nn, 0.0), rho(P), part;
-    S.problems.assign(P, fsk_svm_cv_problem{});
-    for (uint32_t p = 0; p < P; ++p) {
-        const uint32_t np = probs[p].n;
-        part.resize(np);
-        const SvmFinish fin = svm_finish(S.alpha.data() + st_off[p], G.data() + st_off[p], y.data() + idx_off[p], np, probs[p].C, part.data());
-        for (uint32_t q = 0; q < np; ++q) coef[(size_t)p * nn + idx[idx_off[p] + q]] = part[q];
-        rho[p] = fin.rho;
-        fsk_svm_cv_problem& o = S.problems[p];
-        o.n_rows = np;
-        o.iterations = status[p].iter;
-        o.gap = status[p].gmax - status[p].gmin;
-        o.objective = fin.objective;
-        o.rho = fin.rho;
-        o.C = probs[p].C;
-        o.n_sv = fin.n_sv;
-        o.n_bsv = fin.n_bsv;
-        o.converged = status[p].converged;
-        o.fold = (int32_t)(p % F);
-    }
-    FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    {
-        const dim3 grid((nn + 3) / 4, nC);
-        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = src.Kf;
-        const int32_t* df = S.d_fold.p;
-        const u64* Ku = src.Ku;
-        double* out = S.d_oof.p;
-        if (src.f64)
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<double>), grid, dim3(256), 0, e->stream, Kf, diag, dc, dr, df, F, nn, out);
-        else
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<u64>), grid, dim3(256), 0, e->stream, Ku, diag, dc, dr, df, F, nn, out);
-    }
-    S.oof.resize((size_t)nC * nn);
-    FSK_HIP(hipMemcpyAsync(S.oof.data(), S.d_oof.p, S.oof.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    FSK_HIP(hipStreamSynchronize(e->stream));
-    FSK_HIP(hipGetLastError());
-    S.scores.assign(nC, fsk_svm_cv_score{});
-    for (uint32_t c = 0; c < nC; ++c) {
-        S.scores[c].C = Cs[c];
-        cv_metrics(S.oof.data() + (size_t)c * nn, labels, n, &S.scores[c].auc, &S.scores[c].accuracy);
-    }
-    S.idx.swap(idx);
-    S.st_off.swap(st_off);
-    S.idx_off.swap(idx_off);
-    S.info = fsk_svm_cv_info{};
-    S.info.n = n;
-    S.info.n_folds = n_folds;
-    S.info.n_C = n_C;
-    S.info.form = form;
-    S.info.launches = launches;
-    S.info.ms = now_ms() - t0;
-    S.valid = true;
-    return FSK_OK;
+    return cv_run(e, e->svm.cv, labels, n, fold, n_folds, Cs, n_C, eps, max_iter);
 }
 
 int fsk_svm_cv_get(fsk_engine* e, double* oof, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info) {
@@ -558,6 +652,72 @@ int fsk_svm_cv_get_alpha(fsk_engine* e, int32_t p, double* alpha) {
     if (!alpha) return e->fail(FSK_EINVAL, "null output");
     std::fill(alpha, alpha + S.info.n, 0.0);
     for (int64_t q = 0; q < S.problems[p].n_rows; ++q) alpha[S.idx[S.idx_off[p] + q]] = S.alpha[S.st_off[p] + q];
+    return FSK_OK;
+}
+
+int fsk_svm_set_class_weights(fsk_engine* e, double w_pos, double w_neg) {
+    if (!e) return FSK_EINVAL;
+    if (!(w_pos > 0.0) || !std::isfinite(w_pos) || !(w_neg > 0.0) || !std::isfinite(w_neg))
+        return e->fail(FSK_EINVAL, "class weights must be positive finite numbers");
+    SvmState& S = e->svm;
+    if (w_pos != S.w_pos || w_neg != S.w_neg) S.valid = S.cv.valid = S.cal.valid = S.platt_valid = false;  // (a model belongs to its weights)
+    S.w_pos = w_pos;
+    S.w_neg = w_neg;
+    return FSK_OK;
+}
+
+int fsk_svm_get_class_weights(fsk_engine* e, double* w_pos, double* w_neg) {
+    if (!e) return FSK_EINVAL;
+    if (!w_pos || !w_neg) return e->fail(FSK_EINVAL, "null output");
+    *w_pos = e->svm.w_pos;
+    *w_neg = e->svm.w_neg;
+    return FSK_OK;
+}
+
+int fsk_svm_platt_fit(const double* dec, const int32_t* labels, int64_t n, fsk_svm_platt_info* out) {
+    if (!dec || !labels || !out || n < 1) return FSK_EINVAL;
+    for (int64_t t = 0; t < n; ++t)
+        if (labels[t] != 1 && labels[t] != -1) return FSK_EINVAL;
+    platt_fit(dec, labels, n, out);
+    return FSK_OK;
+}
+
+int fsk_svm_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    int rc = model_ready(e);
+    if (rc) return rc;
+    SvmState& S = e->svm;
+    const std::vector<int32_t> labels(S.y.begin(), S.y.end());
+    const double C = S.C;
+    rc = cv_run(e, S.cal, labels.data(), (int64_t)labels.size(), fold, n_folds, &C, 1, S.eps, S.max_iter);
+    if (rc) return rc;
+    S.platt_valid = false;
+    platt_fit(S.cal.oof.data(), labels.data(), (int64_t)labels.size(), &S.platt);
+    S.platt.n_folds = n_folds;
+    S.platt.form = S.cal.info.form;
+    S.platt.launches = S.cal.info.launches;
+    S.platt.ms = now_ms() - t0;
+    S.platt_valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* out) {
+    if (!e) return FSK_EINVAL;
+    int rc = calibration_ready(e);
+    if (rc) return rc;
+    if (oof) memcpy(oof, e->svm.cal.oof.data(), e->svm.cal.oof.size() * sizeof(double));
+    if (out) *out = e->svm.platt;
+    return FSK_OK;
+}
+
+int fsk_svm_proba(fsk_engine* e, int64_t r0, int64_t r1, double* out) {
+    if (!e) return FSK_EINVAL;
+    int rc = calibration_ready(e);
+    if (rc) return rc;
+    rc = fsk_svm_decision(e, r0, r1, out);
+    if (rc) return rc;
+    for (int64_t r = 0; r < r1 - r0; ++r) out[r] = platt_predict(out[r], e->svm.platt.A, e->svm.platt.B);
     return FSK_OK;
 }
 

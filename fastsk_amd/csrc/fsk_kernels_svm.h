@@ -7,11 +7,13 @@
 // very IEEE values the getters hand out, from whichever triangle the result is (u64 counts, fp64 of variance mode).
 //
 // The arithmetic of one iteration is fixed to the operation (tests restate it in numpy and compare bit for bit). With
-// y in {-1, +1}, alpha = 0 and G = -1 at the start, v_t = -y_t G_t:
-//   1. I_up = {y > 0, alpha < C} u {y < 0, alpha > 0}, I_low = {y > 0, alpha > 0} u {y < 0, alpha < C};
+// y in {-1, +1}, alpha = 0 and G = -1 at the start, v_t = -y_t G_t, and the box of row t C_t = Cp where y_t > 0, Cn where
+// y_t < 0 (fsk_svm_set_class_weights: Cp = C w_pos, Cn = C w_neg, each rounded once on the host; two kernel arguments, chosen
+// by y in registers — with equal weights every C_t is the one C and C_i - C_j is 0.0):
+//   1. I_up = {y > 0, alpha < C_t} u {y < 0, alpha > 0}, I_low = {y > 0, alpha > 0} u {y < 0, alpha < C_t};
 //      i = argmax v over I_up, Gmax = v_i, Gmin = min v over I_low; stop when Gmax - Gmin <= eps (then: at max_iter);
 //   2. b_t = Gmax - v_t, a_t = K_ii + K_tt - 2 K_it = 2 - 2 K_it (TAU where <= 0): j = argmin over I_low, b_t > 0, of -(b_t b_t) / a_t;
-//   3. the two-variable step and its clipping to [0, C]^2 as in LIBSVM's Solver::Solve (svm_step);
+//   3. the two-variable step and its clipping to [0, C_i] x [0, C_j] as in LIBSVM's Solver::Solve (svm_step);
 //   4. G_t = G_t + ((Q_it dalpha_i) + (Q_jt dalpha_j)), Q_it = y_i y_t K_it.
 // Every tie goes to the lowest index: (value, index) compared lexicographically is associative, so neither the shape of a
 // reduction tree nor the grid shows in the result. Products and sums are the __d*_rn forms: no contraction.
@@ -59,8 +61,10 @@ __device__ __forceinline__ double svm_cell(const SrcT* K, const double* diag, ui
 }
 
 __device__ __forceinline__ double svm_inf() { return __builtin_huge_val(); }
-__device__ __forceinline__ bool svm_in_up(int y, double a, double C) { return y > 0 ? a < C : a > 0.0; }
-__device__ __forceinline__ bool svm_in_low(int y, double a, double C) { return y > 0 ? a > 0.0 : a < C; }
+__device__ __forceinline__ double svm_box(int y, double Cp, double Cn) { return y > 0 ? Cp : Cn; }  // C_t
+// (a set tests alpha against one box only: I_up that of the positives, I_low that of the negatives)
+__device__ __forceinline__ bool svm_in_up(int y, double a, double Cp) { return y > 0 ? a < Cp : a > 0.0; }
+__device__ __forceinline__ bool svm_in_low(int y, double a, double Cn) { return y > 0 ? a > 0.0 : a < Cn; }
 __device__ __forceinline__ double svm_v(int y, double G) { return y > 0 ? -G : G; }
 // (value, index) orders: the larger value / the smaller value first, then the lower index
 __device__ __forceinline__ bool svm_better_max(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -75,12 +79,16 @@ __device__ __forceinline__ bool svm_j_objective(double gmax, double v, double ki
     return true;
 }
 
-// Step 3: LIBSVM's Solver::Solve for one pair with Q_ii = Q_jj = 1 and C_i = C_j = C; Qij = y_i y_j K_ij. ai, aj: in the old
-// values, out the new ones.
-__device__ __forceinline__ void svm_step(int yi, int yj, double Kij, double Gi, double Gj, double C, double* ai, double* aj) {
+// Step 3: LIBSVM's Solver::Solve for one pair with Q_ii = Q_jj = 1, C_i and C_j by class; Qij = y_i y_j K_ij. ai, aj: in the
+// old values, out the new ones.
+__device__ __forceinline__ void svm_step(int yi, int yj, double Kij, double Gi, double Gj, double Cp, double Cn, double* ai, double* aj) {
     const double Qij = yi == yj ? Kij : -Kij;
     double a_i = *ai, a_j = *aj;
     if (yi != yj) {
+        // (two classes: C_j is the other box, and C_i - C_j is Cp - Cn or its exact negative — one subtraction that does not
+        // depend on the pair, so it stays out of the step's chain)
+        const double dPN = __dsub_rn(Cp, Cn);
+        const double Ci = yi > 0 ? Cp : Cn, Cj = yi > 0 ? Cn : Cp, dC = yi > 0 ? dPN : -dPN;
         double quad = __dadd_rn(2.0, __dmul_rn(2.0, Qij));
         if (quad <= 0.0) quad = SVM_TAU;
         const double delta = __ddiv_rn(__dsub_rn(-Gi, Gj), quad);
@@ -92,12 +100,13 @@ __device__ __forceinline__ void svm_step(int yi, int yj, double Kij, double Gi, 
         } else {
             if (a_i < 0.0) { a_i = 0.0; a_j = -diff; }
         }
-        if (diff > 0.0) {  // (C_i - C_j = 0)
-            if (a_i > C) { a_i = C; a_j = __dsub_rn(C, diff); }
+        if (diff > dC) {  // (C_i - C_j; 0.0 with equal weights)
+            if (a_i > Ci) { a_i = Ci; a_j = __dsub_rn(Ci, diff); }
         } else {
-            if (a_j > C) { a_j = C; a_i = __dadd_rn(C, diff); }
+            if (a_j > Cj) { a_j = Cj; a_i = __dadd_rn(Cj, diff); }
         }
     } else {
+        const double C = svm_box(yi, Cp, Cn);  // (one class: C_i = C_j)
         double quad = __dsub_rn(2.0, __dmul_rn(2.0, Qij));
         if (quad <= 0.0) quad = SVM_TAU;
         const double delta = __ddiv_rn(__dsub_rn(Gi, Gj), quad);
@@ -177,7 +186,7 @@ __host__ __device__ inline size_t svm_wg_lds(uint32_t n, uint32_t nt) {
 // loaded from and written back to device memory around them, so no launch runs unbounded. Element e belongs to thread
 // e mod blockDim.x, which alone writes its alpha and G. Seven barriers an iteration (two a reduction, one before the writes).
 template <typename SrcT>
-__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const double* diag, uint32_t n, double C, double eps,
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
                                                            long long max_iter, uint32_t chunk, double* alpha, double* G,
                                                            const signed char* y, SvmRecB* rec) {
     FSK_DYN_SHARED(unsigned char, smem);
@@ -207,8 +216,8 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
         for (uint32_t e = tid; e < n; e += nt) {
             const int ye = sY[e];
             const double a = sA[e], v = svm_v(ye, sG[e]);
-            if (svm_in_up(ye, a, C) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
-            if (svm_in_low(ye, a, C) && v < vmin) vmin = v;
+            if (svm_in_up(ye, a, Cp) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
+            if (svm_in_low(ye, a, Cn) && v < vmin) vmin = v;
         }
         svm_reduce<true>(red, &vmax, &imax, &none);
         int at = 0;
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
                 kit[q] = svm_cell(K, diag, i, e);
                 const int ye = sY[e];
                 double o;
-                if (svm_in_low(ye, sA[e], C) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
+                if (svm_in_low(ye, sA[e], Cn) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
             }
         }
         svm_reduce<false>(red, &obj, &j, &none);
@@ -240,7 +249,7 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
         const int yi = sY[i], yj = sY[j];
         const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
         double ai = ai0, aj = aj0;
-        svm_step(yi, yj, svm_cell(K, diag, i, (uint32_t)j), Gi, Gj, C, &ai, &aj);
+        svm_step(yi, yj, svm_cell(K, diag, i, (uint32_t)j), Gi, Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
         __syncthreads();  // (everybody has read alpha and G of i and j)
         // ---- 4. G, alpha
@@ -272,7 +281,7 @@ constexpr int SVM_THREADS = 256;
 // LAUNCH A: finish the pending step — j from the workgroups' candidates, the scalar step, this workgroup's slice of G, alpha
 // of i and j by the workgroups that hold them — then this workgroup's share of the next step 1.
 template <typename SrcT>
-__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, const double* diag, uint32_t n, double C, double* alpha,
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double* alpha,
                                                               double* G, const signed char* y, const double* krow,
                                                               const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i,
                                                               const SvmCandJ* cand_j, uint32_t n_wg) {
@@ -304,7 +313,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, con
         const SvmCandJ cj = cand_j[w];
         const int i = rb->i, yi = rb->yi;
         double ai = rb->ai, aj = cj.aj;
-        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, C, &ai, &aj);
+        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
         if (mine) {
             g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, (uint32_t)j, t), dai, daj);
@@ -317,8 +326,8 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, con
     const double v = svm_v(yt, g);
     double vmax = -svm_inf(), vmin = svm_inf();
     int imax = SVM_NONE, none = 0, at = 0;
-    if (mine && svm_in_up(yt, a, C)) { vmax = v; imax = (int)t; }
-    if (mine && svm_in_low(yt, a, C)) vmin = v;
+    if (mine && svm_in_up(yt, a, Cp)) { vmax = v; imax = (int)t; }
+    if (mine && svm_in_low(yt, a, Cn)) vmin = v;
     svm_reduce<true>(red, &vmax, &imax, &none);
     svm_reduce<false>(red, &vmin, &at, &none);
     if (tid == 0) {
@@ -330,7 +339,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, con
 // LAUNCH B: i, Gmax and Gmin from the workgroups' candidates; the stop tests; row i (kept in krow for launch A), this
 // workgroup's candidate for j.
 template <typename SrcT>
-__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, const double* diag, uint32_t n, double C, double eps,
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
                                                               long long max_iter, const double* alpha, const double* G,
                                                               const signed char* y, double* krow, SvmRecB* rb, const SvmRecA* ra,
                                                               const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
@@ -370,7 +379,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, con
         krow[t] = kit;
         yt = (int)y[t]; a = alpha[t]; g = G[t];
         double o;
-        if (svm_in_low(yt, a, C) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
+        if (svm_in_low(yt, a, Cn) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
     }
     svm_reduce<false>(red, &obj, &j, &none);
     if (j == SVM_NONE) {
@@ -412,11 +421,11 @@ __global__ __launch_bounds__(256) void k_svm_decision(const SrcT* K, const doubl
 // =============================================================================================
 // A BATCH OF PROBLEMS ON ONE TRIANGLE (fsk_svm_cv: folds x values of C). Problem p is n of the training rows — element e is
 // row idx[e], the list strictly ascending, so the lowest element is the lowest row and every tie falls as in the single
-// solve on the sub-matrix — with labels and C of its own. The kernels below are the three above with the problem as one
+// solve on the sub-matrix — with labels and Cp, Cn of its own. The kernels below are the three above with the problem as one
 // more grid dimension and every cell read through idx; the arithmetic of an iteration is the same to the operation. They
 // are kernels of their own, not a mode of the single-problem ones: those keep their code and their launches.
 struct SvmProb {
-    double C;
+    double Cp, Cn;               // the boxes of its rows of label +1 / -1
     unsigned long long idx_off;  // idx and y of the problem start here (the problems of one fold share them)
     unsigned long long st_off;   // alpha, G and the kept row of the problem start here
     uint32_t n;                  // elements
@@ -436,7 +445,7 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, 
     if (rec->done) return;  // (the whole workgroup: nobody writes the record before the end of the launch)
     const SvmProb pr = probs[blockIdx.x];
     const uint32_t tid = threadIdx.x, nt = blockDim.x, n = pr.n;
-    const double C = pr.C;
+    const double Cp = pr.Cp, Cn = pr.Cn;
     const uint32_t* idx = idx_all + pr.idx_off;
     const signed char* y = y_all + pr.idx_off;
     double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
@@ -465,8 +474,8 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, 
         for (uint32_t e = tid; e < n; e += nt) {
             const int ye = sY[e];
             const double a = sA[e], v = svm_v(ye, sG[e]);
-            if (svm_in_up(ye, a, C) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
-            if (svm_in_low(ye, a, C) && v < vmin) vmin = v;
+            if (svm_in_up(ye, a, Cp) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
+            if (svm_in_low(ye, a, Cn) && v < vmin) vmin = v;
         }
         svm_reduce<true>(red, &vmax, &imax, &none);
         int at = 0;
@@ -490,7 +499,7 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, 
                 kit[q] = svm_cell(K, diag, ri, row[q]);
                 const int ye = sY[e];
                 double o;
-                if (svm_in_low(ye, sA[e], C) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
+                if (svm_in_low(ye, sA[e], Cn) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
             }
         }
         svm_reduce<false>(red, &obj, &j, &none);
@@ -500,7 +509,7 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, 
         const int yi = sY[i], yj = sY[j];
         const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
         double ai = ai0, aj = aj0;
-        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, C, &ai, &aj);
+        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
         __syncthreads();  // (everybody has read alpha and G of i and j)
         // ---- 4. G, alpha
@@ -538,7 +547,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i_batch(const SrcT* 
     const SvmProb pr = probs[blockIdx.y];
     const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
     if (blockIdx.x >= n_wg) return;
-    const double C = pr.C;
+    const double Cp = pr.Cp, Cn = pr.Cn;
     const uint32_t* idx = idx_all + pr.idx_off;
     const signed char* y = y_all + pr.idx_off;
     double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
@@ -572,7 +581,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i_batch(const SrcT* 
         const SvmCandJ cj = cand_j[w];
         const int i = rb->i, yi = rb->yi;
         double ai = rb->ai, aj = cj.aj;
-        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, C, &ai, &aj);
+        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
         if (mine) {
             g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, idx[j], idx[t]), dai, daj);
@@ -585,8 +594,8 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i_batch(const SrcT* 
     const double v = svm_v(yt, g);
     double vmax = -svm_inf(), vmin = svm_inf();
     int imax = SVM_NONE, none = 0, at = 0;
-    if (mine && svm_in_up(yt, a, C)) { vmax = v; imax = (int)t; }
-    if (mine && svm_in_low(yt, a, C)) vmin = v;
+    if (mine && svm_in_up(yt, a, Cp)) { vmax = v; imax = (int)t; }
+    if (mine && svm_in_low(yt, a, Cn)) vmin = v;
     svm_reduce<true>(red, &vmax, &imax, &none);
     svm_reduce<false>(red, &vmin, &at, &none);
     if (tid == 0) {
@@ -607,7 +616,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j_batch(const SrcT* 
     const SvmProb pr = probs[blockIdx.y];
     const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
     if (blockIdx.x >= n_wg) return;
-    const double C = pr.C;
+    const double Cp = pr.Cp, Cn = pr.Cn;
     const uint32_t* idx = idx_all + pr.idx_off;
     const signed char* y = y_all + pr.idx_off;
     const double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
@@ -648,7 +657,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j_batch(const SrcT* 
         krow[t] = kit;
         yt = (int)y[t]; a = alpha[t]; g = G[t];
         double o;
-        if (svm_in_low(yt, a, C) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
+        if (svm_in_low(yt, a, Cn) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
     }
     svm_reduce<false>(red, &obj, &j, &none);
     if (j == SVM_NONE) {

@@ -38,7 +38,9 @@ extern "C" {
                                   fsk_svm_train, fsk_svm_get_model, fsk_svm_decision, fsk_svm_decision_device and fsk_svm_info;
                                   fsk_svm_cv, fsk_svm_cv_get, fsk_svm_cv_get_alpha and their three structs;
                                   fsk_rows_build, fsk_rows_get_block(_device), fsk_rows_get_info and fsk_rows_info,
-                                  fsk_svm_set_kernel / fsk_svm_get_kernel) */
+                                  fsk_svm_set_kernel / fsk_svm_get_kernel;
+                                  fsk_svm_set_class_weights / fsk_svm_get_class_weights, fsk_svm_platt_fit, fsk_svm_calibrate,
+                                  fsk_svm_get_calibration, fsk_svm_proba and fsk_svm_platt_info) */
 
 enum {
     FSK_OK = 0,
@@ -423,7 +425,7 @@ typedef struct fsk_svm_info {
     int64_t iterations;      /* two-variable steps taken                                                    */
     double gap;              /* Gmax - Gmin of the last selection                                           */
     double objective;        /* dual objective 1/2 sum alpha_t (G_t - 1)                                    */
-    int64_t n_sv, n_bsv;     /* alpha_t > 0; alpha_t >= C                                                   */
+    int64_t n_sv, n_bsv;     /* alpha_t > 0; alpha_t >= C_t (C, or the class's box under class weights)     */
     int32_t converged;       /* 1: gap <= eps; 0: max_iter reached first                                    */
     int32_t form;            /* 1: one workgroup (k_svm_wg); 2: two launches an iteration                   */
     int64_t launches;        /* kernel launches of the solve                                                */
@@ -528,6 +530,51 @@ int fsk_rows_get_block_device(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0,
 int fsk_rows_get_info(fsk_engine* e, fsk_rows_info* out);
 int fsk_svm_set_kernel(fsk_engine* e, int32_t kind);
 int fsk_svm_get_kernel(fsk_engine* e, int32_t* kind);
+
+/* ---- class weights and Platt probabilities: what the reference's svm_parameter carries as weight_label / weight and
+ * probability = 1 (fastsk.hpp:26-30, fastsk.cpp:269-281), on the resident triangle.
+ *
+ * fsk_svm_set_class_weights: from then on fsk_svm_train and every problem of fsk_svm_cv solve LIBSVM's weighted C-SVC: the box
+ * of row t is C_t = Cp = C w_pos where labels[t] = +1 and Cn = C w_neg where it is -1, each product formed once on the host
+ * (one rounding). The algorithm is fsk_svm_train's with C_t in place of C: I_up and I_low test alpha_t against C_t; a step of
+ * two rows of one class clips with that class's box; a step of two classes clips, after the clips at zero, by
+ * `if (diff > C_i - C_j) { if (alpha_i > C_i) ... } else { if (alpha_j > C_j) ... }`, C_i - C_j one correctly rounded subtraction
+ * (0.0 with equal weights: the code path is the unweighted one, to the bit and to the launch). rho's free support vectors are
+ * 0 < alpha_t < C_t, its bounds and n_bsv count alpha_t >= C_t. The default is (1, 1). The weights stay with the handle, as
+ * the kind of fsk_svm_set_kernel does; a call that changes them drops the model, the cross-validation result and the
+ * calibration, a call with the values in force drops nothing. FSK_EINVAL unless both are positive finite numbers. */
+int fsk_svm_set_class_weights(fsk_engine* e, double w_pos, double w_neg);
+int fsk_svm_get_class_weights(fsk_engine* e, double* w_pos, double* w_neg);
+/* fsk_svm_platt_fit: LIBSVM's sigmoid_train (Lin, Lin and Weng's form of Platt's fit) on n decision values and labels in
+ * {-1, +1}, host only, no device and no handle: targets (n_pos + 1) / (n_pos + 2) and 1 / (n_neg + 2), start A = 0,
+ * B = log((n_neg + 1) / (n_pos + 1)), Newton's method on H + 1e-12 I with a backtracking line search (sufficient decrease
+ * 0.0001, smallest step 1e-10), at most 100 iterations, stop when both gradient entries are below 1e-5 — in LIBSVM's order
+ * of operations, sums in index order, every operation a single correctly rounded double one, exp and log from libm.
+ * FSK_EINVAL on a null pointer, n < 1 or a label that is not -1 or +1 (no message: there is no handle).
+ * fsk_svm_calibrate: needs the model of fsk_svm_train (FSK_ESTATE before one). Solves, with the model's labels, C, eps,
+ * max_iter, class weights and kernel kind, the n_folds problems "train on the rows with fold[t] != f" side by side — the
+ * batch of fsk_svm_cv at the one C: same kernels, same choice of form — computes the out-of-fold decision values as
+ * fsk_svm_cv does and runs fsk_svm_platt_fit on them. FSK_EINVAL, with fsk_svm_cv's messages: a fold id out of range, a fold
+ * without rows, a fold whose training rows are of one class, n_folds < 2; a refused call leaves an earlier calibration. It
+ * neither needs nor changes a stored cross-validation result, and fsk_svm_cv does not touch the calibration. The calibration
+ * belongs to the model: whatever drops the model drops it, and so does a new fsk_svm_train.
+ * fsk_svm_get_calibration: the out-of-fold decision values (n_train, may be NULL) and the fit (may be NULL).
+ * fsk_svm_proba: P(y = +1) of rows r0 <= r < r1 <= N into a HOST array: fsk_svm_decision's values f, then LIBSVM's
+ * sigmoid_predict on the host: with fApB = f A + B, exp(-fApB) / (1 + exp(-fApB)) where fApB >= 0, else 1 / (1 + exp(fApB)).
+ * FSK_ESTATE without a calibration; range errors as fsk_svm_decision. */
+typedef struct fsk_svm_platt_info {
+    double A, B;             /* P(y = +1 | f) = 1 / (1 + exp(A f + B))                                       */
+    int32_t iterations;      /* Newton iterations taken                                                     */
+    int32_t status;          /* 0: gradient below 1e-5; 1: 100 iterations; 2: line search failed            */
+    int32_t n_folds, form;   /* of the fold solves (form as in fsk_svm_cv_info); 0 from fsk_svm_platt_fit   */
+    int64_t launches;        /* kernel launches of the fold solves                                          */
+    double ms;               /* host time of fsk_svm_calibrate                                              */
+    double reserved[4];
+} fsk_svm_platt_info;
+int fsk_svm_platt_fit(const double* dec, const int32_t* labels, int64_t n, fsk_svm_platt_info* out);
+int fsk_svm_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds);
+int fsk_svm_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* out);
+int fsk_svm_proba(fsk_engine* e, int64_t r0, int64_t r1, double* out);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
