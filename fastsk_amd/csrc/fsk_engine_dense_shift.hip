@@ -168,7 +168,8 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
         slot0 = end;
     }
     if (e->shift_packed) {
-        FSK_LAUNCH(fsk::k_dense_shift_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
+        const auto k_packed = e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true> : fsk::k_dense_shift_packed<false>;
+        FSK_LAUNCH(k_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
                    (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, p.n_bases, (uint32_t)(32u * p.wsum), (uint32_t)e->N, K);
     } else {

@@ -95,6 +95,7 @@ using fsk_detail::DevBuf;
     X(dense_small, 0, 0, 1, "dense: 1 = a split tile launch (small N) leaves its sums as 32-bit staging blocks that k_dense_widen adds into K (0: one 64-bit atomic a cell and split — measured faster: the atomics drain under other workgroups' dot products)")                                        \
     X(dense_shift, 0, -1, 1, "dense: one weighted Gram product per chain of shifted combinations, the other members by edge lookups (fsk_engine_dense_shift.hip) — 1 = whenever the call is eligible, -1 = never (0: when eligible, tile_splits = 0 and the launch has 16384 tiles or more, the size from which a tile has one workgroup anyway)") \
     X(dense_shift_packed, 0, -1, 0, "dense, shift classes: the derived steps from key-major planes, eight cells an LDS read (k_dense_keymajor, k_dense_shift_packed; chains cut at nine members) — 0 = whenever the shift path runs and the planes fit, -1 = never: k_dense_shift_fix on the count panels") \
+    X(dense_shift_inplace, 1, 0, 1, "dense, shift classes: k_dense_shift_packed stages a chain's first planes and makes every further step's in LDS, one nibble up and one down a sequence (a step that meets a count above 15 in its tile, and the step behind it, are staged) — 0 = every step staged") \
     X(dense_shift_plane_kb, 0, 0, (int64_t)1 << 40, "dense, shift classes: the key-major planes and offsets may take this many KiB at most (0: half of the free memory; tests: the planes do not fit)") \
     X(dense_chunk, 0, 0, 1 << 24, "dense: cap of the count kernel's staging chunk, in windows (0: none)")                             \
     X(variance_dense_slots, 1, 0, 1, "variance mode, dense: 0 = zero fill + k_welford per iteration instead of storing slot triangles") \

@@ -274,6 +274,19 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 // rare). The unflagged side contributes nothing: k_dense_count writes every hi plane, an unflagged panel's as zeros, and
 // k_dense_keymajor transposes the hi plane unconditionally, so its key-major form is zero too. The key offsets are loaded one step
 // ahead, as in k_dense_shift_fix. The flush adds, per wave instruction, 8 runs of 8 adjacent cells of K.
+//
+// INPLACE (tuning dense_shift_inplace, the default): where step s + 1 continues the chain of step s and neither step is flagged,
+// its planes are not staged but MADE in LDS from the ones step s looked up, by the identity at the head of this file:
+//   A holds c_up(s)  and becomes c_up(s + 1) = c_up(s) + e(sigma) - e(delta) with the keys of step s + 1 of the tile's 128 rows,
+//   B holds c_lo(s)  and becomes c_lo(s + 1) = c_up(s) = c_lo(s) + e(sigma) - e(delta) with the keys of step s of its 128 columns.
+// Thread q < 128 owns row-side position q, thread 128 + q column-side position q: one dword of `offs`, and two atomic adds of
+// 1 << 4 e (the second negated) on LDS dwords off ^ 4 t, for position p = 64 h + 4 t + x = nibble e = 4 h + x of dword t — up to 8
+// positions share a dword. A position whose two offsets are equal adds nothing (sigma = delta; a padded row or a sequence without
+// a window: 0 | 0, whose zero plane stays zero). A nibble never leaves [0, 15]: both steps are unflagged, so every count of the four
+// planes is below 16. A barrier ends the lookups, the next ends the updates. A chain's first step, a flagged step and the step
+// behind a flagged one (whose buffer the hi planes took) are staged as before; the planes in memory are never written. The step
+// table runs three steps ahead and the masks two, so that a step knows at its head whether the next one is flagged.
+template <bool INPLACE>
 __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* KM, const uint32_t* KMH, const uint32_t* rowmask, const uint32_t* tile_tab,
                                                                const uint32_t* steps, uint32_t n_steps, const uint32_t* offs, uint32_t np_seq,
                                                                int n_slots, uint32_t Vq8, uint32_t n_bases, uint32_t bias, uint32_t N, u64* K) {
@@ -332,6 +345,11 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
     // (the step table runs two steps ahead and the masks one, both loaded at the END of a step and landed by its barrier)
     uint32_t sl = steps[0], wt = steps[1] & 255u, fl = flagged(sl);
     uint32_t sn = n_steps > 1u ? steps[2] : 0u, wn = n_steps > 1u ? steps[3] : 0u;
+    uint32_t s2 = 0u, w2 = 0u, fl_nx = 0u;  // (in place: the table entry of step s + 2 and the masks of step s + 1, at the head of step s)
+    if constexpr (INPLACE) {
+        if (n_steps > 2u) { s2 = steps[4]; w2 = steps[5]; }
+        if (n_steps > 1u) fl_nx = flagged(sn);
+    }
     uint4 oR_n[2], oC_n[2];
     load_offs(0u, oR_n, oC_n);
     uint32_t buf = 0;
@@ -347,9 +365,14 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             oC[4 * h] = fsk_hw::vgpr_copy(oC_n[h].x); oC[4 * h + 1] = fsk_hw::vgpr_copy(oC_n[h].y);
             oC[4 * h + 2] = fsk_hw::vgpr_copy(oC_n[h].z); oC[4 * h + 3] = fsk_hw::vgpr_copy(oC_n[h].w);
         }
+        // the next step's planes are made from this step's: it continues the chain, and neither step has a count above 15
+        const bool same = INPLACE && s + 1u < n_steps && (sn & 0xffffu) >= n_bases && fl == 0u && fl_nx == 0u;
+        uint32_t uo_n = 0u;
         if (s + 1u < n_steps) {
             load_offs(s + 1u, oR_n, oC_n);
-            load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
+            // (thread q < 128: row-side position q, the keys of step s + 1; thread 128 + q: column-side position q, the keys of step s)
+            if (same) uo_n = offs[(size_t)(w < 2u ? s + 1u : s) * np_seq + (w < 2u ? ti : tj) * TILE + (tid & 127u)];
+            else load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
         }
         if ((sl & 0xffffu) < n_bases) {  // a new chain: the prefix sums restart
 #pragma unroll
@@ -413,7 +436,15 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             }
         }
         uint32_t fl_n = 0u, sl_n2 = 0u, wt_n2 = 0u;
-        if (s + 1u < n_steps) {
+        if constexpr (INPLACE) {  // the masks of step s + 2, the table entry of step s + 3
+            if (s + 2u < n_steps) {
+                fl_n = flagged(s2);
+                if (s + 3u < n_steps) {
+                    sl_n2 = steps[2u * (s + 3u)];
+                    wt_n2 = steps[2u * (s + 3u) + 1u];
+                }
+            }
+        } else if (s + 1u < n_steps) {
             fl_n = flagged(sn);
             if (s + 2u < n_steps) {
                 sl_n2 = steps[2u * (s + 2u)];
@@ -422,9 +453,26 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
         }
         fsk_hw::wait_panel_rows();  // this wave's part of the next stage has landed (and every load of this trip)
         __syncthreads();            // ... everyone's has, and everyone is done with the current buffer
-        sl = sn; wt = wn & 255u; fl = fl_n;
-        sn = sl_n2; wn = wt_n2;
-        buf ^= 1u;
+        if (same) {  // A: c_up(s) -> c_up(s + 1), B: c_lo(s) -> c_up(s): one nibble up and one down a position, where the keys differ
+            const uint32_t uo = fsk_hw::vgpr_copy(uo_n), od = uo & 0xffffu, os = uo >> 16;
+            if (od != os) {
+                const uint32_t p = tid & 127u, t4 = p & 0x3cu, e = (p >> 6) * 4u + (p & 3u);
+                const uint32_t base = buf * PBUF + (w >> 1) * SIDE, inc = 1u << (4u * e);
+                atomicAdd(&P[base + ((os ^ t4) >> 2)], inc);
+                atomicAdd(&P[base + ((od ^ t4) >> 2)], 0u - inc);
+            }
+            __syncthreads();  // the planes of step s + 1 are whole
+        } else {
+            buf ^= 1u;
+        }
+        if constexpr (INPLACE) {
+            sl = sn; wt = wn & 255u; fl = fl_nx;
+            sn = s2; wn = w2; fl_nx = fl_n;
+            s2 = sl_n2; w2 = wt_n2;
+        } else {
+            sl = sn; wt = wn & 255u; fl = fl_n;
+            sn = sl_n2; wn = wt_n2;
+        }
     }
 #pragma unroll
     for (int er = 0; er < 8; ++er) {
