@@ -187,9 +187,9 @@ int choose_path(fsk_engine* e) {
 // rows that fsk_reset_counts left for a storing tile launch get their zeros now (anything but such
 // a launch is about to look at K)
 int materialise_zero(fsk_engine* e) {
-    if (e->lazy_lo < 0) return FSK_OK;
-    const u64 c0 = (u64)e->lazy_lo * ((u64)e->lazy_lo + 1) / 2, c1 = (u64)e->lazy_hi * ((u64)e->lazy_hi + 1) / 2;
-    e->lazy_lo = e->lazy_hi = -1;
+    if (e->ld.lazy_lo < 0) return FSK_OK;
+    const u64 c0 = (u64)e->ld.lazy_lo * ((u64)e->ld.lazy_lo + 1) / 2, c1 = (u64)e->ld.lazy_hi * ((u64)e->ld.lazy_hi + 1) / 2;
+    e->ld.lazy_lo = e->ld.lazy_hi = -1;
     if (c1 > c0) FSK_HIP(hipMemsetAsync(e->d_K + c0, 0, (size_t)(c1 - c0) * sizeof(u64), e->stream));
     return FSK_OK;
 }
@@ -202,16 +202,16 @@ int do_accumulate(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_t r
     if (row1 < 0) row1 = e->N;
     for (int i = 0; i < n; ++i)
         if (combos[i] < 0 || combos[i] >= e->ncomb) return e->fail(FSK_EINVAL, "combo id %d out of range [0,%lld)", combos[i], (long long)e->ncomb);
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a;
     if (e->cfg.profile) {  // (the whole call on the engine's stream; profile = 2: harvested later, see fsk_engine::tic)
         a = e->lazy_event();
         if (a) (void)hipEventRecord(a, e->stream);
     }
     int rc = e->path == FSK_PATH_DENSE ? accumulate_dense(e, combos, n, K, row0, row1) : accumulate_sparse(e, combos, n, K, row0, row1, slot_stride, defer);
     if (e->cfg.profile) {
-        b = e->lazy_event();
+        Event b = e->lazy_event();
         if (b) (void)hipEventRecord(b, e->stream);
-        e->lazy_interval(a, b, &e->st.ms_total);
+        e->lazy_interval(std::move(a), std::move(b), &e->st.ms_total);
         if (e->profile_sync()) e->harvest_times();
     }
     if (rc == FSK_OK && row1 >= e->N) {  // a combo is done when its last row band is
@@ -379,8 +379,8 @@ int fsk_create(const fsk_config* cfg, fsk_engine** out) {
     e->cfg_profile0 = e->cfg.profile;  // (what tuning key profile = -1 goes back to)
     if (e->tune.profile >= 0) e->cfg.profile = (int)e->tune.profile;
     if (e->trace()) fprintf(stderr, "[fsk] tuning: %s\n", tuning_in_force(e->tune).c_str());
-    if (hipStreamCreate(&e->stream) != hipSuccess || hipEventCreate(&e->ev0) != hipSuccess ||
-        hipEventCreate(&e->ev1) != hipSuccess) {
+    if (e->stream.create(0) != hipSuccess || e->ev0.create(0) != hipSuccess ||
+        e->ev1.create(0) != hipSuccess) {
         delete e;
         g_create_error = "cannot create HIP stream/events";
         return FSK_EDEVICE;
@@ -406,35 +406,14 @@ void fsk_destroy(fsk_engine* e) {
 
 }  // extern "C"
 
+// Everything the engine owns goes in its destructor (fsk_engine_internal.h: who owns what), on its device and after whatever
+// may still run on its streams
 void fsk_detail::one_destroy(fsk_engine* e) {
     DeviceScope on_device(e->cfg.device);
     (void)hipStreamSynchronize(e->stream);
     if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
     if (e->chain_stream) (void)hipStreamSynchronize(e->chain_stream);  // (variance mode may leave a dropped batch's sums running)
-    e->d_words.release(); e->d_wstart.release(); e->d_len.release(); e->d_fstart.release(); e->d_featseq.release(); e->d_win.release(); e->d_comp.release();
-    e->d_vbits.release(); e->d_vstart.release(); e->d_fwin.release(); e->d_cw.release();
-    e->d_pos.release(); e->d_allpos.release(); e->d_bsum.release(); e->d_seqblk.release(); e->K_store.release(); e->d_Kf64.release(); e->d_Khat.release(); e->d_prod.release();
-    e->d_diag.release(); e->d_stage.release(); e->d_stage_u64.release(); e->d_Kslots.release(); e->d_cell_idx.release(); e->d_C4.release(); e->d_C4H.release(); e->d_rowmask.release(); e->d_flag.release(); e->d_tiletab.release(); e->d_rare.release(); e->d_rare_n.release(); e->d_common.release(); e->d_keybits.release(); e->d_lut.release(); e->d_vc.release();
-    if (e->lane_stream) { (void)hipStreamSynchronize(e->lane_stream); (void)hipStreamDestroy(e->lane_stream); }
     e->harvest_times();
-    if (e->lazy_open) (void)hipEventDestroy(e->lazy_open);
-    for (hipEvent_t ev : e->lazy_free) (void)hipEventDestroy(ev);
-    for (auto& lane : e->sxs) lane.release();
-    e->d_owner_r0.release(); e->d_U.release(); e->d_U2.release(); e->d_stage32.release(); e->d_shift_steps.release(); e->d_edge_keys.release(); e->d_KM.release(); e->d_KMH.release(); e->d_edge_offs.release(); e->d_blk_r0.release(); e->mm_scratch.release();
-    if (e->h_prod) (void)hipHostFree(e->h_prod);
-    if (e->h_sx_pos) (void)hipHostFree(e->h_sx_pos);
-    if (e->h_sx_stat) (void)hipHostFree(e->h_sx_stat);
-    if (e->h_sx_head_pos) (void)hipHostFree(e->h_sx_head_pos);
-    if (e->h_sx_head_stat) (void)hipHostFree(e->h_sx_head_stat);
-    if (e->h_sx_head_flag) (void)hipHostFree(e->h_sx_head_flag);
-    if (e->h_stage) (void)hipHostFree(e->h_stage);
-    for (auto& ev : e->ev_lane) if (ev) (void)hipEventDestroy(ev);
-    if (e->ev_out) (void)hipEventDestroy(e->ev_out);
-    if (e->ev_in) (void)hipEventDestroy(e->ev_in);
-    if (e->chain_stream) { (void)hipStreamSynchronize(e->chain_stream); (void)hipStreamDestroy(e->chain_stream); }
-    (void)hipEventDestroy(e->ev0);
-    (void)hipEventDestroy(e->ev1);
-    (void)hipStreamDestroy(e->stream);
     delete e;
 }
 
@@ -545,19 +524,16 @@ using fsk_load::LoadPlan;
 
 // the plan's words and tables go into the engine's pinned staging, grown when it is too small
 uint32_t* grow_stage(fsk_engine* e, size_t need) {
-    if (need > e->h_stage_cap) {
-        if (e->h_stage) (void)hipHostFree(e->h_stage);
-        e->h_stage = nullptr; e->h_stage_cap = 0;
-        if (hipHostMalloc((void**)&e->h_stage, (need + need / 4) * sizeof(uint32_t)) != hipSuccess) return nullptr;
-        e->h_stage_cap = need + need / 4;
-    }
-    return e->h_stage;
+    return e->h_stage.reserve(need, need / 4) == hipSuccess ? e->h_stage.p : nullptr;
 }
 
 // the engine's view of the loaded set: sizes, modes, the sparse dataflow's hint and key widths, the dataflow
 int commit_load(fsk_engine* e, const LoadPlan& p, int64_t n_train, int64_t n_test) {
     const int64_t N = p.N;
     const uint32_t strands = p.rc_on ? 2u : 1u;
+    // whatever was known about the previous set — what is resident, pending or promised (the triangle is zeroed, or promised
+    // to be, by the caller), the per-load figures of fsk_stats — starts from its initial values
+    e->ld = {};
     // (the dense dataflow's tile table depends on the number of sequences and the train / test split alone: a set of the same
     // shape keeps the one on the device)
     if (e->N != N || e->n_train != n_train) e->tab_n = 0;
@@ -573,11 +549,7 @@ int commit_load(fsk_engine* e, const LoadPlan& p, int64_t n_train, int64_t n_tes
     e->cw_n = p.cw_on ? (uint32_t)e->cw_profile.size() : 0u;
     e->fwin_on = p.wild_on || p.cw_on;
     e->n_panels = (uint32_t)((N + fsk::PANEL - 1) / fsk::PANEL);
-    e->h_len = p.len32; e->h_fstart = p.fstart; e->featseq_ready = false;
-    e->prep_valid = false; e->vc_sum = 0; e->vc_n = 0;
-
-    e->lazy_lo = e->lazy_hi = -1;  // (the triangle is zeroed, or promised to be, by the caller)
-    e->u_known = false; e->u_pending = false; e->u_extra = 0; e->u_value = 0;
+    e->h_len = p.len32; e->h_fstart = p.fstart;
     {
         // The update words per record seen on the previous set of sequences stay as a HINT when the new set has the same shape
         // (sequences, windows, alphabet, longest sequence: the same data loaded again, or its next fold): the first batch is then
@@ -589,7 +561,6 @@ int commit_load(fsk_engine* e, const LoadPlan& p, int64_t n_train, int64_t n_tes
         if (!same) { e->sx_wpr = 0; e->sx_ppr = 0; e->slots16_ok = true; }
         std::copy(shape, shape + 4, e->sx_shape);
     }
-    for (auto& d : e->sx_defer) d.active = false;
     if (e->V > DENSE_MAX_KEYS) e->Vq = 1;  // unused on the sparse path
     // sparse dataflow: sort record = (k-mer << sx_sb) | sequence id; owner bands of K
     e->sx_sb = 1;
@@ -685,7 +656,6 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
     if (rc) return rc;
     const Compaction c = choose_compaction(plan, e->tune, e->cfg.g, e->k);
     e->compact = c.compact; e->compact_rare = c.compact_rare; e->rare_mask = c.rare_mask; e->rare_places = c.rare_places;
-    e->rare_ready = false;
     rc = upload_load(e, plan);
     if (rc) return rc;
     if (e->d_K && !e->K_owned) {
@@ -697,14 +667,13 @@ int fsk_detail::one_load_sequences(fsk_engine* e, const int32_t* tokens, const i
         e->K_owned = true;
     }
     if (lazy_zero_possible(e)) {  // (as after fsk_reset_counts: the first tile launch stores its sums)
-        e->lazy_lo = 0; e->lazy_hi = N;
+        e->ld.lazy_lo = 0; e->ld.lazy_hi = N;
     } else {
         FSK_HIP(hipMemsetAsync(e->d_K, 0, (size_t)e->pairs * sizeof(u64), e->stream));
     }
     FSK_HIP(e->d_U.reserve(2));  // [0] update count U (multi-chunk dense launches), [1] remainder row products of the dense tile launches
     FSK_HIP(hipMemsetAsync(e->d_U.p, 0, 2 * sizeof(u64), e->stream));
     e->loaded = true; e->finalized = false; e->result_f64 = false;
-    e->stdevs.clear();
     fsk_stats& st = e->st;
     st = fsk_stats{};
     st.n_seq = N; st.n_train = n_train; st.n_test = n_test; st.n_feat = plan.nfeat; st.n_pairs = e->pairs;
@@ -724,7 +693,7 @@ int fsk_bind_counts(fsk_engine* e, void* device_u64, int64_t n_cells) {
     if (!e) return FSK_EINVAL;
     if (!device_u64 || n_cells <= 0) return e->fail(FSK_EINVAL, "bad counts buffer");
     if (e->loaded && n_cells != e->pairs) return e->fail(FSK_EINVAL, "counts buffer holds %lld cells, need %lld", (long long)n_cells, (long long)e->pairs);
-    if (e->lazy_lo >= 0) {
+    if (e->ld.lazy_lo >= 0) {
         FSK_ON_DEVICE(e);
         int rcz = materialise_zero(e);
         if (rcz) return rcz;
@@ -788,7 +757,7 @@ int fsk_synchronize(fsk_engine* e) {
 int fsk_stream_wait_engine(fsk_engine* e, void* hip_stream) {
     if (!e) return FSK_EINVAL;
     FSK_ON_DEVICE(e);
-    if (!e->ev_out) FSK_HIP(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
+    FSK_HIP(e->ev_out.create(hipEventDisableTiming));
     FSK_HIP(hipEventRecord(e->ev_out, e->stream));
     FSK_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, e->ev_out, 0));
     return FSK_OK;
@@ -797,7 +766,7 @@ int fsk_stream_wait_engine(fsk_engine* e, void* hip_stream) {
 int fsk_engine_wait_stream(fsk_engine* e, void* hip_stream) {
     if (!e) return FSK_EINVAL;
     FSK_ON_DEVICE(e);
-    if (!e->ev_in) FSK_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
+    FSK_HIP(e->ev_in.create(hipEventDisableTiming));
     FSK_HIP(hipEventRecord(e->ev_in, (hipStream_t)hip_stream));
     FSK_HIP(hipStreamWaitEvent(e->stream, e->ev_in, 0));
     return FSK_OK;
@@ -883,14 +852,14 @@ int one_reset_counts(fsk_engine* e) {
     if (!e->loaded) return e->fail(FSK_ESTATE, "load sequences first");
     FSK_ON_DEVICE(e);
     if (lazy_zero_possible(e)) {
-        e->lazy_lo = 0; e->lazy_hi = e->N;  // (whatever was pending is covered by this range)
+        e->ld.lazy_lo = 0; e->ld.lazy_hi = e->N;  // (whatever was pending is covered by this range)
     } else {
-        e->lazy_lo = e->lazy_hi = -1;
+        e->ld.lazy_lo = e->ld.lazy_hi = -1;
         FSK_HIP(hipMemsetAsync(e->d_K, 0, (size_t)e->pairs * sizeof(u64), e->stream));
     }
     e->finalized = false; e->result_f64 = false;
     e->st.combos_done = 0;
-    e->prep_valid = false;  // a new pass recounts its panels even when its first band starts at row > 0
+    e->ld.prep_valid = false;  // a new pass recounts its panels even when its first band starts at row > 0
     return FSK_OK;
 }
 
@@ -901,13 +870,13 @@ int one_reset_counts_rows(fsk_engine* e, int64_t row_begin, int64_t row_end) {
     const u64 c0 = (u64)row_begin * ((u64)row_begin + 1) / 2, c1 = (u64)row_end * ((u64)row_end + 1) / 2;
     { int rcz = materialise_zero(e); if (rcz) return rcz; }  // an earlier, different reset
     if (lazy_zero_possible(e) && row_begin % fsk::TILE == 0 && row_end > row_begin) {
-        e->lazy_lo = row_begin; e->lazy_hi = row_end;
+        e->ld.lazy_lo = row_begin; e->ld.lazy_hi = row_end;
     } else if (c1 > c0) {
         FSK_HIP(hipMemsetAsync(e->d_K + c0, 0, (size_t)(c1 - c0) * sizeof(u64), e->stream));
     }
     e->finalized = false; e->result_f64 = false;
     e->st.combos_done = 0;
-    e->prep_valid = false;
+    e->ld.prep_valid = false;
     return FSK_OK;
 }
 
@@ -1063,15 +1032,16 @@ int fsk_alloc_triangle_device(fsk_engine* e, double** device_out) {
     *device_out = nullptr;
     if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
     FSK_ON_DEVICE(e);
-    double* p = nullptr;
-    if (hipMalloc((void**)&p, (size_t)e->pairs * sizeof(double)) != hipSuccess) {
+    DevBuf<double> block;  // (the caller's from the moment it is handed out: fsk_free_device)
+    if (block.reserve((size_t)e->pairs) != hipSuccess) {
         (void)hipGetLastError();
         return e->fail(FSK_ENOMEM, "cannot allocate the %lld-cell normalised triangle (%.1f GB) on device %d", (long long)e->pairs,
                        (double)e->pairs * 8e-9, e->cfg.device);
     }
-    const int rc = fsk_get_triangle_device(e, p);
-    if (rc) { (void)hipFree(p); return rc; }
-    *device_out = p;
+    const int rc = fsk_get_triangle_device(e, block.p);
+    if (rc) return rc;
+    *device_out = block.p;
+    block.p = nullptr;
     return FSK_OK;
 }
 
@@ -1138,8 +1108,8 @@ int fsk_get_counts_cells(fsk_engine* e, const int64_t* rows, const int64_t* cols
 
 int fsk_get_stdevs(fsk_engine* e, double* out, int32_t cap, int32_t* n) {
     if (!e || !n) return FSK_EINVAL;
-    *n = (int32_t)e->stdevs.size();
-    for (int32_t i = 0; i < *n && i < cap && out; ++i) out[i] = e->stdevs[i];
+    *n = (int32_t)e->ld.stdevs.size();
+    for (int32_t i = 0; i < *n && i < cap && out; ++i) out[i] = e->ld.stdevs[i];
     return FSK_OK;
 }
 
@@ -1192,12 +1162,13 @@ int fsk_alloc_block_device(fsk_engine* e, int64_t i0, int64_t i1, int64_t j0, in
     if (i0 < 0 || j0 < 0 || i1 > e->N || j1 > e->N || i0 > i1 || j0 > j1) return e->fail(FSK_EINVAL, "block out of range");
     FSK_ON_DEVICE(e);
     const size_t cells = (size_t)(i1 - i0) * (size_t)(j1 - j0);
-    double* p = nullptr;
-    if (hipMalloc((void**)&p, std::max<size_t>(1, cells) * sizeof(double)) != hipSuccess)
+    DevBuf<double> block;  // (the caller's from the moment it is handed out: fsk_free_device)
+    if (block.reserve(std::max<size_t>(1, cells)) != hipSuccess)
         return e->fail(FSK_ENOMEM, "cannot allocate a %lld x %lld block on device %d", (long long)(i1 - i0), (long long)(j1 - j0), e->cfg.device);
-    const int rc = fsk_get_block_device(e, i0, i1, j0, j1, p);
-    if (rc) { (void)hipFree(p); return rc; }
-    *device_out = p;
+    const int rc = fsk_get_block_device(e, i0, i1, j0, j1, block.p);
+    if (rc) return rc;
+    *device_out = block.p;
+    block.p = nullptr;
     return FSK_OK;
 }
 
@@ -1219,16 +1190,16 @@ int fsk_detail::one_get_stats(fsk_engine* e, fsk_stats* out) {
         e->harvest_times();
         if (hipStreamSynchronize(e->stream) == hipSuccess && fetch_pending_u(e) == FSK_OK &&
             hipMemcpy(U, e->d_U.p, sizeof U, hipMemcpyDeviceToHost) == hipSuccess) {
-            e->st.cell_updates = U[0] + e->u_extra;
+            e->st.cell_updates = U[0] + e->ld.u_extra;
             rem_rows = U[1];
         }
     }
     e->st.batches_redone = (double)e->sx_redone;
-    e->st.sparse_form = (double)e->sx_form_used;
-    e->st.sparse_passes = (double)e->sx_passes;
-    e->st.sparse_desc = e->sx_desc_used ? 1.0 : 0.0;
-    e->st.share_positions = (double)e->sx_share_used;
-    e->st.share_groups = (double)e->sx_share_groups;
+    e->st.sparse_form = (double)e->ld.sx_form_used;
+    e->st.sparse_passes = (double)e->ld.sx_passes;
+    e->st.sparse_desc = e->ld.sx_desc_used ? 1.0 : 0.0;
+    e->st.share_positions = (double)e->ld.sx_share_used;
+    e->st.share_groups = (double)e->ld.sx_share_groups;
     *out = e->st;
     // (every flagged-row remainder product is one more dot8 per cell of its tile: 8 count-MACs x 128 x 128)
     out->dense_macs += rem_rows * (u64)fsk::TILE * fsk::TILE * 8;
@@ -1351,7 +1322,7 @@ static int fold_level(fsk_engine* e, int64_t a, bool first, double* ms) {
 int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offsets, int64_t n_train, int64_t n_test) {
     int rc = one_load_sequences(e, tokens, offsets, n_train, n_test);
     if (rc) return rc;
-    e->lazy_lo = e->lazy_hi = -1;  // (the first fold stores every cell: no zeros are owed)
+    e->ld.lazy_lo = e->ld.lazy_hi = -1;  // (the first fold stores every cell: no zeros are owed)
     const int g = e->cfg.g, d = (int)e->mm_a.size() - 1;
     // a failure from here on leaves the handle as it was before any sequences were loaded
     auto give_up = [&](int code) { e->loaded = false; e->finalized = false; return code; };
@@ -1440,7 +1411,7 @@ int mismatch_compute(fsk_engine* e, const int32_t* tokens, const int64_t* offset
     st.ms_segment = sum.ms_segment; st.ms_pairs = sum.ms_pairs; st.ms_total = sum.ms_total;
     st.n_tile_launches = sum.n_tile_launches; st.dense_macs = sum.dense_macs; st.panel_bytes = sum.panel_bytes;
     st.u4_tile_launches = sum.u4_tile_launches; st.count_launches = sum.count_launches;
-    e->u_extra = sum.cell_updates;
+    e->ld.u_extra = sum.cell_updates;
     return make_diag(e);
 }
 
@@ -1520,10 +1491,11 @@ __global__ __launch_bounds__(256) void k_test_wave_ops(const int32_t* in, const 
 extern "C" int fsk_test_wave_ops(const int32_t* in, const uint32_t* aux, int32_t n, int32_t* out_max, uint32_t* out_sum, unsigned long long* out_sum64,
                                  uint32_t* out_xnor, int32_t* out_sbfe, uint32_t* out_mbcnt) {
     if (n <= 0 || n % 64) return FSK_EINVAL;
+    DevBuf<unsigned char> buf[8];
     void* d[8] = {nullptr};
     const size_t sz[8] = {4, 4, 4, 4, 8, 4, 4, 4};
     bool ok = true;
-    for (int q = 0; q < 8 && ok; ++q) ok = hipMalloc(&d[q], sz[q] * (size_t)n) == hipSuccess;
+    for (int q = 0; q < 8 && ok; ++q) { ok = buf[q].reserve(sz[q] * (size_t)n) == hipSuccess; d[q] = buf[q].p; }
     if (ok) ok = hipMemcpy(d[0], in, 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d[1], aux, 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         FSK_LAUNCH(fsk::k_test_wave_ops, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t) nullptr, (const int32_t*)d[0], (const uint32_t*)d[1], n,
@@ -1532,7 +1504,6 @@ extern "C" int fsk_test_wave_ops(const int32_t* in, const uint32_t* aux, int32_t
     }
     void* host[8] = {nullptr, nullptr, out_max, out_sum, out_sum64, out_xnor, out_sbfe, out_mbcnt};
     for (int q = 2; q < 8 && ok; ++q) ok = hipMemcpy(host[q], d[q], sz[q] * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
-    for (int q = 0; q < 8; ++q) if (d[q]) (void)hipFree(d[q]);
     return ok ? FSK_OK : FSK_EDEVICE;
 }
 #endif

@@ -80,11 +80,11 @@ void build_tile_table(uint32_t t0, uint32_t t1, uint32_t first_test_tile, std::v
 
 // the U of the first launch of a combo list arrives here (profile mode only)
 int fetch_pending_u(fsk_engine* e) {
-    if (!e->u_pending) return FSK_OK;
+    if (!e->ld.u_pending) return FSK_OK;
     FSK_HIP(hipStreamSynchronize(e->stream));
-    FSK_HIP(hipMemcpy(&e->u_value, e->d_U2.p, sizeof(u64), hipMemcpyDeviceToHost));
-    e->u_extra += e->u_value;
-    e->u_pending = false;
+    FSK_HIP(hipMemcpy(&e->ld.u_value, e->d_U2.p, sizeof(u64), hipMemcpyDeviceToHost));
+    e->ld.u_extra += e->ld.u_value;
+    e->ld.u_pending = false;
     return FSK_OK;
 }
 
@@ -213,10 +213,10 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
         const int nb = std::min(chunk, n - s);
         // the count panels of an unchanged single-chunk combo list are reused by the FOLLOWING row
         // bands of one pass (row0 > 0); a call that starts at row 0 always recounts
-        const bool cached = row0 > 0 && e->prep_valid && nb == n && (int)e->prep_combos.size() == n && e->prep_shift == use_shift &&
-                            (!use_shift || e->prep_chain == e->shift.max_chain) && std::equal(combos, combos + n, e->prep_combos.begin());
+        const bool cached = row0 > 0 && e->ld.prep_valid && nb == n && (int)e->prep_combos.size() == n && e->ld.prep_shift == use_shift &&
+                            (!use_shift || e->ld.prep_chain == e->shift.max_chain) && std::equal(combos, combos + n, e->prep_combos.begin());
         if (!cached) {
-            e->prep_valid = false;
+            e->ld.prep_valid = false;
             // the chunk's kept positions: a run of consecutive combo ids (every exact call: 0, 1, 2, ...) reads them from the
             // resident table of all combos, uploaded once per engine; any other list is gathered and uploaded
             bool consecutive = !use_shift;  // (the shift plan's slot order: chain bases first)
@@ -249,7 +249,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             if (compact) {  // which keys occur per combo -> rank tables -> compacted panels
                 if (e->compact_rare) {  // from the places of the rare symbols (listed once per set of sequences)
                     const uint32_t cap = std::max(1u, e->rare_places);
-                    if (!e->rare_ready) {
+                    if (!e->ld.rare_ready) {
                         FSK_HIP(e->d_rare.reserve(cap));
                         FSK_HIP(e->d_rare_n.reserve(1));
                         FSK_HIP(hipMemsetAsync(e->d_rare_n.p, 0, sizeof(uint32_t), e->stream));
@@ -258,7 +258,7 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                         FSK_HIP(e->d_common.reserve(Vw));
                         FSK_LAUNCH(fsk::k_dense_common_keys, dim3((Vw + 255u) / 256u), dim3(256), 0, e->stream, e->d_common.p, Vkeys, e->k, e->sigma,
                                    e->rare_mask);
-                        e->rare_ready = true;
+                        e->ld.rare_ready = true;
                     }
                     FSK_LAUNCH(fsk::k_dense_keybits_init, dim3((Vw + 255u) / 256u, (uint32_t)nb), dim3(256), 0, e->stream, e->d_keybits.p,
                                (const uint32_t*)e->d_common.p, Vkeys);
@@ -284,8 +284,8 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
                 {   // running mean of the compacted key counts (stats)
                     double sum = 0;
                     for (uint16_t v : h_vc) sum += v;
-                    e->vc_sum += sum; e->vc_n += (double)nb;
-                    e->st.compact_keys_avg = e->vc_sum / e->vc_n;
+                    e->ld.vc_sum += sum; e->ld.vc_n += (double)nb;
+                    e->st.compact_keys_avg = e->ld.vc_sum / e->ld.vc_n;
                 }
             } else {
                 FSK_LAUNCH(k_count, cgrid, dim3(256), lds, e->stream, e->view(), e->cfg.g,
@@ -298,35 +298,35 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             e->st.panel_bytes += 2 * slot_dwords4 * sizeof(uint32_t) * (u64)nb;
             // a count above 255 does not fit the u8 panels either: take the general dataflow
             // for this batch (only possible when a sequence has more than 255 windows)
-            e->prep_overflow = false;
+            e->ld.prep_overflow = false;
             if (e->maxW > 255) {
                 uint32_t flag = 0;
                 FSK_HIP(hipMemcpyAsync(&flag, e->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, e->stream));
                 FSK_HIP(hipStreamSynchronize(e->stream));
-                e->prep_overflow = (flag & 1u) != 0;
+                e->ld.prep_overflow = (flag & 1u) != 0;
             }
-            if (e->profile_sync() && !e->prep_overflow) {  // exact algorithmic update count U
-                const bool same = nb == n && e->u_known && (int)e->u_combos.size() == n && std::equal(combos, combos + n, e->u_combos.begin());
-                if (e->u_pending) {  // value of the previous first-time launch
+            if (e->profile_sync() && !e->ld.prep_overflow) {  // exact algorithmic update count U
+                const bool same = nb == n && e->ld.u_known && (int)e->u_combos.size() == n && std::equal(combos, combos + n, e->u_combos.begin());
+                if (e->ld.u_pending) {  // value of the previous first-time launch
                     int rc = fetch_pending_u(e);
                     if (rc) return rc;
                 }
                 if (same) {
-                    e->u_extra += e->u_value;  // same sequences, same combos: same U
+                    e->ld.u_extra += e->ld.u_value;  // same sequences, same combos: same U
                 } else if (nb == n) {
                     FSK_HIP(e->d_U2.reserve(1));
                     FSK_HIP(hipMemsetAsync(e->d_U2.p, 0, sizeof(u64), e->stream));
                     FSK_LAUNCH(fsk::k_dense_distinct, dim3(Vq8, nb), dim3(64), 0, e->stream, e->d_C4.p, e->d_C4H.p, panels_pad, nb, Vq8,
                                e->d_U2.p, compact ? (const uint16_t*)e->d_vc.p : (const uint16_t*)nullptr);
                     e->u_combos.assign(combos, combos + n);
-                    e->u_known = true;
-                    e->u_pending = true;
+                    e->ld.u_known = true;
+                    e->ld.u_pending = true;
                 } else {
                     FSK_LAUNCH(fsk::k_dense_distinct, dim3(Vq8, nb), dim3(64), 0, e->stream, e->d_C4.p, e->d_C4H.p, panels_pad, nb, Vq8,
                                e->d_U.p, compact ? (const uint16_t*)e->d_vc.p : (const uint16_t*)nullptr);
                 }
             }
-            if (use_shift && !e->prep_overflow) {  // the edge keys stay with the panels: row bands reuse them
+            if (use_shift && !e->ld.prep_overflow) {  // the edge keys stay with the panels: row bands reuse them
                 e->tic();
                 const int rck = dense_shift_edge_keys(e, chunk_pos, panels_pad);
                 if (rck) return rck;
@@ -336,12 +336,12 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             }
             if (nb == n) {
                 e->prep_combos.assign(combos, combos + n);
-                e->prep_valid = true;
-                e->prep_shift = use_shift;
-                e->prep_chain = use_shift ? e->shift.max_chain : 0u;
+                e->ld.prep_valid = true;
+                e->ld.prep_shift = use_shift;
+                e->ld.prep_chain = use_shift ? e->shift.max_chain : 0u;
             }
         }
-        if (e->prep_overflow) {
+        if (e->ld.prep_overflow) {
             // (variance mode's slot triangle: the storing launch that would have written every cell is
             // not coming, and the general dataflow ADDS — the slot still holds an earlier iteration)
             if (e->store_next) FSK_HIP(hipMemsetAsync(K, 0, (size_t)e->pairs * sizeof(u64), e->stream));
@@ -389,12 +389,12 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
             if (!(!compact && n_splits == 1 && first_test_tile == 0xffffffffu && row0 == 0 && row1 >= e->N))
                 return e->fail(FSK_ESTATE, "internal: a storing tile launch was asked for where none is possible");
             store = 1;
-        } else if (e->lazy_lo >= 0) {
-            if (K == e->d_K && !compact && n_splits == 1 && first_test_tile == 0xffffffffu && row0 == e->lazy_lo &&
-                row1 <= e->lazy_hi) {
+        } else if (e->ld.lazy_lo >= 0) {
+            if (K == e->d_K && !compact && n_splits == 1 && first_test_tile == 0xffffffffu && row0 == e->ld.lazy_lo &&
+                row1 <= e->ld.lazy_hi) {
                 store = 1;
-                e->lazy_lo = row1 < e->lazy_hi ? row1 : -1;
-                if (e->lazy_lo < 0) e->lazy_hi = -1;
+                e->ld.lazy_lo = row1 < e->ld.lazy_hi ? row1 : -1;
+                if (e->ld.lazy_lo < 0) e->ld.lazy_hi = -1;
             } else {
                 int rcz = materialise_zero(e);
                 if (rcz) return rcz;

@@ -113,14 +113,14 @@ int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t pane
 }
 
 // The key-major planes of the list just counted, and the edge keys as offsets into them: what k_dense_shift_packed reads. They
-// stay with the panels (row bands reuse them). Leaves e->shift_packed false, and the corrections to k_dense_shift_fix, when the
+// stay with the panels (row bands reuse them). Leaves e->ld.shift_packed false, and the corrections to k_dense_shift_fix, when the
 // tuning says so, the plan's chains are not cut to the packed kernel's eight steps, or the planes do not fit: never an error.
 // A call that wanted the packed kernel and did not get it says so under trace=1 (the slower kernel otherwise shows only as
 // three launches fewer in fsk_stats.launches). Memory is asked about only when the buffers have to grow; a growth may take half
 // of what is free then, because the results (the normalised triangle of fsk_finalize) are still to be allocated.
 int dense_shift_keymajor(fsk_engine* e, uint32_t panels_pad, int nb, uint32_t Vq8) {
     const ShiftPlan& p = e->shift;
-    e->shift_packed = false;
+    e->ld.shift_packed = false;
     if (e->tune.dense_shift_packed < 0 || p.max_chain != SHIFT_PACKED_CHAIN) return FSK_OK;
     const size_t plane = (size_t)panels_pad * Vq8 * fsk::PANEL * (size_t)nb;  // dwords: as many as a plane of the panels
     const size_t n_keys = (p.steps.size() / 2) * (size_t)panels_pad * fsk::PANEL;
@@ -152,7 +152,7 @@ int dense_shift_keymajor(fsk_engine* e, uint32_t panels_pad, int nb, uint32_t Vq
     FSK_LAUNCH(fsk::k_dense_edge_offs, dim3((uint32_t)((n_keys + 255u) / 256u)), dim3(256), 0, e->stream, (const uint16_t*)e->d_edge_keys.p, n_keys,
                e->d_edge_offs.p);
     e->st.launches += 3;
-    e->shift_packed = true;
+    e->ld.shift_packed = true;
     return FSK_OK;
 }
 
@@ -167,7 +167,7 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
                    slot0, p.groups[gi + 1]);
         slot0 = end;
     }
-    if (e->shift_packed) {
+    if (e->ld.shift_packed) {
         const auto k_packed = e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true> : fsk::k_dense_shift_packed<false>;
         FSK_LAUNCH(k_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),

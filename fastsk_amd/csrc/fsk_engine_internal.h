@@ -36,15 +36,21 @@ namespace fsk_detail {
         if (_e != hipSuccess) return e->fail(FSK_EDEVICE, "%s failed: %s", #call, hipGetErrorString(_e)); \
     } while (0)
 
+// ---- who owns what. Device memory, pinned memory, streams and events each belong to ONE object of the four types below, which
+// frees them in its destructor and can be moved but not copied: an engine (or a group, or a function's local) that goes takes
+// everything it made with it, and nobody keeps a list of what to free. What is freed EARLY, to make room, says so with
+// release(). Memory the engine was only lent (fsk_bind_counts: fsk_engine::d_K) is a plain pointer.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         hipError_t r = hipMalloc((void**)&p, n * sizeof(T));
         if (r == hipSuccess) cap = n;
         return r;
@@ -55,6 +61,44 @@ struct DevBuf {
         cap = 0;
     }
 };
+
+// pinned host memory; reserve(n, slack) takes n + slack elements when it has to grow, so that the next few sizes fit too
+template <typename T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~PinnedBuf() { release(); }
+    hipError_t reserve(size_t n, size_t slack = 0) {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t r = hipHostMalloc((void**)&p, (n + slack) * sizeof(T));
+        if (r == hipSuccess) cap = n + slack;
+        return r;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// a stream or an event: null until create(flags), which does nothing on one that exists (the lazy ones are made where they
+// are first needed); converts to the raw handle wherever HIP wants one
+template <typename H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)Destroy(h); }
+    hipError_t create(unsigned flags) { return h ? hipSuccess : Create(&h, flags); }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 
 // Every entry point runs on the engine's device and puts the calling thread's current device back
 // afterwards: the engine shares one HIP runtime with torch, whose current device must not move
@@ -80,6 +124,9 @@ struct DeviceScope {
 }  // namespace fsk_detail
 
 using fsk_detail::DevBuf;
+using fsk_detail::PinnedBuf;
+using fsk_detail::Stream;
+using fsk_detail::Event;
 
 // ---------------------------------------------------------------------------------------------
 // Every knob of the engine that is not part of fsk_config, in ONE place. A key is set with fsk_set_tuning(handle,
@@ -167,16 +214,6 @@ struct SxScratch {
     DevBuf<uint32_t> d_ulist2, d_subcnt, d_suboff, d_subcur;  // blocks form: the stream split by sub-band, words / start / cursor per (band, sub-band)
     DevBuf<uint32_t> d_dsubcnt, d_dsuboff, d_dsubcur;         //              the same for the descriptor records
     DevBuf<uint32_t> d_cols;                                  // descriptors: the entries' column array (2 or 4 bytes an entry)
-    void release() {
-        d_ulist2.release(); d_subcnt.release(); d_suboff.release(); d_subcur.release();
-        d_dsubcnt.release(); d_dsuboff.release(); d_dsubcur.release(); d_cols.release();
-        d_group_of.release(); d_group_head.release(); d_winp.release(); d_part.release();
-        for (auto& k : d_keys) k.release();
-        d_blockhist.release(); d_totals.release(); d_tile_ent.release(); d_ebase.release(); d_Pk.release(); d_Tk.release();
-        d_ucount.release(); d_uchunk.release(); d_utot.release(); d_list_off.release(); d_ulist.release(); d_part_base.release();
-        d_tile_stat.release(); d_segc.release(); d_tile_lrh.release(); d_tile_rs.release(); d_tile_lth.release(); d_tile_ts.release();
-        d_E.release(); d_sxstat.release();
-    }
 };
 
 // The shift-class plan of a combination list (fsk_engine_dense_shift.hip): the count panels' slot order — chain bases first,
@@ -210,10 +247,6 @@ struct SvmCvState {
     DevBuf<int32_t> d_fold;
     DevBuf<signed char> d_y;
     DevBuf<unsigned char> d_prob, d_rec;         // fsk::SvmProb [problems]; the records and candidate slots
-    void release() {
-        d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_rho.release(); d_oof.release();
-        d_idx.release(); d_fold.release(); d_y.release(); d_prob.release(); d_rec.release();
-    }
 };
 
 struct SvmState {
@@ -236,11 +269,6 @@ struct SvmState {
     DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_out;
     DevBuf<signed char> d_y;
     DevBuf<unsigned char> d_rec;     // the records the launches of a solve hand each other (fsk_kernels_svm.h)
-    void release() { d_alpha.release(); d_G.release(); d_krow.release(); d_coef.release(); d_out.release(); d_y.release(); d_rec.release(); cv.release(); cal.release(); }
-    SvmState() = default;
-    SvmState(const SvmState&) = delete;
-    SvmState& operator=(const SvmState&) = delete;
-    ~SvmState() { release(); }
 };
 
 // The rows kernel (fsk_engine_rows.hip): L(r, c) = <K(r, train), K(c, train)> of the finalized result as a packed fp64
@@ -251,34 +279,58 @@ struct RowsState {
     DevBuf<double> d_L, d_diag;
     fsk_rows_info info{};
     void drop() { valid = false; d_L.release(); d_diag.release(); }
-    RowsState() = default;
-    RowsState(const RowsState&) = delete;
-    RowsState& operator=(const RowsState&) = delete;
-    ~RowsState() { drop(); }
 };
 
 struct fsk_engine {
+    // Members are destroyed in reverse order of declaration: the streams come FIRST, so that they are destroyed LAST, after
+    // every event and buffer whose work ran on them (one_destroy has synchronised all three by then).
+    Stream stream;        // the engine's own
+    Stream lane_stream;   // sparse dataflow, lane 1 (lane 0 runs on `stream`); made by the first call that runs two lanes
+    Stream chain_stream;  // variance mode: the sequential sums of a batch, under the next batches' kernels; made by its first call
     fsk_config cfg{};
     int cfg_profile0 = 0;  // fsk_config.profile as the engine was created (tuning key profile = -1 restores it)
     fsk_tuning tune{};  // (fsk_set_tuning / FSK_TUNING at fsk_create; see FSK_TUNING_KEYS)
     std::string err;
     int k = 0;
     int64_t ncomb = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_out = nullptr, ev_in = nullptr;  // fsk_stream_wait_engine / fsk_engine_wait_stream: one event per direction
+    Event ev0, ev1;
+    Event ev_out, ev_in;  // fsk_stream_wait_engine / fsk_engine_wait_stream: one event per direction, made by the first call
     fsk_group* group = nullptr;          // fsk_create_multi: this engine leads a group (fsk_multi.hip); its other engines have none
-    hipStream_t chain_stream = nullptr;  // variance mode: the sequential sums of a batch, under the next batches' kernels
-    // fsk_reset_counts does not fill K when the next accumulate can STORE its sums instead of adding
-    // them (dense dataflow, one workgroup per tile): rows [lazy_lo, lazy_hi) are zero by contract
-    // but not in memory until a tile launch stores them or materialise_zero() fills them.
-    int64_t lazy_lo = -1, lazy_hi = -1;
     bool store_next = false;  // variance mode, dense dataflow: the next (one-combo, whole-triangle) tile launch stores into the K it is given
-    uint32_t* h_stage = nullptr;         // pinned: the packed sequences on their way to the device (fsk_load_sequences)
-    size_t h_stage_cap = 0;
+    PinnedBuf<uint32_t> h_stage;         // the packed sequences on their way to the device (fsk_load_sequences)
     bool stage_in_flight = false;
-    double* h_prod = nullptr;            // pinned: one sequential sum per iteration in flight (kept across calls)
-    size_t h_prod_cap = 0;
+    PinnedBuf<double> h_prod;            // one sequential sum per iteration in flight (kept across calls)
+
+    // What belongs to the LOADED SET and nothing else: a load starts it afresh in one assignment, ld = {} (commit_load), so a
+    // field added here cannot be forgotten there. What stays outside, and why: the caches that name what they were built for
+    // and so check themselves (tab_*: the tile table's shape; owner_N: the owner bands' N; ShiftPlan: its combination list);
+    // the hint that outlives a load of the same shape on purpose (sx_wpr, sx_ppr, slots16_ok, sx_shape: commit_load's own
+    // block); allpos_ready (it follows from g and m, not from the sequences); sx_redone (cumulative); whatever fsk_set_* sets.
+    struct Loaded {
+        bool featseq_ready = false;  // sparse dataflow: d_featseq (and d_win) hold these sequences' features
+        bool rare_ready = false;     // key compaction: d_rare lists the places of these sequences' rare symbols
+        // the count panels on the device hold prep_combos — prep_overflow: with their hi planes; prep_shift: in the slot order of
+        // the shift-class plan, with its edge keys; prep_chain: whose chains were cut after this many members
+        // (ShiftPlan::max_chain); shift_packed: the key-major planes and offsets hold that list too
+        bool prep_valid = false, prep_overflow = false, prep_shift = false, shift_packed = false;
+        uint32_t prep_chain = 0;
+        double vc_sum = 0, vc_n = 0;  // key compaction: keys that occur, summed over the combos counted, and those combos
+        // profile mode, dense dataflow: the update count U of u_combos is known / on its way; cell updates counted elsewhere
+        bool u_known = false, u_pending = false;
+        u64 u_value = 0, u_extra = 0;
+        struct SxDefer { bool active = false; u64 cap = 0, nrec = 0; } sx_defer[8];  // variance mode: the deferred batches in flight
+        // fsk_reset_counts does not fill K when the next accumulate can STORE its sums instead of adding them (dense dataflow,
+        // one workgroup per tile): rows [lazy_lo, lazy_hi) are zero by contract but not in memory until a tile launch stores
+        // them or materialise_zero() fills them.
+        int64_t lazy_lo = -1, lazy_hi = -1;
+        std::vector<double> stdevs;
+        // fsk_stats, sparse dataflow, "since the sequences were loaded" / "the last batch":
+        u64 sx_passes = 0;             // blocks form: passes run (sparse_passes)
+        int sx_form_used = -1;         // the update stage the last batch really took (sparse_form; sx_form is the plan)
+        bool sx_desc_used = false;     // the last batch, owner bands or two-level blocks, sent descriptors (sparse_desc)
+        int sx_share_used = 0;         // shared prefixes: leading positions / groups of the last batch (share_positions,
+        uint32_t sx_share_groups = 0;  // share_groups)
+    } ld;
 
     // sequences
     bool loaded = false, finalized = false, result_f64 = false;
@@ -291,7 +343,6 @@ struct fsk_engine {
     DevBuf<uint32_t> d_win;  // sparse dataflow: the g-mer windows, win_words 32-bit words each (0: g * bits > 128, symbols are gathered)
     int win_words = 0;
     std::vector<uint32_t> h_len, h_fstart;
-    bool featseq_ready = false;
     // reverse-complement mode (fsk_set_complement): the map as it was set, sorted by token (empty: off); what the LOADED
     // sequences were packed with — revcomp, the complement of every rank (d_comp, beside the packed sequences, which hold
     // one strand only) — and the windows of ONE strand of the longest sequence. maxW, nfeat, fstart count both strands.
@@ -337,7 +388,6 @@ struct fsk_engine {
     std::vector<int32_t> order;
     bool order_set = false;
     uint64_t seed = 0;
-    std::vector<double> stdevs;
 
     // counts / results
     u64* d_K = nullptr;
@@ -357,30 +407,24 @@ struct fsk_engine {
     bool compact = false;         // decided at load: the alphabet has a rare symbol
     // key compaction from the places of the rare symbols (k_dense_rare_scan / k_dense_mark_rare) instead of a marking pass
     // over every window: decided at load (few places, plenty of windows per common key); tuning compact_rare = 0: never
-    bool compact_rare = false, rare_ready = false;
+    bool compact_rare = false;
     uint32_t rare_mask = 0, rare_places = 0;
     DevBuf<u64> d_rare;
     DevBuf<uint32_t> d_rare_n, d_common;  // (d_common: the bitmap of the keys made of common symbols alone)
     std::vector<uint16_t> h_vc_cache;
-    double vc_sum = 0, vc_n = 0;
     DevBuf<uint32_t> d_tiletab;
     uint32_t tab_t0 = 0, tab_t1 = 0, tab_n = 0;   // tile-row range the table on the device covers
     uint32_t tab_ftt = 0xffffffffu;               // ... and the first all-test tile column it was built for (skip_test_block)
-    std::vector<int32_t> prep_combos;              // combos whose count panels are resident
-    bool prep_valid = false, prep_overflow = false;
-    bool prep_shift = false;                       // ... in the slot order of the shift-class plan, with its edge keys
-    uint32_t prep_chain = 0;                       // ... whose chains were cut after this many members (ShiftPlan::max_chain)
-    ShiftPlan shift;
+    std::vector<int32_t> prep_combos;              // combos whose count panels are resident (Loaded::prep_valid)
+    ShiftPlan shift;                               // (outside Loaded: it names the combination list it was made for)
     DevBuf<uint32_t> d_shift_steps;
     DevBuf<uint16_t> d_edge_keys;                  // [derived step][panel][dword of the panel row]: delta | sigma << 8
     // the packed corrections (tuning dense_shift_packed): the lo / hi planes key-major, [panel pair][slot][key][16 dwords], and
-    // the edge keys as byte offsets into a staged plane; shift_packed: they hold the resident panels' list
+    // the edge keys as byte offsets into a staged plane (Loaded::shift_packed: they hold the resident panels' list)
     DevBuf<uint32_t> d_KM, d_KMH, d_edge_offs;
-    bool shift_packed = false;
     // sparse scratch
     SxScratch sxs[2];                     // lane 0: every exact accumulate; lanes 0 and 1: variance mode's batches in flight
-    hipStream_t lane_stream = nullptr;    // lane 1's stream (lane 0 runs on `stream`)
-    hipEvent_t ev_lane[4] = {nullptr, nullptr, nullptr, nullptr};  // exact accumulate in two lanes: fork, join, K handed on by lane 0 / 1
+    Event ev_lane[4];                     // exact accumulate in two lanes: fork, join, K handed on by lane 0 / 1
     DevBuf<uint32_t> d_owner_r0;
     DevBuf<u64> d_U;
     std::vector<uint32_t> h_owner_r0;     // owner bands of K: rows [r0[o], r0[o+1])
@@ -391,10 +435,6 @@ struct fsk_engine {
     bool sx_lists = false, owner_ready = false;
     int n_cu = 256;   // compute units of the device (persistent launches)
     int sx_form = 0;  // the update stage of the sparse dataflow for these sequences: 0 = owner bands, 1 = 64-bit atomics, 2 = two-level blocks
-    int sx_form_used = -1;  // ... what the last batch really took (fsk_stats.sparse_form)
-    u64 sx_passes = 0;      // blocks form: passes run since the sequences were loaded
-    int sx_share_used = 0;  // shared prefixes: leading positions / groups of the last batch (fsk_stats)
-    uint32_t sx_share_groups = 0;
     DevBuf<uint32_t> d_blk_r0;  // blocks form: the band table of the pass at hand
     bool sx_pairs_asked = true;
     bool sx_pairs = false;  // update streams: unit products travel as 15-bit cells, two to a 32-bit container (bands of < 32767 cells)
@@ -403,30 +443,25 @@ struct fsk_engine {
     // the same pass (bench steps, row bands of later passes) does not re-read every count panel
     DevBuf<u64> d_U2;
     std::vector<int32_t> u_combos;
-    bool u_known = false, u_pending = false;
-    u64 u_value = 0, u_extra = 0;
     // Batches are enqueued without waiting for their word counts once one batch of these sequences has
     // been sized: the stream buffer keeps headroom over the largest count seen, the kernels leave a
     // batch that does not fit alone, and the host redoes such a batch (sized exactly) when it reads the
     // counts back — at the end of an exact accumulate, at the hand-over of a variance-mode batch.
-    unsigned char* h_sx_pos = nullptr;   // pinned: positions of the batches of ONE exact accumulate (read back before it returns)
-    size_t h_sx_pos_cap = 0;
-    u64* h_sx_stat = nullptr;            // pinned: {pairs, words} of those batches
-    size_t h_sx_stat_cap = 0;
-    unsigned char* h_sx_head_pos = nullptr;  // pinned, fixed size, never moved: positions of variance mode's deferred batches (in flight across calls)
-    u64* h_sx_head_stat = nullptr;           //                                   their {pairs, words}
+    PinnedBuf<unsigned char> h_sx_pos;   // positions of the batches of ONE exact accumulate (read back before it returns)
+    PinnedBuf<u64> h_sx_stat;            // {pairs, words} of those batches
+    PinnedBuf<unsigned char> h_sx_head_pos;  // fixed size, never moved: positions of variance mode's deferred batches (in flight across calls)
+    PinnedBuf<u64> h_sx_head_stat;           //                          their {pairs, words}
     // variance mode, grouped sparse batches: u16 slot triangles (half the bytes between k_sx_consume and the Welford pass); a
     // sum above 65535 raises the batch's flag in pinned memory and the batch is redone with u32 triangles, which the
     // sequences then keep (slots16_ok). Tuning var_slots16 = 0: never.
     bool sx_slot16 = false;              // set by run_variance_mode around the accumulate of a deferred batch
     bool sx_slot16_used = false;         // what accumulate_sparse really did
     bool slots16_ok = true;
-    uint32_t* h_sx_head_flag = nullptr;  // pinned, fixed size: one overflow flag per deferred batch
+    PinnedBuf<uint32_t> h_sx_head_flag;  // fixed size: one overflow flag per deferred batch
     uint32_t* sx_ovf_now = nullptr;      // the flag of the batch being enqueued
     int sx_last_lane = 0;                // the lane (scratch + stream) the last accumulate_sparse ran in
     u64 sx_shape[4] = {0, 0, 0, 0};      // sequences, windows, alphabet, longest sequence of the set at hand
     double sx_ppr = 0;                   // most pairs (the reference's +=) per sort record of a batch since the sequences were loaded
-    bool sx_desc_used = false;           // the last batch of the owner-band form sent descriptors (fsk_stats.sparse_desc)
     double sx_wpr = 0;                   // most update words per sort record of a batch since the sequences were loaded (0: none seen)
     u64 sx_words_of(u64 nrec) const { return (u64)(sx_wpr * (double)nrec) + 1; }  // what a batch of nrec records is expected to emit
     void sx_saw(u64 words, u64 nrec) { if (nrec) sx_wpr = std::max(sx_wpr, std::max(1e-9, (double)words / (double)nrec)); }
@@ -440,8 +475,7 @@ struct fsk_engine {
         sx_ppr = std::max(sx_ppr, (double)pairs / (double)nrec);
         if (!was && sx_desc_now()) sx_wpr = 0;
     }
-    struct SxDefer { bool active = false; u64 cap = 0, nrec = 0; } sx_defer[8];
-    u64 sx_redone = 0;                   // batches redone because they did not fit
+    u64 sx_redone = 0;                   // batches redone because they did not fit (outside Loaded: counted over the engine's life)
     bool sx_redoing = false;             // set around such a redo: the batch waits for its word count and is sized exactly
     bool sx_exactly() const { return tune.sparse_sync != 0 || sx_redoing; }
     // update words per batch beyond which the pairs go to K with atomics
@@ -468,46 +502,42 @@ struct fsk_engine {
     // is waited for on the spot (and the exact update count U is computed; the sparse dataflow runs on one stream, every batch
     // sized exactly). profile = 2: the PRODUCT dataflow, untouched — the events are only recorded (on the stream the kernels
     // are launched on) and their times are harvested later, by fsk_get_stats or when some hundred intervals are pending.
-    struct LazyTime { hipEvent_t a, b; double* acc; };
+    struct LazyTime { Event a, b; double* acc; };
     std::vector<LazyTime> lazy_pending;
-    std::vector<hipEvent_t> lazy_free;
-    hipEvent_t lazy_open = nullptr;
+    std::vector<Event> lazy_free;
+    Event lazy_open;
     bool profile_sync() const { return cfg.profile == 1; }
-    hipEvent_t lazy_event() {
-        hipEvent_t ev = nullptr;
-        if (!lazy_free.empty()) { ev = lazy_free.back(); lazy_free.pop_back(); }
-        else if (hipEventCreate(&ev) != hipSuccess) ev = nullptr;
+    Event lazy_event() {  // (null when none can be made: the interval is then dropped)
+        Event ev;
+        if (!lazy_free.empty()) { ev = std::move(lazy_free.back()); lazy_free.pop_back(); }
+        else if (ev.create(0) != hipSuccess) (void)hipGetLastError();
         return ev;
     }
+    void lazy_done(LazyTime& t, bool reached) {  // the interval's time, and its events back into the pool
+        float ms = 0;
+        if (reached && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) *t.acc += ms;
+        lazy_free.push_back(std::move(t.a));
+        lazy_free.push_back(std::move(t.b));
+    }
     void harvest_times() {
-        for (const LazyTime& t : lazy_pending) {
-            float ms = 0;
-            if (hipEventSynchronize(t.b) == hipSuccess && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) *t.acc += ms;
-            lazy_free.push_back(t.a);
-            lazy_free.push_back(t.b);
-        }
+        for (LazyTime& t : lazy_pending) lazy_done(t, hipEventSynchronize(t.b) == hipSuccess);
         lazy_pending.clear();
     }
     // the intervals whose end event has been reached already (never a wait: profile = 2 leaves the dataflow alone)
     void harvest_finished() {
         size_t keep = 0;
-        for (size_t i = 0; i < lazy_pending.size(); ++i) {
-            const LazyTime t = lazy_pending[i];
-            float ms = 0;
-            if (hipEventQuery(t.b) == hipSuccess) {
-                if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) *t.acc += ms;
-                lazy_free.push_back(t.a);
-                lazy_free.push_back(t.b);
-            } else {
+        for (LazyTime& t : lazy_pending) {
+            if (hipEventQuery(t.b) == hipSuccess) lazy_done(t, true);
+            else {
                 (void)hipGetLastError();
-                lazy_pending[keep++] = t;
+                lazy_pending[keep++] = std::move(t);
             }
         }
         lazy_pending.resize(keep);
     }
-    void lazy_interval(hipEvent_t a, hipEvent_t b, double* acc) {
-        if (!a || !b) { if (a) lazy_free.push_back(a); if (b) lazy_free.push_back(b); return; }
-        lazy_pending.push_back(LazyTime{a, b, acc});
+    void lazy_interval(Event a, Event b, double* acc) {
+        if (!a || !b) return;
+        lazy_pending.push_back(LazyTime{std::move(a), std::move(b), acc});
         // (a long accumulate: collect what has finished; what has not stays pending — the vector grows, nothing blocks.
         // Only fsk_get_stats, a change of mode and fsk_destroy wait: harvest_times)
         if (lazy_pending.size() >= 512 && lazy_pending.size() % 128 == 0) harvest_finished();
@@ -515,7 +545,7 @@ struct fsk_engine {
     void tic(hipStream_t s = nullptr) {
         if (cfg.profile == 1) (void)hipEventRecord(ev0, s ? s : stream);
         else if (cfg.profile == 2) {
-            if (lazy_open) lazy_free.push_back(lazy_open);
+            if (lazy_open) lazy_free.push_back(std::move(lazy_open));
             lazy_open = lazy_event();
             if (lazy_open) (void)hipEventRecord(lazy_open, s ? s : stream);
         }
@@ -528,10 +558,9 @@ struct fsk_engine {
             (void)hipEventElapsedTime(&ms, ev0, ev1);
             *acc += ms;
         } else if (cfg.profile == 2 && lazy_open) {
-            hipEvent_t b = lazy_event();
+            Event b = lazy_event();
             if (b) (void)hipEventRecord(b, s ? s : stream);
-            lazy_interval(lazy_open, b, acc);
-            lazy_open = nullptr;
+            lazy_interval(std::move(lazy_open), std::move(b), acc);
         }
     }
 };

@@ -24,12 +24,6 @@ double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// the build's scratch leaves with the build, whichever way it ends
-struct Scratch {
-    DevBuf<double> b;
-    ~Scratch() { b.release(); }
-};
-
 int rows_ready(fsk_engine* e) {
     if (!e->finalized || !e->rows.valid) return e->fail(FSK_ESTATE, "no rows kernel: call fsk_rows_build on a finalized result first");
     return FSK_OK;
@@ -67,8 +61,8 @@ int fsk_detail::rows_build(fsk_engine* e) {
         return e->fail(FSK_ENOMEM, "cannot allocate the rows kernel: %llu bytes (%.1f GB) for %llu sequences on device %d",
                        (unsigned long long)((L_cells + N) * sizeof(double)), (double)(L_cells + N) * 8e-9, (unsigned long long)N, e->cfg.device);
     }
-    Scratch scratch;
-    if (scratch.b.reserve((size_t)scratch_cells) != hipSuccess) {
+    DevBuf<double> scratch;  // (leaves with the build, whichever way it ends)
+    if (scratch.reserve((size_t)scratch_cells) != hipSuccess) {
         (void)hipGetLastError();
         R.drop();
         return e->fail(FSK_ENOMEM, "cannot allocate the scratch of the rows kernel: %llu bytes (%.1f GB) for %llu train columns of %llu sequences on device %d",
@@ -82,11 +76,11 @@ int fsk_detail::rows_build(fsk_engine* e) {
     const double t0 = now_ms();
     const u64 chunk = (u64)1 << 33;
     for (u64 c0 = 0; c0 < tri_cells; c0 += chunk) {
-        const int rc = launch_triangle(e, c0, std::min<u64>(chunk, tri_cells - c0), scratch.b.p + c0);
+        const int rc = launch_triangle(e, c0, std::min<u64>(chunk, tri_cells - c0), scratch.p + c0);
         if (rc) { R.drop(); return rc; }
     }
     if (nt > 0) {
-        const int rc = fsk_get_block_device(e, (int64_t)n, (int64_t)N, 0, (int64_t)n, scratch.b.p + rect_off);
+        const int rc = fsk_get_block_device(e, (int64_t)n, (int64_t)N, 0, (int64_t)n, scratch.p + rect_off);
         if (rc) { R.drop(); return rc; }
     }
     FSK_HIP(hipStreamSynchronize(e->stream));
@@ -94,7 +88,7 @@ int fsk_detail::rows_build(fsk_engine* e) {
 
     // 2. the product. The test rows of L are zero but for their train columns and their diagonal.
     if (nt > 0) FSK_HIP(hipMemsetAsync(R.d_L.p + tri_cells, 0, (size_t)(L_cells - tri_cells) * sizeof(double), e->stream));
-    const fsk::RowsSrc src{scratch.b.p, scratch.b.p + rect_off, (uint32_t)n, (uint32_t)N};
+    const fsk::RowsSrc src{scratch.p, scratch.p + rect_off, (uint32_t)n, (uint32_t)N};
     const uint32_t T = fsk::ROWS_TILE, ncb = (uint32_t)((n + T - 1) / T), nrb = (uint32_t)((N + T - 1) / T);
     double *Lp = R.d_L.p, *dp = R.d_diag.p;
     FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_rows_syrk, fsk::ROWS_LDS_BYTES));

@@ -138,7 +138,7 @@ void sx_with_flags(F&& f, bool flag, Flags... rest) {
 // The LSD passes over `bits` bits from bit `shift0` of the records of n_slots slots (the digits of the first pass have been
 // counted by whoever wrote the records). *cur: which of rec[0] / rec[1] holds the result.
 template <typename T>
-int sx_sort(fsk_engine* e, SxScratch& S, hipStream_t stream, T* const rec[2], uint32_t nfeat, uint32_t tps, uint32_t n_slots, int shift0,
+int sx_sort(fsk_engine* e, SxScratch* S, hipStream_t stream, T* const rec[2], uint32_t nfeat, uint32_t tps, uint32_t n_slots, int shift0,
             int bits, int* cur_out) {
     const int passes = (bits + 7) / 8;
     // the bits split evenly over the passes: 19 bits sort as 7 + 6 + 6, not 8 + 8 + 3 (a ballot per bit and record)
@@ -148,14 +148,14 @@ int sx_sort(fsk_engine* e, SxScratch& S, hipStream_t stream, T* const rec[2], ui
         const int nbits = pass_bits(p);
         if (p > 0)
             FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_sx_hist<T>), dim3(tps, n_slots), dim3(256), 0, stream, (const T*)rec[cur], nfeat, tps, shift,
-                       (1u << nbits) - 1u, S.d_blockhist.p);
-        FSK_LAUNCH(fsk::k_sx_scan_slot, dim3(n_slots), dim3(1024), 0, stream, S.d_blockhist.p, tps, S.d_totals.p);
+                       (1u << nbits) - 1u, S->d_blockhist.p);
+        FSK_LAUNCH(fsk::k_sx_scan_slot, dim3(n_slots), dim3(1024), 0, stream, S->d_blockhist.p, tps, S->d_totals.p);
         {   // (function pointers: a template-id with a comma cannot pass through the launch macro; 4 bits at least)
             decltype(&fsk::k_sx_scatter<T, 8>) const k_scatter[] = {fsk::k_sx_scatter<T, 4>, fsk::k_sx_scatter<T, 5>, fsk::k_sx_scatter<T, 6>,
                                                                     fsk::k_sx_scatter<T, 7>, fsk::k_sx_scatter<T, 8>};
             const auto k = k_scatter[std::max(nbits, 4) - 4];
             FSK_LAUNCH(k, dim3(fsk::xcd_grid(tps * n_slots)), dim3(256), 0, stream, (const T*)rec[cur], rec[cur ^ 1], nfeat, tps, n_slots,
-                       shift, nbits, (const uint32_t*)S.d_blockhist.p, (const uint32_t*)S.d_totals.p);
+                       shift, nbits, (const uint32_t*)S->d_blockhist.p, (const uint32_t*)S->d_totals.p);
         }
         cur ^= 1;
         e->st.launches += 3;
@@ -250,7 +250,7 @@ struct SxBatch {
 template <typename RecT>
 int sx_batch_begin(SxBatch& c) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     const int nb = c.nb;
     const uint32_t nfeat = c.nfeat = (uint32_t)e->nfeat;
     const size_t nrec = c.nrec = (size_t)nb * nfeat;
@@ -260,8 +260,8 @@ int sx_batch_begin(SxBatch& c) {
     // (consecutive combos keep the same leading positions for long stretches: those are sorted once per group)
     const SxShare sh = c.sh = nb > 16 ? sx_plan_share(e, c.combos, nb, 8 * (int)sizeof(RecT)) : SxShare();
     c.keybits = sh.share ? sh.lowbits : e->sx_keybits;  // (what every slot sorts)
-    e->sx_share_used = sh.share;
-    e->sx_share_groups = sh.groups;
+    e->ld.sx_share_used = sh.share;
+    e->ld.sx_share_groups = sh.groups;
     if (e->trace())
         fprintf(stderr, "[fsk] sparse batch: %d slots, shared leading positions %d (%u groups, %d + %d key bits; plain %d)\n", nb, sh.share, sh.groups,
                 sh.topbits, sh.lowbits, e->sx_keybits);
@@ -271,7 +271,7 @@ int sx_batch_begin(SxBatch& c) {
     // the form of the update stage (sx_choose_form); a batch of slot triangles (variance mode) knows the owner bands only
     c.form = c.slot_stride != 0 ? ((e->sx_lists && e->sx_form != 1) ? 0 : 1) : e->sx_form;
     const bool lists = c.form == 0, blocks = c.form == 2;
-    e->sx_form_used = c.form;
+    e->ld.sx_form_used = c.form;
     c.pairs = lists && e->sx_pairs ? 1 : 0;  // (unit products as bare cells, two to a word: plan_owner_bands)
     c.slot16 = c.slot_stride != 0 && e->sx_slot16_used;  // (u16 slot triangles: set by accumulate_sparse for a deferred batch)
     c.O = blocks ? (uint32_t)e->tune.blocks_max_bands : e->n_owners;  // (blocks: the most bands a pass can have)
@@ -281,7 +281,7 @@ int sx_batch_begin(SxBatch& c) {
     c.desc = !e->sx_desc_now() ? 0u : lists ? 1u : (blocks && e->tune.sparse_desc_blocks) ? 2u : 0u;
     c.short_max = c.desc && e->tune.sparse_desc_min > 0 ? (uint32_t)std::min<int64_t>(e->tune.sparse_desc_min, (int64_t)fsk::SX_SHORT) : fsk::SX_SHORT;
     c.OC = c.desc ? 2u * c.O : c.O;  // columns
-    e->sx_desc_used = c.desc != 0;
+    e->ld.sx_desc_used = c.desc != 0;
     // skip_test_block: test rows pair only with the train entries of their runs (and themselves)
     c.skip_from = e->cfg.skip_test_block && e->n_test > 0 ? (uint32_t)e->n_train : 0xffffffffu;
     c.skipping = c.skip_from != 0xffffffffu;
@@ -301,22 +301,22 @@ int sx_batch_begin(SxBatch& c) {
 
     // (the presort's records, 4 or 8 bytes a window and group, go through the same two buffers first)
     const size_t pre_bytes = sh.share ? (size_t)sh.groups * nfeat * (sh.pre64 ? 8 : 4) : 0;
-    for (int b = 0; b < 2; ++b) FSK_HIP(S.d_keys[b].reserve(std::max(pre_bytes, nrec * sizeof(RecT))));
-    FSK_HIP(S.d_blockhist.reserve((size_t)256 * c.tps * nb));
-    FSK_HIP(S.d_totals.reserve((size_t)256 * nb));
-    FSK_HIP(S.d_tile_ent.reserve(ntiles));
-    FSK_HIP(S.d_tile_lrh.reserve(ntiles));
-    FSK_HIP(S.d_tile_rs.reserve(ntiles));
-    FSK_HIP(S.d_ebase.reserve((size_t)ntiles + 1));
-    FSK_HIP(S.d_E.reserve(nrec + 2));  // (+ 16 bytes: the descriptors' partners are read in whole 16-byte pieces)
-    FSK_HIP(S.d_Pk.reserve(nrec));
+    for (int b = 0; b < 2; ++b) FSK_HIP(S->d_keys[b].reserve(std::max(pre_bytes, nrec * sizeof(RecT))));
+    FSK_HIP(S->d_blockhist.reserve((size_t)256 * c.tps * nb));
+    FSK_HIP(S->d_totals.reserve((size_t)256 * nb));
+    FSK_HIP(S->d_tile_ent.reserve(ntiles));
+    FSK_HIP(S->d_tile_lrh.reserve(ntiles));
+    FSK_HIP(S->d_tile_rs.reserve(ntiles));
+    FSK_HIP(S->d_ebase.reserve((size_t)ntiles + 1));
+    FSK_HIP(S->d_E.reserve(nrec + 2));  // (+ 16 bytes: the descriptors' partners are read in whole 16-byte pieces)
+    FSK_HIP(S->d_Pk.reserve(nrec));
     if (c.skipping) {
-        FSK_HIP(S.d_Tk.reserve(nrec));
-        FSK_HIP(S.d_tile_lth.reserve(ntiles));
-        FSK_HIP(S.d_tile_ts.reserve(ntiles));
+        FSK_HIP(S->d_Tk.reserve(nrec));
+        FSK_HIP(S->d_tile_lth.reserve(ntiles));
+        FSK_HIP(S->d_tile_ts.reserve(ntiles));
     }
-    FSK_HIP(S.d_sxstat.reserve(3));
-    FSK_HIP(S.d_tile_stat.reserve((size_t)2 * ntiles));
+    FSK_HIP(S->d_sxstat.reserve(3));
+    FSK_HIP(S->d_tile_stat.reserve((size_t)2 * ntiles));
     FSK_HIP(e->d_pos.reserve(c.pos_off + (size_t)nb * e->k));
     if (!e->owner_ready) {
         FSK_HIP(e->d_owner_r0.reserve(e->h_owner_r0.size()));
@@ -325,11 +325,11 @@ int sx_batch_begin(SxBatch& c) {
         e->owner_ready = true;
     }
     if (lists || blocks) {
-        FSK_HIP(S.d_ucount.reserve((size_t)c.OC * ntiles));
-        FSK_HIP(S.d_uchunk.reserve((size_t)c.OC * c.nchunks));
-        FSK_HIP(S.d_utot.reserve(c.OC));
-        FSK_HIP(S.d_list_off.reserve((size_t)c.OC + 1));
-        FSK_HIP(S.d_part_base.reserve((size_t)c.O + 2));
+        FSK_HIP(S->d_ucount.reserve((size_t)c.OC * ntiles));
+        FSK_HIP(S->d_uchunk.reserve((size_t)c.OC * c.nchunks));
+        FSK_HIP(S->d_utot.reserve(c.OC));
+        FSK_HIP(S->d_list_off.reserve((size_t)c.OC + 1));
+        FSK_HIP(S->d_part_base.reserve((size_t)c.O + 2));
     }
     // positions: a handful of combos (variance mode) by id, a run of consecutive combo ids (every exact call) as a piece of
     // the resident table of all combos, anything else through the pinned staging (the batch's statistics are zeroed by the
@@ -358,20 +358,20 @@ int sx_batch_begin(SxBatch& c) {
 template <typename RecT, typename T>
 int sx_presort(const SxBatch& c, const fsk::SxSrc& src, bool small) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     const SxShare& sh = c.sh;
     const uint32_t G = sh.groups, nfeat = c.nfeat, tps = c.tps;
-    FSK_HIP(S.d_group_of.reserve((size_t)c.nb));
-    FSK_HIP(S.d_group_head.reserve((size_t)c.nb));
-    FSK_HIP(S.d_winp.reserve((size_t)G * nfeat * e->win_words));
-    FSK_HIP(S.d_part.reserve((size_t)G * nfeat * sizeof(RecT)));
-    FSK_LAUNCH(fsk::k_sx_group_tables, dim3(1), dim3(1024), 0, c.stream, src, (uint32_t)c.nb, sh.share, S.d_group_of.p, S.d_group_head.p);
-    T* pre[2] = {(T*)S.d_keys[0].p, (T*)S.d_keys[1].p};
+    FSK_HIP(S->d_group_of.reserve((size_t)c.nb));
+    FSK_HIP(S->d_group_head.reserve((size_t)c.nb));
+    FSK_HIP(S->d_winp.reserve((size_t)G * nfeat * e->win_words));
+    FSK_HIP(S->d_part.reserve((size_t)G * nfeat * sizeof(RecT)));
+    FSK_LAUNCH(fsk::k_sx_group_tables, dim3(1), dim3(1024), 0, c.stream, src, (uint32_t)c.nb, sh.share, S->d_group_of.p, S->d_group_head.p);
+    T* pre[2] = {(T*)S->d_keys[0].p, (T*)S->d_keys[1].p};
     const uint32_t dmask_top = (1u << sx_first_pass_bits(sh.topbits)) - 1u;
     sx_with_flags([&](auto w2, auto sm) {
         auto k = fsk::k_sx_group_extract<T, w2 ? 2 : 4, sm && sizeof(T) == 4>;
-        FSK_LAUNCH(k, dim3(tps, G), dim3(256), 0, c.stream, src, (const uint32_t*)S.d_group_head.p, sh.share, sh.wb, nfeat, tps, pre[0],
-                   S.d_blockhist.p, dmask_top);
+        FSK_LAUNCH(k, dim3(tps, G), dim3(256), 0, c.stream, src, (const uint32_t*)S->d_group_head.p, sh.share, sh.wb, nfeat, tps, pre[0],
+                   S->d_blockhist.p, dmask_top);
     }, e->win_words == 2, small);
     int cur = 0;
     const int rc = sx_sort<T>(e, S, c.stream, pre, nfeat, tps, G, sh.wb, sh.topbits, &cur);
@@ -379,7 +379,7 @@ int sx_presort(const SxBatch& c, const fsk::SxSrc& src, bool small) {
     sx_with_flags([&](auto w2) {
         auto k = fsk::k_sx_group_gather<T, RecT, w2 ? 2 : 4>;
         FSK_LAUNCH(k, dim3((nfeat + 255u) / 256u, G), dim3(256), 0, c.stream, (const T*)pre[cur], (const uint32_t*)e->d_win.p,
-                   (const uint32_t*)e->d_featseq.p, nfeat, sh.wb, sh.lowbits + e->sx_sb, S.d_winp.p, (RecT*)S.d_part.p);
+                   (const uint32_t*)e->d_featseq.p, nfeat, sh.wb, sh.lowbits + e->sx_sb, S->d_winp.p, (RecT*)S->d_part.p);
     }, e->win_words == 2);
     e->st.launches += 3;
     return FSK_OK;
@@ -390,11 +390,11 @@ int sx_presort(const SxBatch& c, const fsk::SxSrc& src, bool small) {
 template <typename RecT>
 int sx_extract(const SxBatch& c) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     const uint32_t nfeat = c.nfeat, tps = c.tps, nb = (uint32_t)c.nb;
-    RecT* const rec = (RecT*)S.d_keys[0].p;
+    RecT* const rec = (RecT*)S->d_keys[0].p;
     const uint32_t dmask = (1u << sx_first_pass_bits(c.keybits)) - 1u;
-    u64* const zeroed_stats = S.d_sxstat.p;
+    u64* const zeroed_stats = S->d_sxstat.p;
     const int ww = e->win_words;
     constexpr bool R32 = sizeof(RecT) == 4;
     const bool small = R32 && e->V <= ((u64)1 << 24) && e->sigma < (1u << 24);  // (the k-mer and every prefix of it fit 24 bits)
@@ -409,23 +409,23 @@ int sx_extract(const SxBatch& c) {
     if (c.sh.share) {
         const int rc = c.sh.pre64 ? sx_presort<RecT, u64>(c, src, small) : sx_presort<RecT, uint32_t>(c, src, small);
         if (rc) return rc;
-        src.win = S.d_winp.p;
+        src.win = S->d_winp.p;
         src.c0 = c.sh.share;
         sx_with_flags([&](auto w2, auto sm, auto f4) {
             auto k = fsk::k_sx_extract_shared<RecT, w2 ? 2 : 4, sm && R32, f4 ? 4 : 1>;
-            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, (const uint32_t*)S.d_group_of.p, (const RecT*)S.d_part.p, nfeat, tps, nb, rec,
-                       S.d_blockhist.p, dmask, zeroed_stats);
+            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, (const uint32_t*)S->d_group_of.p, (const RecT*)S->d_part.p, nfeat, tps, nb, rec,
+                       S->d_blockhist.p, dmask, zeroed_stats);
         }, ww == 2, small, four);
     } else if (ww) {
         sx_with_flags([&](auto w2, auto sm, auto f4) {
             auto k = fsk::k_sx_extract_win<RecT, w2 ? 2 : 4, sm && R32, f4 ? 4 : 1>;
-            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, nfeat, tps, nb, rec, S.d_blockhist.p, dmask, zeroed_stats);
+            FSK_LAUNCH(k, grid, dim3(256), 0, c.stream, src, nfeat, tps, nb, rec, S->d_blockhist.p, dmask, zeroed_stats);
         }, ww == 2, small, four);
     } else {
         auto k = e->revcomp ? fsk::k_sx_extract<RecT, true> : fsk::k_sx_extract<RecT, false>;
         if (e->fwin_on) k = e->revcomp ? fsk::k_sx_extract<RecT, true, true> : fsk::k_sx_extract<RecT, false, true>;
         FSK_LAUNCH(k, dim3(tps, nb), dim3(256), 0, c.stream, e->view(), (const uint32_t*)e->d_featseq.p,
-                   (const uint32_t*)e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S.d_blockhist.p, dmask, c.ids, zeroed_stats,
+                   (const uint32_t*)e->d_fstart.p, nfeat, tps, e->k, e->sigma, e->sx_sb, c.pos_tab, rec, S->d_blockhist.p, dmask, c.ids, zeroed_stats,
                    c.by_id ? 1 : 0, e->sx_symbits, e->revcomp ? (const uint16_t*)e->d_comp.p : (const uint16_t*)nullptr, e->cfg.g,
                    e->fwin_on ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
     }
@@ -440,45 +440,45 @@ int sx_extract(const SxBatch& c) {
 template <typename RecT>
 int sx_segment(SxBatch& c) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     const uint32_t ntiles = c.ntiles;
     const bool skipping = c.skipping;
     e->tic(c.stream);
     {
         auto k_cnt = skipping ? fsk::k_sx_seg_count<RecT, true> : fsk::k_sx_seg_count<RecT, false>;
-        FSK_LAUNCH(k_cnt, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, S.d_tile_ent.p,
-                   S.d_tile_lrh.p, c.skip_from, skipping ? S.d_tile_lth.p : (int*)nullptr);
+        FSK_LAUNCH(k_cnt, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, S->d_tile_ent.p,
+                   S->d_tile_lrh.p, c.skip_from, skipping ? S->d_tile_lth.p : (int*)nullptr);
     }
-    const int* lth = skipping ? (const int*)S.d_tile_lth.p : (const int*)nullptr;
-    int* ts = skipping ? S.d_tile_ts.p : (int*)nullptr;
+    const int* lth = skipping ? (const int*)S->d_tile_lth.p : (const int*)nullptr;
+    int* ts = skipping ? S->d_tile_ts.p : (int*)nullptr;
     if (ntiles <= 4096u && !e->tune.seg_scan_chunked) {
-        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
-                   S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)S->d_tile_ent.p, (const int*)S->d_tile_lrh.p, ntiles,
+                   S->d_ebase.p, S->d_tile_rs.p, lth, ts, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
                    (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
     } else {
         const uint32_t nch = (ntiles + 1023u) / 1024u;
-        FSK_HIP(S.d_segc.reserve((size_t)6 * (nch + 1)));
-        uint32_t* c_tot = S.d_segc.p;
+        FSK_HIP(S->d_segc.reserve((size_t)6 * (nch + 1)));
+        uint32_t* c_tot = S->d_segc.p;
         int* c_lrh = reinterpret_cast<int*>(c_tot + (nch + 1));
         int* c_lth = c_lrh + (nch + 1);
         uint32_t* c_ex = reinterpret_cast<uint32_t*>(c_lth + (nch + 1));
         int* c_h = reinterpret_cast<int*>(c_ex + (nch + 1));
         int* c_t = c_h + (nch + 1);
-        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S->d_tile_ent.p, (const int*)S->d_tile_lrh.p, ntiles,
                    (uint32_t*)nullptr, (int*)nullptr, lth, (int*)nullptr, (const uint32_t*)nullptr, (const int*)nullptr, (const int*)nullptr,
                    c_tot, c_lrh, c_lth);
         FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(1), dim3(1024), 0, c.stream, (const uint32_t*)c_tot, (const int*)c_lrh, nch, c_ex, c_h,
                    skipping ? (const int*)c_lth : (const int*)nullptr, skipping ? c_t : (int*)nullptr, (const uint32_t*)nullptr,
                    (const int*)nullptr, (const int*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr);
-        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S.d_tile_ent.p, (const int*)S.d_tile_lrh.p, ntiles,
-                   S.d_ebase.p, S.d_tile_rs.p, lth, ts, (const uint32_t*)c_ex, (const int*)c_h, (const int*)c_t, (uint32_t*)nullptr,
+        FSK_LAUNCH(fsk::k_sx_seg_scan, dim3(nch), dim3(1024), 0, c.stream, (const uint32_t*)S->d_tile_ent.p, (const int*)S->d_tile_lrh.p, ntiles,
+                   S->d_ebase.p, S->d_tile_rs.p, lth, ts, (const uint32_t*)c_ex, (const int*)c_h, (const int*)c_t, (uint32_t*)nullptr,
                    (int*)nullptr, (int*)nullptr);
         e->st.launches += 2;
     }
     // descriptors: the entries' column array, what their partners are read from (tuning sparse_desc_cols)
     if (c.desc && (e->tune.sparse_desc_cols >= 2 || (e->tune.sparse_desc_cols == 1 && !c.packed))) {
-        FSK_HIP(S.d_cols.reserve(((c.col16 & 1) ? (c.nrec + 1) / 2 : c.nrec) + 4));  // (+ 16 bytes: a lane's last load reads whole 16-byte pieces)
-        c.colp = (void*)S.d_cols.p;
+        FSK_HIP(S->d_cols.reserve(((c.col16 & 1) ? (c.nrec + 1) / 2 : c.nrec) + 4));  // (+ 16 bytes: a lane's last load reads whole 16-byte pieces)
+        c.colp = (void*)S->d_cols.p;
     }
     return FSK_OK;
 }
@@ -502,15 +502,15 @@ SxBands sx_owner_bands(const SxBatch& c) {
 template <typename RecT>
 void sx_seg_write(const SxBatch& c, const SxBands& b) {
     const fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
-    uint32_t* const ucount = c.form == 1 ? nullptr : S.d_ucount.p;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
+    uint32_t* const ucount = c.form == 1 ? nullptr : S->d_ucount.p;
     sx_with_flags([&](auto packed, auto pairs, auto skip, auto desc) {
         using X = fsk::SxEnt<packed>;
         auto k = fsk::k_sx_seg_write<RecT, packed, pairs, skip, desc>;
-        FSK_LAUNCH(k, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, (const uint32_t*)S.d_ebase.p,
-                   (const int*)S.d_tile_rs.p, reinterpret_cast<typename X::ent_t*>(S.d_E.p), reinterpret_cast<typename X::rank_t*>(S.d_Pk.p),
-                   b.shift, b.n, ucount, b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.cwide, S.d_tile_stat.p, c.skip_from,
-                   skip ? (const int*)S.d_tile_ts.p : (const int*)nullptr, skip ? reinterpret_cast<typename X::rank_t*>(S.d_Tk.p) : nullptr,
+        FSK_LAUNCH(k, dim3(c.tpg, c.nb), dim3(256), 0, c.stream, (const RecT*)c.sorted, c.nfeat, c.tpg, e->sx_sb, (const uint32_t*)S->d_ebase.p,
+                   (const int*)S->d_tile_rs.p, reinterpret_cast<typename X::ent_t*>(S->d_E.p), reinterpret_cast<typename X::rank_t*>(S->d_Pk.p),
+                   b.shift, b.n, ucount, b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.cwide, S->d_tile_stat.p, c.skip_from,
+                   skip ? (const int*)S->d_tile_ts.p : (const int*)nullptr, skip ? reinterpret_cast<typename X::rank_t*>(S->d_Tk.p) : nullptr,
                    b.own_base, c.short_max, c.desc, b.sub_shift, c.colp, c.col16);
     }, c.packed, c.pairs != 0, c.skipping, c.desc != 0);
 }
@@ -518,27 +518,27 @@ void sx_seg_write(const SxBatch& c, const SxBands& b) {
 // k_sx_ucol_*: where every (tile, column) share of the update streams starts, and the batch's pair and word totals (into
 // stat_pin)
 void sx_stream_offsets(const SxBatch& c, uint32_t cols) {
-    SxScratch& S = *c.S;
-    FSK_LAUNCH(fsk::k_sx_ucol_sum, dim3(c.nchunks), dim3(256), 0, c.stream, (const uint32_t*)S.d_ucount.p, c.ntiles, cols, S.d_uchunk.p,
-               (const u64*)S.d_tile_stat.p, S.d_sxstat.p, c.stat_pin, c.uc);
-    FSK_LAUNCH(fsk::k_sx_ucol_scan, dim3(cols), dim3(256), 0, c.stream, S.d_uchunk.p, c.nchunks, cols, S.d_utot.p);
-    FSK_LAUNCH(fsk::k_sx_ucol_apply, dim3(c.nchunks), dim3(256), 0, c.stream, S.d_ucount.p, c.ntiles, cols, (const uint32_t*)S.d_uchunk.p,
-               (const uint32_t*)S.d_utot.p, S.d_list_off.p, c.uc);
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
+    FSK_LAUNCH(fsk::k_sx_ucol_sum, dim3(c.nchunks), dim3(256), 0, c.stream, (const uint32_t*)S->d_ucount.p, c.ntiles, cols, S->d_uchunk.p,
+               (const u64*)S->d_tile_stat.p, S->d_sxstat.p, c.stat_pin, c.uc);
+    FSK_LAUNCH(fsk::k_sx_ucol_scan, dim3(cols), dim3(256), 0, c.stream, S->d_uchunk.p, c.nchunks, cols, S->d_utot.p);
+    FSK_LAUNCH(fsk::k_sx_ucol_apply, dim3(c.nchunks), dim3(256), 0, c.stream, S->d_ucount.p, c.ntiles, cols, (const uint32_t*)S->d_uchunk.p,
+               (const uint32_t*)S->d_utot.p, S->d_list_off.p, c.uc);
 }
 
 // k_sx_emit: the update words of the entries, binned by band into the streams — or, `direct`, each one 64-bit atomic into
 // K (no streams, no descriptors)
 void sx_emit(const SxBatch& c, const SxBands& b, bool direct, u64 cap_words) {
     const fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     sx_with_flags([&](auto dir, auto skip, auto packed, auto desc) {
         using X = fsk::SxEnt<packed>;
         auto k = fsk::k_sx_emit<dir, skip, packed, desc && !dir>;
-        FSK_LAUNCH(k, dim3(fsk::xcd_grid(c.ntiles)), dim3(fsk::EM_THREADS), 0, c.stream, reinterpret_cast<const typename X::ent_t*>(S.d_E.p),
-                   reinterpret_cast<const typename X::rank_t*>(S.d_Pk.p), (const uint32_t*)S.d_ebase.p, b.r0, b.shift, b.n,
-                   dir ? nullptr : (const uint32_t*)S.d_list_off.p, dir ? nullptr : (const uint32_t*)S.d_ucount.p, dir ? nullptr : S.d_ulist.p,
+        FSK_LAUNCH(k, dim3(fsk::xcd_grid(c.ntiles)), dim3(fsk::EM_THREADS), 0, c.stream, reinterpret_cast<const typename X::ent_t*>(S->d_E.p),
+                   reinterpret_cast<const typename X::rank_t*>(S->d_Pk.p), (const uint32_t*)S->d_ebase.p, b.r0, b.shift, b.n,
+                   dir ? nullptr : (const uint32_t*)S->d_list_off.p, dir ? nullptr : (const uint32_t*)S->d_ucount.p, dir ? nullptr : S->d_ulist.p,
                    b.row0, b.row1, e->maxW, b.maxprod, b.cmax, b.cwide, b.pb, c.K, c.tpg, c.slot_stride,
-                   skip ? reinterpret_cast<const typename X::rank_t*>(S.d_Tk.p) : nullptr, dir ? nullptr : (const u64*)S.d_sxstat.p, cap_words,
+                   skip ? reinterpret_cast<const typename X::rank_t*>(S->d_Tk.p) : nullptr, dir ? nullptr : (const u64*)S->d_sxstat.p, cap_words,
                    c.ntiles, dir ? 0 : c.pairs, b.own_base, dir ? fsk::SX_SHORT : c.short_max, dir ? 0u : c.desc, b.sub_shift);
     }, direct, c.skipping, c.packed, c.desc != 0);
 }
@@ -547,7 +547,7 @@ void sx_emit(const SxBatch& c, const SxBands& b, bool direct, u64 cap_words) {
 // them), or (variance mode) by slot, into the slots' own triangles. After k_wait.
 int sx_consume(const SxBatch& c, u64 words, u64 cap_words) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     const uint32_t O = c.O;
     const size_t lds = (size_t)e->sx_cap * sizeof(uint32_t), lds_slot = (size_t)e->sx_cap_slot * sizeof(uint32_t);
     FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<false>, lds));
@@ -560,22 +560,22 @@ int sx_consume(const SxBatch& c, u64 words, u64 cap_words) {
     // (with descriptors k_sx_parts sets the target itself: about sparse_desc_parts parts, at most one more a band)
     const uint32_t desc_parts = (uint32_t)std::max<int64_t>(1, e->tune.sparse_desc_parts);
     const uint32_t max_parts = c.desc ? O + desc_parts + 9u : O + (uint32_t)(((c.guard_cap ? c.guard_cap : words) + target - 1) / target);
-    const void* const Ep = (const void*)S.d_E.p;
-    if (c.slot_stride == 0) FSK_HIP(S.d_part_base.reserve((size_t)O + 8 + (size_t)4 * max_parts));  // (bases, total, target, then 16 bytes a part)
+    const void* const Ep = (const void*)S->d_E.p;
+    if (c.slot_stride == 0) FSK_HIP(S->d_part_base.reserve((size_t)O + 8 + (size_t)4 * max_parts));  // (bases, total, target, then 16 bytes a part)
     if (c.k_wait) FSK_HIP(hipStreamWaitEvent(c.stream, c.k_wait, 0));
     if (c.slot_stride != 0) {  // one triangle per slot: a slot's words of a stream are one contiguous piece
         if (c.slot16) FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_sx_consume<true, true>, lds_slot));
         auto k_cs = c.slot16 ? fsk::k_sx_consume<true, true> : fsk::k_sx_consume<true>;
-        FSK_LAUNCH(k_cs, dim3(O, e->sx_rounds_slot, c.nb), dim3(fsk::CS_THREADS), lds_slot, c.stream, (const uint32_t*)S.d_ulist.p,
-                   (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)nullptr, O, target, e->sx_cap_slot,
-                   e->sx_pb, c.K, (const uint32_t*)S.d_ucount.p, c.tpg, c.slot_stride, (const u64*)S.d_sxstat.p, cap_words,
+        FSK_LAUNCH(k_cs, dim3(O, e->sx_rounds_slot, c.nb), dim3(fsk::CS_THREADS), lds_slot, c.stream, (const uint32_t*)S->d_ulist.p,
+                   (const uint32_t*)S->d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)nullptr, O, target, e->sx_cap_slot,
+                   e->sx_pb, c.K, (const uint32_t*)S->d_ucount.p, c.tpg, c.slot_stride, (const u64*)S->d_sxstat.p, cap_words,
                    c.slot16 ? e->sx_ovf_now : (uint32_t*)nullptr, c.pairs, c.desc, Ep, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
     } else {
-        FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, c.stream, (const uint32_t*)S.d_list_off.p, O, target, S.d_part_base.p,
-                   (const u64*)S.d_sxstat.p, cap_words, c.desc, S.d_part_base.p + ((O + 2 + 3) & ~3u), max_parts, desc_parts);
-        FSK_LAUNCH(fsk::k_sx_consume<false>, dim3(max_parts, e->sx_rounds), dim3(fsk::CS_THREADS), lds, c.stream, (const uint32_t*)S.d_ulist.p,
-                   (const uint32_t*)S.d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)S.d_part_base.p, O, target, e->sx_cap,
-                   e->sx_pb, c.K, (const uint32_t*)nullptr, c.tpg, (u64)0, (const u64*)S.d_sxstat.p, cap_words, (uint32_t*)nullptr, c.pairs,
+        FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, c.stream, (const uint32_t*)S->d_list_off.p, O, target, S->d_part_base.p,
+                   (const u64*)S->d_sxstat.p, cap_words, c.desc, S->d_part_base.p + ((O + 2 + 3) & ~3u), max_parts, desc_parts);
+        FSK_LAUNCH(fsk::k_sx_consume<false>, dim3(max_parts, e->sx_rounds), dim3(fsk::CS_THREADS), lds, c.stream, (const uint32_t*)S->d_ulist.p,
+                   (const uint32_t*)S->d_list_off.p, (const uint32_t*)e->d_owner_r0.p, (const uint32_t*)S->d_part_base.p, O, target, e->sx_cap,
+                   e->sx_pb, c.K, (const uint32_t*)nullptr, c.tpg, (u64)0, (const u64*)S->d_sxstat.p, cap_words, (uint32_t*)nullptr, c.pairs,
                    c.desc, Ep, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
         e->st.launches += 1;
     }
@@ -608,7 +608,7 @@ int sx_word_count(const SxBatch& c, u64* words, u64* cap_words) {
         *cap_words = c.guard_cap;
     } else {
         FSK_HIP(hipStreamSynchronize(c.stream));  // the update streams are sized exactly
-        e->u_extra += c.stat_pin[0];
+        e->ld.u_extra += c.stat_pin[0];
         *words = c.stat_pin[1];
         e->sx_saw(*words, c.nrec);
         e->sx_saw_pairs(c.stat_pin[0], c.nrec);
@@ -648,7 +648,7 @@ int sx_update_atomics(const SxBatch& c) {
 template <typename RecT>
 int sx_update_bands(const SxBatch& c) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     sx_seg_write<RecT>(c, sx_owner_bands(c));
     c.stat_pin[0] = c.stat_pin[1] = 0;
     e->st.launches += 3;
@@ -662,8 +662,8 @@ int sx_update_bands(const SxBatch& c) {
         return sx_emit_atomics(c, cap_words);
     }
     if (words > 0 || c.slot_stride != 0) {
-        if (!c.guard_cap && (size_t)words > S.d_ulist.cap)  // (grown with headroom: the batches of a pass differ by a few percent)
-            FSK_HIP(S.d_ulist.reserve((size_t)std::max<u64>(1, words + words / 4)));
+        if (!c.guard_cap && (size_t)words > S->d_ulist.cap)  // (grown with headroom: the batches of a pass differ by a few percent)
+            FSK_HIP(S->d_ulist.reserve((size_t)std::max<u64>(1, words + words / 4)));
         sx_emit(c, sx_owner_bands(c), false, cap_words);
         rc = sx_consume(c, words, cap_words);
         if (rc) return rc;
@@ -671,60 +671,60 @@ int sx_update_bands(const SxBatch& c) {
     } else if (c.k_wait) {
         FSK_HIP(hipStreamWaitEvent(c.stream, c.k_wait, 0));
     }
-    return sx_finish(c, S.d_sxstat.p, cap_words);
+    return sx_finish(c, S->d_sxstat.p, cap_words);
 }
 
 // One pass of the two-level form, its word count known: k_sx_emit by band, the bands' streams cut into tiles (k_sx_parts),
 // split by sub-band (k_sxb_count / _scan / _scatter; the descriptor records likewise) and summed in LDS (k_sxb_consume).
 int sx_blocks_pass(SxBatch& c, const SxPass& P, const SxBands& bands, u64 words) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     hipStream_t stream = c.stream;
     const uint32_t Op = P.n_owners;
-    if ((size_t)words > S.d_ulist.cap) FSK_HIP(S.d_ulist.reserve((size_t)(words + words / 8)));
-    if ((size_t)words > S.d_ulist2.cap) FSK_HIP(S.d_ulist2.reserve((size_t)(words + words / 8)));
+    if ((size_t)words > S->d_ulist.cap) FSK_HIP(S->d_ulist.reserve((size_t)(words + words / 8)));
+    if ((size_t)words > S->d_ulist2.cap) FSK_HIP(S->d_ulist2.reserve((size_t)(words + words / 8)));
     const size_t nsub = (size_t)Op * P.submax;
-    FSK_HIP(S.d_subcnt.reserve(nsub));
-    FSK_HIP(S.d_suboff.reserve(nsub));
-    FSK_HIP(S.d_subcur.reserve(nsub));
-    FSK_HIP(hipMemsetAsync(S.d_subcnt.p, 0, nsub * sizeof(uint32_t), stream));
+    FSK_HIP(S->d_subcnt.reserve(nsub));
+    FSK_HIP(S->d_suboff.reserve(nsub));
+    FSK_HIP(S->d_subcur.reserve(nsub));
+    FSK_HIP(hipMemsetAsync(S->d_subcnt.p, 0, nsub * sizeof(uint32_t), stream));
     if (c.k_wait) { FSK_HIP(hipStreamWaitEvent(stream, c.k_wait, 0)); c.k_wait = nullptr; }
     sx_emit(c, bands, false, ~(u64)0);
     // (persistent launches: two workgroups of 1024 threads a CU walk the tiles of the bands' streams in contiguous chunks)
     const uint32_t n_tiles_max = Op + (uint32_t)((words + fsk::SXB_TILE - 1) / fsk::SXB_TILE);
     const uint32_t n_split = std::min<uint32_t>(n_tiles_max, 2u * (uint32_t)std::max(1, e->n_cu));
-    const uint32_t* const w_off = (const uint32_t*)S.d_list_off.p + (c.desc ? Op : 0u);  // where the bands' word streams start (behind the descriptors')
-    FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, stream, w_off, Op, (uint32_t)fsk::SXB_TILE, S.d_part_base.p,
-               (const u64*)S.d_sxstat.p, ~(u64)0, 0u, (uint32_t*)nullptr, 0xffffffffu, 1u);
-    FSK_LAUNCH(fsk::k_sxb_count, dim3(n_split), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_ulist.p, w_off,
-               (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcnt.p);
-    FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_subcnt.p, w_off, P.submax,
-               S.d_suboff.p, S.d_subcur.p, 0);
+    const uint32_t* const w_off = (const uint32_t*)S->d_list_off.p + (c.desc ? Op : 0u);  // where the bands' word streams start (behind the descriptors')
+    FSK_LAUNCH(fsk::k_sx_parts, dim3(1), dim3(512), 0, stream, w_off, Op, (uint32_t)fsk::SXB_TILE, S->d_part_base.p,
+               (const u64*)S->d_sxstat.p, ~(u64)0, 0u, (uint32_t*)nullptr, 0xffffffffu, 1u);
+    FSK_LAUNCH(fsk::k_sxb_count, dim3(n_split), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S->d_ulist.p, w_off,
+               (const uint32_t*)S->d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S->d_subcnt.p);
+    FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S->d_subcnt.p, w_off, P.submax,
+               S->d_suboff.p, S->d_subcur.p, 0);
     if (c.desc) {  // the descriptor records by (band, sub-band): count, scan, scatter (into the head of the second buffer, as in the first)
-        FSK_HIP(S.d_dsubcnt.reserve(nsub));
-        FSK_HIP(S.d_dsuboff.reserve(nsub));
-        FSK_HIP(S.d_dsubcur.reserve(nsub));
-        FSK_HIP(hipMemsetAsync(S.d_dsubcnt.p, 0, nsub * sizeof(uint32_t), stream));
+        FSK_HIP(S->d_dsubcnt.reserve(nsub));
+        FSK_HIP(S->d_dsuboff.reserve(nsub));
+        FSK_HIP(S->d_dsubcur.reserve(nsub));
+        FSK_HIP(hipMemsetAsync(S->d_dsubcnt.p, 0, nsub * sizeof(uint32_t), stream));
         const dim3 dgrid((uint32_t)std::max(1, 4 * e->n_cu / (int)std::max(1u, Op)) + 1u, Op);
-        FSK_LAUNCH(fsk::k_sxb_drecords<false>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
-                   S.d_dsubcnt.p, (uint4*)nullptr);
-        FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S.d_dsubcnt.p, (const uint32_t*)S.d_list_off.p,
-                   P.submax, S.d_dsuboff.p, S.d_dsubcur.p, 2);
-        FSK_LAUNCH(fsk::k_sxb_drecords<true>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S.d_ulist.p, (const uint32_t*)S.d_list_off.p, P.submax,
-                   S.d_dsubcur.p, reinterpret_cast<uint4*>(S.d_ulist2.p));
+        FSK_LAUNCH(fsk::k_sxb_drecords<false>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S->d_ulist.p, (const uint32_t*)S->d_list_off.p, P.submax,
+                   S->d_dsubcnt.p, (uint4*)nullptr);
+        FSK_LAUNCH(fsk::k_sxb_scan, dim3(Op), dim3(fsk::SXB_THREADS), 0, stream, (const uint32_t*)S->d_dsubcnt.p, (const uint32_t*)S->d_list_off.p,
+                   P.submax, S->d_dsuboff.p, S->d_dsubcur.p, 2);
+        FSK_LAUNCH(fsk::k_sxb_drecords<true>, dgrid, dim3(1024), 0, stream, (const uint32_t*)S->d_ulist.p, (const uint32_t*)S->d_list_off.p, P.submax,
+                   S->d_dsubcur.p, reinterpret_cast<uint4*>(S->d_ulist2.p));
         e->st.launches += 3;
     }
     // (workgroups of 256 threads, three a CU by their LDS)
     FSK_LAUNCH(fsk::k_sxb_scatter<256>, dim3(std::min<uint32_t>(n_tiles_max, 3u * (uint32_t)std::max(1, e->n_cu))), dim3(256), 0, stream,
-               (const uint32_t*)S.d_ulist.p, w_off, (const uint32_t*)S.d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S.d_subcur.p, S.d_ulist2.p);
+               (const uint32_t*)S->d_ulist.p, w_off, (const uint32_t*)S->d_part_base.p, Op, P.pb, P.sub_shift, P.submax, S->d_subcur.p, S->d_ulist2.p);
     // (a block of 2^13 cells and fewer: workgroups of 512 threads, four a CU)
     const size_t lds_sub = sizeof(uint32_t) << P.sub_shift;
     auto k_cs = P.sub_shift <= 13 ? fsk::k_sxb_consume<512> : fsk::k_sxb_consume<1024>;
     FSK_HIP(fsk_hw::allow_dynamic_lds(k_cs, lds_sub));
-    FSK_LAUNCH(k_cs, dim3(P.submax, Op), dim3(P.sub_shift <= 13 ? 512u : 1024u), lds_sub, stream, (const uint32_t*)S.d_ulist2.p,
-               (const uint32_t*)S.d_suboff.p, (const uint32_t*)S.d_subcnt.p, (const uint32_t*)e->d_blk_r0.p, P.pb, P.sub_shift, P.submax, c.K,
-               c.desc ? reinterpret_cast<const uint4*>(S.d_ulist2.p) : (const uint4*)nullptr, (const uint32_t*)S.d_dsuboff.p,
-               (const uint32_t*)S.d_dsubcnt.p, (const void*)S.d_E.p, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
+    FSK_LAUNCH(k_cs, dim3(P.submax, Op), dim3(P.sub_shift <= 13 ? 512u : 1024u), lds_sub, stream, (const uint32_t*)S->d_ulist2.p,
+               (const uint32_t*)S->d_suboff.p, (const uint32_t*)S->d_subcnt.p, (const uint32_t*)e->d_blk_r0.p, P.pb, P.sub_shift, P.submax, c.K,
+               c.desc ? reinterpret_cast<const uint4*>(S->d_ulist2.p) : (const uint4*)nullptr, (const uint32_t*)S->d_dsuboff.p,
+               (const uint32_t*)S->d_dsubcnt.p, (const void*)S->d_E.p, c.packed ? 1 : 0, (const void*)c.colp, c.col16);
     e->st.launches += 6;
     FSK_HIP(hipStreamSynchronize(stream));  // (the next pass overwrites the band table, the entries' unit marks and the streams)
     return FSK_OK;
@@ -736,7 +736,7 @@ int sx_blocks_pass(SxBatch& c, const SxPass& P, const SxBands& bands, u64 words)
 template <typename RecT>
 int sx_update_blocks(SxBatch& c) {
     fsk_engine* e = c.e;
-    SxScratch& S = *c.S;
+    SxScratch* const S = c.S;  // (a pointer: a launch names its arguments by value)
     hipStream_t stream = c.stream;
     const u64 pass_words = e->tune.blocks_pass_words > 0 ? (u64)e->tune.blocks_pass_words : ((u64)1 << 31);
     const u64 total_cells = (u64)e->N * ((u64)e->N + 1) / 2;
@@ -777,16 +777,16 @@ int sx_update_blocks(SxBatch& c) {
             // count matrix and the offsets by this pass's own bands; found by tools/stress_parity.py's blocks cases as a
             // memory fault at N = 6500 with seven bands of 2^9 cells a pass. The previous pass has been waited for.)
             const size_t cols = (size_t)(c.desc ? 2u : 1u) * std::max(Op, c.O);
-            FSK_HIP(S.d_ucount.reserve(cols * c.ntiles));
-            FSK_HIP(S.d_uchunk.reserve(cols * c.nchunks));
-            FSK_HIP(S.d_utot.reserve(cols));
-            FSK_HIP(S.d_list_off.reserve(cols + 1));
-            FSK_HIP(S.d_part_base.reserve((size_t)std::max(Op, c.O) + 2));
+            FSK_HIP(S->d_ucount.reserve(cols * c.ntiles));
+            FSK_HIP(S->d_uchunk.reserve(cols * c.nchunks));
+            FSK_HIP(S->d_utot.reserve(cols));
+            FSK_HIP(S->d_list_off.reserve(cols + 1));
+            FSK_HIP(S->d_part_base.reserve((size_t)std::max(Op, c.O) + 2));
         }
         FSK_HIP(e->d_blk_r0.reserve((size_t)fsk::SX_MAX_OWNERS + 1));
         // (the previous pass has been waited for: nothing reads the table any more)
         FSK_HIP(hipMemcpy(e->d_blk_r0.p, P.r0.data(), P.r0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (!first_pass) FSK_HIP(hipMemsetAsync(S.d_sxstat.p, 0, 3 * sizeof(u64), stream));  // (the first pass: zeroed by the extraction kernel)
+        if (!first_pass) FSK_HIP(hipMemsetAsync(S->d_sxstat.p, 0, 3 * sizeof(u64), stream));  // (the first pass: zeroed by the extraction kernel)
         first_pass = false;
         const uint32_t maxprod = (1u << P.pb) - 1u;
         const SxBands bands{(const uint32_t*)e->d_blk_r0.p, P.t, Op, (uint32_t)ra, (uint32_t)rb, maxprod, maxprod / std::max<uint32_t>(1u, e->maxW),
@@ -803,9 +803,9 @@ int sx_update_blocks(SxBatch& c) {
         }
         if (words >= ((u64)1 << 32))
             return e->fail(FSK_EUNSUPPORTED, "sparse dataflow: row %lld alone emits %llu update words a batch", (long long)ra, (unsigned long long)words);
-        e->u_extra += pairs;
+        e->ld.u_extra += pairs;
         batch_pairs += pairs;
-        e->sx_passes += 1;
+        e->ld.sx_passes += 1;
         if (e->trace())
             fprintf(stderr, "[fsk] sparse blocks: pass rows [%lld, %lld), %u bands of 2^%d cells, %u sub-bands a band, %d product bits, %llu words\n",
                     (long long)ra, (long long)rb, Op, P.t, P.submax, P.pb, (unsigned long long)words);
@@ -836,7 +836,7 @@ int sparse_batch(fsk_engine* e, const int32_t* combos, int nb, u64* K, int64_t r
     e->tic(c.stream);
     RecT* rec[2] = {(RecT*)c.S->d_keys[0].p, (RecT*)c.S->d_keys[1].p};
     int cur = 0;
-    rc = sx_sort<RecT>(e, *c.S, c.stream, rec, c.nfeat, c.tps, (uint32_t)nb, e->sx_sb, c.keybits, &cur);
+    rc = sx_sort<RecT>(e, c.S, c.stream, rec, c.nfeat, c.tps, (uint32_t)nb, e->sx_sb, c.keybits, &cur);
     if (rc) return rc;
     e->toc(&e->st.ms_sort, c.stream);
     e->st.sort_records += c.nrec;
@@ -852,7 +852,7 @@ int sparse_batch(fsk_engine* e, const int32_t* combos, int nb, u64* K, int64_t r
 }
 
 int ensure_featseq(fsk_engine* e) {
-    if (e->featseq_ready) return FSK_OK;
+    if (e->ld.featseq_ready) return FSK_OK;
     // (on the device, from the window offsets that are there already: a host loop over the features and its upload
     // were 0.2 ms of idle stream at the head of every first call)
     FSK_HIP(e->d_featseq.reserve((size_t)std::max<int64_t>(1, e->nfeat)));
@@ -876,7 +876,7 @@ int ensure_featseq(fsk_engine* e) {
                    e->fwin_on ? (const uint32_t*)e->d_fwin.p : (const uint32_t*)nullptr);
     }
     FSK_HIP(hipStreamSynchronize(e->stream));  // (every lane's kernels read both arrays)
-    e->featseq_ready = true;
+    e->ld.featseq_ready = true;
     return FSK_OK;
 }
 
@@ -889,25 +889,15 @@ constexpr int SX_DEFER_COMBOS = 16;  //                combos of such a batch at
 constexpr size_t SX_HEAD_POS = (size_t)SX_DEFER * SX_DEFER_COMBOS * 255;  // (k <= g <= 255)
 constexpr size_t SX_HEAD_STAT = (size_t)2 * SX_DEFER;
 int sx_pinned(fsk_engine* e, size_t tail_pos_bytes, size_t tail_stat_words) {
-    if (!e->h_sx_head_pos) {
-        FSK_HIP(hipHostMalloc((void**)&e->h_sx_head_pos, SX_HEAD_POS));
-        FSK_HIP(hipHostMalloc((void**)&e->h_sx_head_stat, SX_HEAD_STAT * sizeof(u64)));
-        memset(e->h_sx_head_stat, 0, SX_HEAD_STAT * sizeof(u64));
-        FSK_HIP(hipHostMalloc((void**)&e->h_sx_head_flag, SX_DEFER * sizeof(uint32_t)));
-        memset(e->h_sx_head_flag, 0, SX_DEFER * sizeof(uint32_t));
+    if (!e->h_sx_head_flag.p) {
+        FSK_HIP(e->h_sx_head_pos.reserve(SX_HEAD_POS));
+        FSK_HIP(e->h_sx_head_stat.reserve(SX_HEAD_STAT));
+        memset(e->h_sx_head_stat.p, 0, SX_HEAD_STAT * sizeof(u64));
+        FSK_HIP(e->h_sx_head_flag.reserve(SX_DEFER));
+        memset(e->h_sx_head_flag.p, 0, SX_DEFER * sizeof(uint32_t));
     }
-    if (tail_pos_bytes > e->h_sx_pos_cap) {
-        if (e->h_sx_pos) (void)hipHostFree(e->h_sx_pos);
-        e->h_sx_pos = nullptr; e->h_sx_pos_cap = 0;
-        FSK_HIP(hipHostMalloc((void**)&e->h_sx_pos, tail_pos_bytes + tail_pos_bytes / 2));
-        e->h_sx_pos_cap = tail_pos_bytes + tail_pos_bytes / 2;
-    }
-    if (tail_stat_words > e->h_sx_stat_cap) {
-        if (e->h_sx_stat) (void)hipHostFree(e->h_sx_stat);
-        e->h_sx_stat = nullptr; e->h_sx_stat_cap = 0;
-        FSK_HIP(hipHostMalloc((void**)&e->h_sx_stat, (tail_stat_words + tail_stat_words / 2) * sizeof(u64)));
-        e->h_sx_stat_cap = tail_stat_words + tail_stat_words / 2;
-    }
+    FSK_HIP(e->h_sx_pos.reserve(tail_pos_bytes, tail_pos_bytes / 2));
+    FSK_HIP(e->h_sx_stat.reserve(tail_stat_words, tail_stat_words / 2));
     return FSK_OK;
 }
 
@@ -929,23 +919,23 @@ u64 sx_guard_for(fsk_engine* e, int lane, u64 nrec, bool by_slot = false) {
 // the counts of deferred batch `slot` (its kernels have finished): false when it has to be redone
 bool sx_harvest(fsk_engine* e, int slot) {
     if (slot < 0) return true;
-    if (e->h_sx_head_flag && e->h_sx_head_flag[slot]) {  // a sum did not fit its u16 slot triangle (k_sx_consume): u32 from here on
-        e->h_sx_head_flag[slot] = 0u;
+    if (e->h_sx_head_flag.p && e->h_sx_head_flag.p[slot]) {  // a sum did not fit its u16 slot triangle (k_sx_consume): u32 from here on
+        e->h_sx_head_flag.p[slot] = 0u;
         e->slots16_ok = false;
         e->sx_redone += 1;
-        if (e->sx_defer[slot].active) {
-            e->sx_defer[slot].active = false;
-            e->sx_saw(e->h_sx_head_stat[2 * slot + 1], e->sx_defer[slot].nrec);
+        if (e->ld.sx_defer[slot].active) {
+            e->ld.sx_defer[slot].active = false;
+            e->sx_saw(e->h_sx_head_stat.p[2 * slot + 1], e->ld.sx_defer[slot].nrec);
         }
         return false;
     }
-    if (!e->sx_defer[slot].active) return true;
-    e->sx_defer[slot].active = false;
-    const u64 pairs = e->h_sx_head_stat[2 * slot], words = e->h_sx_head_stat[2 * slot + 1];
-    e->sx_saw(words, e->sx_defer[slot].nrec);
-    e->sx_saw_pairs(pairs, e->sx_defer[slot].nrec);
-    if (words > e->sx_defer[slot].cap) { e->sx_redone += 1; return false; }
-    e->u_extra += pairs;
+    if (!e->ld.sx_defer[slot].active) return true;
+    e->ld.sx_defer[slot].active = false;
+    const u64 pairs = e->h_sx_head_stat.p[2 * slot], words = e->h_sx_head_stat.p[2 * slot + 1];
+    e->sx_saw(words, e->ld.sx_defer[slot].nrec);
+    e->sx_saw_pairs(pairs, e->ld.sx_defer[slot].nrec);
+    if (words > e->ld.sx_defer[slot].cap) { e->sx_redone += 1; return false; }
+    e->ld.u_extra += pairs;
     return true;
 }
 
@@ -985,7 +975,7 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
     // variance mode's batches in flight alternate between two lanes of scratch and two streams
     const int lane = sx_lane_of(e, defer);
     e->sx_last_lane = lane;  // (what the caller orders its own passes over the batch's triangles against)
-    if (lane && !e->lane_stream) FSK_HIP(hipStreamCreateWithFlags(&e->lane_stream, hipStreamNonBlocking));
+    if (lane) FSK_HIP(e->lane_stream.create(hipStreamNonBlocking));
     rc = sx_pinned(e, (size_t)n * e->k, (size_t)2 * n);  // (at most one batch per combo)
     if (rc) return rc;
     auto one = [&](int s, int nb, unsigned char* pos_pin, u64* stat_pin, u64 guard, int ln, size_t pos_off = 0, hipEvent_t k_wait = nullptr,
@@ -999,14 +989,14 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
     e->sx_slot16_used = false;
     if (defer >= 0) {
         e->sx_slot16_used = e->sx_slot16 && slot_stride != 0 && e->sx_lists && !e->tune.sparse_global;
-        e->sx_ovf_now = e->h_sx_head_flag + defer;
-        e->h_sx_head_flag[defer] = 0u;
+        e->sx_ovf_now = e->h_sx_head_flag.p + defer;
+        e->h_sx_head_flag.p[defer] = 0u;
         const u64 guard = sx_guard_for(e, lane, (u64)n * nfeat, slot_stride != 0);
-        e->sx_defer[defer].active = guard != 0;
-        e->sx_defer[defer].cap = guard;
-        e->sx_defer[defer].nrec = (u64)n * nfeat;
-        rc = one(0, n, e->h_sx_head_pos + (size_t)defer * SX_DEFER_COMBOS * e->k, e->h_sx_head_stat + 2 * defer, guard, lane);
-        if (rc) e->sx_defer[defer].active = false;
+        e->ld.sx_defer[defer].active = guard != 0;
+        e->ld.sx_defer[defer].cap = guard;
+        e->ld.sx_defer[defer].nrec = (u64)n * nfeat;
+        rc = one(0, n, e->h_sx_head_pos.p + (size_t)defer * SX_DEFER_COMBOS * e->k, e->h_sx_head_stat.p + 2 * defer, guard, lane);
+        if (rc) e->ld.sx_defer[defer].active = false;
         return rc;
     }
     // An exact accumulate of MANY batches runs them in TWO LANES (a scratch set and a stream each, as variance mode's): the
@@ -1030,9 +1020,8 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
     const bool wide = (u64)e->maxW * e->maxW > 0xffffffffull;
     const bool two = (e->tune.sparse_exact_lanes >= 2 || (e->tune.sparse_exact_lanes == 0 && many)) && !e->profile_sync() && !e->sx_exactly() && slot_stride == 0 && nb0 < n && !blocks_form && !wide;
     if (two) {
-        if (!e->lane_stream) FSK_HIP(hipStreamCreateWithFlags(&e->lane_stream, hipStreamNonBlocking));
-        for (auto& ev : e->ev_lane)
-            if (!ev) FSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        FSK_HIP(e->lane_stream.create(hipStreamNonBlocking));
+        for (auto& ev : e->ev_lane) FSK_HIP(ev.create(hipEventDisableTiming));
         FSK_HIP(e->d_pos.reserve((size_t)n * e->k));  // (never grown while a batch in flight reads its piece)
     }
     struct Enq { int s, nb; u64 cap; };  // batches enqueued under a guard (not sized exactly): checked below
@@ -1061,7 +1050,7 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
             if (prev_lane >= 0 && prev_lane != ln) k_wait = e->ev_lane[2 + prev_lane];
             k_done = e->ev_lane[2 + ln];
         }
-        rc = one(s, nb, e->h_sx_pos + (size_t)s * e->k, e->h_sx_stat + 2 * q, cap, ln, two ? (size_t)s * e->k : 0, k_wait, k_done);
+        rc = one(s, nb, e->h_sx_pos.p + (size_t)s * e->k, e->h_sx_stat.p + 2 * q, cap, ln, two ? (size_t)s * e->k : 0, k_wait, k_done);
         if (rc) {
             if (lane1_started) (void)hipStreamSynchronize(e->lane_stream);
             return rc;
@@ -1082,15 +1071,15 @@ int accumulate_sparse(fsk_engine* e, const int32_t* combos, int n, u64* K, int64
     for (size_t i = 0; i < enq.size(); ++i) {
         const Enq& b = enq[i];
         if (!b.cap) continue;
-        const u64 pairs = e->h_sx_stat[2 * i], words = e->h_sx_stat[2 * i + 1];
+        const u64 pairs = e->h_sx_stat.p[2 * i], words = e->h_sx_stat.p[2 * i + 1];
         e->sx_saw(words, (u64)b.nb * nfeat);
         e->sx_saw_pairs(pairs, (u64)b.nb * nfeat);
-        if (words <= b.cap) { e->u_extra += pairs; continue; }
+        if (words <= b.cap) { e->ld.u_extra += pairs; continue; }
         // the batch did not fit and has left K alone: once more, sized exactly
         e->sx_redone += 1;
         const bool was = e->sx_redoing;
         e->sx_redoing = true;
-        rc = one(b.s, b.nb, e->h_sx_pos + (size_t)b.s * e->k, e->h_sx_stat + 2 * i, 0, 0);
+        rc = one(b.s, b.nb, e->h_sx_pos.p + (size_t)b.s * e->k, e->h_sx_stat.p + 2 * i, 0, 0);
         e->sx_redoing = was;
         if (rc) return rc;
     }

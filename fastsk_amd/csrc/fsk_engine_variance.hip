@@ -84,37 +84,30 @@ int run_variance_mode(fsk_engine* e, int T, int chain_first, int chain_step) {
     fsk::SeqGrp* const seq_grp = reinterpret_cast<fsk::SeqGrp*>(e->d_seqblk.p + nblk * slots * sizeof(fsk::SeqBlk));
     FSK_HIP(hipMemsetAsync(e->d_Kf64.p, 0, (size_t)pairs * sizeof(double), e->stream));
     FSK_HIP(hipMemsetAsync(e->d_bsum.p, 0, (nblk * slots + slots) * sizeof(double), e->stream));
-    if (e->h_prod_cap < slots) {
-        if (e->h_prod) (void)hipHostFree(e->h_prod);
-        e->h_prod = nullptr; e->h_prod_cap = 0;
-        FSK_HIP(hipHostMalloc((void**)&e->h_prod, slots * sizeof(double)));
-        e->h_prod_cap = slots;
-    }
-    double* h_avg = e->h_prod;  // pinned
-    if (!e->chain_stream) FSK_HIP(hipStreamCreateWithFlags(&e->chain_stream, hipStreamNonBlocking));
-    hipEvent_t ev_done[MAX_DEPTH], ev_hand[MAX_DEPTH], ev_wf[MAX_DEPTH];  // (ev_wf: one per lane)
-    for (auto& ev : ev_done) FSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (auto& ev : ev_hand) FSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (auto& ev : ev_wf) FSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FSK_HIP(e->h_prod.reserve(slots));
+    double* h_avg = e->h_prod.p;  // pinned
+    FSK_HIP(e->chain_stream.create(hipStreamNonBlocking));
+    Event ev_done[MAX_DEPTH], ev_hand[MAX_DEPTH], ev_wf[MAX_DEPTH];  // (ev_wf: one per lane)
+    for (auto* evs : {ev_done, ev_hand, ev_wf})
+        for (int i = 0; i < MAX_DEPTH; ++i) FSK_HIP(evs[i].create(hipEventDisableTiming));
     // Sparse batches in flight alternate between two lanes (scratch + stream, sx_lane_of): the short kernels of one
     // batch's sort and segmentation run in the gaps of the other's emit / consume / Welford. What orders them: a
     // batch's Welford pass waits for the previous batch's (K_hat is handed from one to the next) through ev_wf.
-    if (!e->profile_sync() && !e->lane_stream) FSK_HIP(hipStreamCreateWithFlags(&e->lane_stream, hipStreamNonBlocking));
+    if (!e->profile_sync()) FSK_HIP(e->lane_stream.create(hipStreamNonBlocking));
     auto sync_all = [e]() {
         (void)hipStreamSynchronize(e->stream);
         if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
         (void)hipStreamSynchronize(e->chain_stream);
     };
-    struct Cleanup {
-        hipEvent_t* a; hipEvent_t* b; hipEvent_t* c; fsk_engine* e;
+    struct Cleanup {  // (declared after the events: it runs before they go)
+        fsk_engine* e;
         bool leave_sums = false;  // (a regular end: only a dropped batch's sequential sums may still run, see below)
         ~Cleanup() {
             (void)hipStreamSynchronize(e->stream);  // nothing of this call may still be in flight
             if (e->lane_stream) (void)hipStreamSynchronize(e->lane_stream);
             if (!leave_sums) (void)hipStreamSynchronize(e->chain_stream);
-            for (int i = 0; i < MAX_DEPTH; ++i) { (void)hipEventDestroy(a[i]); (void)hipEventDestroy(b[i]); (void)hipEventDestroy(c[i]); }
         }
-    } cleanup{ev_done, ev_hand, ev_wf, e};
+    } cleanup{e};
     if (e->lane_stream) {  // lane 1 starts after the uploads and fills enqueued on the engine's stream so far
         FSK_HIP(hipEventRecord(ev_wf[0], e->stream));
         FSK_HIP(hipStreamWaitEvent(e->lane_stream, ev_wf[0], 0));
@@ -264,7 +257,7 @@ int run_variance_mode(fsk_engine* e, int T, int chain_first, int chain_step) {
         FSK_HIP(hipEventRecord(ev_done[B.part], e->chain_stream));
         return FSK_OK;
     };
-    e->stdevs.clear();
+    e->ld.stdevs.clear();
     for (int tid = chain_first; tid < T; tid += chain_step) {
         int cur = 0;  // ring position of the state after the last accepted iteration
         pred_stop = INT32_MAX;
@@ -299,7 +292,7 @@ int run_variance_mode(fsk_engine* e, int T, int chain_first, int chain_step) {
                 // triangles were not written. Everything issued after it started from A's state: drop
                 // it all and run A again, sized exactly.
                 sync_all();
-                for (const Batch& B : q) { e->st.combos_done -= B.n; e->sx_defer[B.part].active = false; }
+                for (const Batch& B : q) { e->st.combos_done -= B.n; e->ld.sx_defer[B.part].active = false; }
                 q.clear();
                 const bool was = e->sx_redoing;
                 e->sx_redoing = true;
@@ -316,7 +309,7 @@ int run_variance_mode(fsk_engine* e, int T, int chain_first, int chain_step) {
                 if (iter == 1) v = 9999999;
                 else v /= iter - 1;
                 const double sd = std::sqrt(v / iter);
-                if (tid == 0) e->stdevs.push_back(sd);
+                if (tid == 0) e->ld.stdevs.push_back(sd);
                 if (e->cfg.delta / sd > 1.96) working = false;
                 if (iter >= 2 && sd > 0.0 && e->cfg.delta > 0.0) {
                     const double at = (double)iter * (1.96 * sd / e->cfg.delta) * (1.96 * sd / e->cfg.delta);
@@ -385,14 +378,15 @@ int fsk_sequential_sum(fsk_engine* e, const double* values, int64_t n, double* o
     const size_t nblk = ((size_t)n + fsk::SQ_BLOCK - 1) / fsk::SQ_BLOCK;
     DevBuf<double> vals, bsum;
     DevBuf<unsigned char> blk;
-    struct Free { DevBuf<double>&a, &b; DevBuf<unsigned char>& c; ~Free() { a.release(); b.release(); c.release(); } } guard{vals, bsum, blk};
     FSK_HIP(vals.reserve((size_t)std::max<int64_t>(1, n)));
     FSK_HIP(bsum.reserve(nblk + 1));
     FSK_HIP(blk.reserve((nblk + 1) * (sizeof(fsk::SeqBlk) + 2 * fsk::SQ_GROUPS * sizeof(fsk::SeqGrp))));
     FSK_HIP(hipMemcpyAsync(vals.p, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice, e->stream));
     FSK_HIP(hipMemsetAsync(bsum.p, 0, (nblk + 1) * sizeof(double), e->stream));
+    const double* vals_p = vals.p;  // (a launch names its arguments by value: pointers, never the owners)
+    double* bsum_p = bsum.p;
     if (n > 0)  // approximate block sums (what k_welford accumulates on the way in variance mode)
-        FSK_LAUNCH(fsk::k_block_sums, dim3((uint32_t)nblk), dim3(256), 0, e->stream, (const double*)vals.p, (u64)n, bsum.p);
+        FSK_LAUNCH(fsk::k_block_sums, dim3((uint32_t)nblk), dim3(256), 0, e->stream, vals_p, (u64)n, bsum_p);
     int rc = enqueue_sequential_sum(e, vals.p, (u64)n, bsum.p, reinterpret_cast<fsk::SeqBlk*>(blk.p),
                                     reinterpret_cast<fsk::SeqGrp*>(blk.p + (nblk + 1) * sizeof(fsk::SeqBlk)), bsum.p + nblk);
     if (rc) return rc;

@@ -133,20 +133,20 @@ struct Collective {
 struct P2PCollective : Collective {
     std::vector<int> dev;
     std::vector<void*> buf;
-    std::vector<hipEvent_t> ready, done;
+    std::vector<Event> ready, done;
     HostBarrier bar;
     int init(const std::vector<int>& devices, std::string& err) {
         kind = FSK_COLL_P2P;
         ranks = (int)devices.size();
         dev = devices;
         buf.assign(dev.size(), nullptr);
-        ready.assign(dev.size(), nullptr);
-        done.assign(dev.size(), nullptr);
+        ready = std::vector<Event>(dev.size());
+        done = std::vector<Event>(dev.size());
         bar.n = ranks;
         for (size_t r = 0; r < dev.size(); ++r) {
             DeviceScope on(dev[r]);
-            if (on.err != hipSuccess || hipEventCreateWithFlags(&ready[r], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&done[r], hipEventDisableTiming) != hipSuccess) {
+            if (on.err != hipSuccess || ready[r].create(hipEventDisableTiming) != hipSuccess ||
+                done[r].create(hipEventDisableTiming) != hipSuccess) {
                 err = "cannot create the events of the peer-to-peer exchange";
                 return FSK_EDEVICE;
             }
@@ -172,8 +172,8 @@ struct P2PCollective : Collective {
     ~P2PCollective() override {
         for (size_t r = 0; r < dev.size(); ++r) {
             DeviceScope on(dev[r]);
-            if (ready[r]) (void)hipEventDestroy(ready[r]);
-            if (done[r]) (void)hipEventDestroy(done[r]);
+            ready[r] = {};
+            done[r] = {};
         }
     }
     template <typename T, int PER>
@@ -447,11 +447,32 @@ struct fsk_group {
     std::vector<fsk_engine*> member;  // member[0] is the handle the caller holds
     std::vector<int> device;
     std::unique_ptr<Collective> coll;
-    std::vector<hipStream_t> xstream;            // the exchange stream of every engine
-    std::vector<hipEvent_t> ev_xdone;            // exchange -> compute
-    std::vector<std::vector<hipEvent_t>> ev_cb;  // [engine][band]: the band's kernels have run on the compute stream (compute -> exchange)
-    std::vector<std::vector<hipEvent_t>> ev_xb;  // [engine][band]: the band's collective has run on the exchange stream
-    std::vector<DevBuf<int32_t>> stage;          // a band of the triangle narrowed to int32
+    struct Exchange {                 // what the group makes on an engine's device
+        Stream xstream;               // the exchange stream
+        Event ev_xdone;               // exchange -> compute
+        std::vector<Event> ev_cb;     // [band]: the band's kernels have run on the compute stream (compute -> exchange)
+        std::vector<Event> ev_xb;     // [band]: the band's collective has run on the exchange stream
+        DevBuf<int32_t> stage;        // a band of the triangle narrowed to int32
+    };
+    std::vector<Exchange> x;          // [engine]; an engine that is not there yet (fsk_create_multi under way) has an empty one
+    // The group goes as fsk_create_multi built it, backwards, whether it was finished or not: nothing of the exchange may still
+    // be in flight; the worker threads; the collective; then every engine with what the group made on its device.
+    ~fsk_group() {
+        for (size_t r = 0; r < member.size(); ++r) {
+            DeviceScope on(device[r]);
+            if (x[r].xstream) (void)hipStreamSynchronize(x[r].xstream);
+            (void)hipStreamSynchronize(member[r]->stream);
+        }
+        pool.shutdown();
+        coll.reset();
+        for (size_t r = 0; r < member.size(); ++r) {
+            {
+                DeviceScope on(device[r]);
+                x[r] = Exchange{};
+            }
+            fsk_detail::one_destroy(member[r]);
+        }
+    }
     WorkerPool pool;
     HostBarrier bar;
     std::atomic<int> failed{0};
@@ -528,7 +549,7 @@ int member_accumulate(fsk_group* g, int r, const std::vector<int32_t>& mine, con
     FSK_ON_DEVICE(e);
     int rc = FSK_OK;
     if (r > 0 && g->others_hold_total) rc = one_reset_counts(e);
-    hipStream_t xs = g->xstream[(size_t)r];
+    hipStream_t xs = g->x[(size_t)r].xstream;
     // After the ranks have agreed to go on, nothing below leaves early: a rank that skipped a collective
     // would leave the others' exchange streams waiting for it for ever. Failures are collected and reported
     // at the end (the exchange then ran on whatever the triangle held); a failed collective poisons the group
@@ -551,8 +572,8 @@ int member_accumulate(fsk_group* g, int r, const std::vector<int32_t>& mine, con
             return rc ? rc : e->fail(FSK_EDEVICE, "another engine of the group failed");
         }
         const u64 c0 = (u64)cell_of(lo), cells = (u64)cell_of(hi) - c0;
-        note(hipEventRecord(g->ev_cb[(size_t)r][b], e->stream), "hipEventRecord");
-        note(hipStreamWaitEvent(xs, g->ev_cb[(size_t)r][b], 0), "hipStreamWaitEvent");
+        note(hipEventRecord(g->x[(size_t)r].ev_cb[b], e->stream), "hipEventRecord");
+        note(hipStreamWaitEvent(xs, g->x[(size_t)r].ev_cb[b], 0), "hipStreamWaitEvent");
 #ifdef FSK_TEST_HOOKS
         {   // test builds only: this engine is late
             const fsk_tuning& t = g->member[0]->tune;
@@ -565,7 +586,7 @@ int member_accumulate(fsk_group* g, int r, const std::vector<int32_t>& mine, con
         std::string cerr;
         int crc;
         if (narrow) {
-            int32_t* st = g->stage[(size_t)r].p;
+            int32_t* st = g->x[(size_t)r].stage.p;
             const uint32_t blocks = (uint32_t)std::min<u64>((cells + 255) / 256, 16384);
             FSK_LAUNCH(fsk::k_narrow_u64_i32, dim3(blocks), dim3(256), 0, xs, (const u64*)(e->d_K + c0), st, cells);
             crc = g->coll->all_reduce(r, st, (size_t)cells, XType::I32, xs, cerr);
@@ -578,12 +599,12 @@ int member_accumulate(fsk_group* g, int r, const std::vector<int32_t>& mine, con
             g->poison(e->err);  // the other engines may already have enqueued their half: release them
         }
         note(hipGetLastError(), "exchange kernels");
-        note(hipEventRecord(g->ev_xb[(size_t)r][b], xs), "hipEventRecord");
+        note(hipEventRecord(g->x[(size_t)r].ev_xb[b], xs), "hipEventRecord");
         if (g->poisoned.load()) return rc ? rc : g->poisoned_rc(e);
     }
     // the engine's next work (finalize, getters, another accumulate) starts after the reduced cells are in place
-    note(hipEventRecord(g->ev_xdone[(size_t)r], xs), "hipEventRecord");
-    note(hipStreamWaitEvent(e->stream, g->ev_xdone[(size_t)r], 0), "hipStreamWaitEvent");
+    note(hipEventRecord(g->x[(size_t)r].ev_xdone, xs), "hipEventRecord");
+    note(hipStreamWaitEvent(e->stream, g->x[(size_t)r].ev_xdone, 0), "hipStreamWaitEvent");
     return rc;
 }
 
@@ -594,7 +615,7 @@ int member_await_exchange(fsk_group* g, int r) {
     fsk_engine* e = g->member[(size_t)r];
     if (g->deadline_ms <= 0 || g->bands_in_flight <= 0) return FSK_OK;
     FSK_ON_DEVICE(e);
-    for (int b = 0; b < g->bands_in_flight && b < (int)g->ev_xb[(size_t)r].size(); ++b) {
+    for (int b = 0; b < g->bands_in_flight && b < (int)g->x[(size_t)r].ev_xb.size(); ++b) {
         // The deadline bounds a band's EXCHANGE, so its clock starts when the band's own kernels have run (the accumulate is
         // asynchronous: a long one — many combos, the sparse dataflow at large g — is not a peer that does not answer).
         // (That wait has a bound of its own, generous — the band's kernels are this engine's own work, minutes at the largest
@@ -602,7 +623,7 @@ int member_await_exchange(fsk_group* g, int r) {
         const auto tc0 = std::chrono::steady_clock::now();
         const long long compute_bound_ms = std::max<long long>(600000, 100ll * g->deadline_ms);
         for (;;) {
-            const hipError_t q = hipEventQuery(g->ev_cb[(size_t)r][(size_t)b]);
+            const hipError_t q = hipEventQuery(g->x[(size_t)r].ev_cb[(size_t)b]);
             if (q == hipSuccess) break;
             (void)hipGetLastError();
             if (q != hipErrorNotReady) {
@@ -621,7 +642,7 @@ int member_await_exchange(fsk_group* g, int r) {
         }
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
-            const hipError_t q = hipEventQuery(g->ev_xb[(size_t)r][(size_t)b]);
+            const hipError_t q = hipEventQuery(g->x[(size_t)r].ev_xb[(size_t)b]);
             if (q == hipSuccess) break;
             if (q != hipErrorNotReady) {
                 (void)hipGetLastError();
@@ -676,7 +697,7 @@ int group_sum_combos(fsk_engine* lead, const int32_t* combos, int32_t n) {
         int rc1 = FSK_OK;
         if (narrow) {
             DeviceScope on(e->cfg.device);
-            if (g->stage[(size_t)r].reserve((size_t)largest) != hipSuccess)
+            if (g->x[(size_t)r].stage.reserve((size_t)largest) != hipSuccess)
                 rc1 = e->fail(FSK_ENOMEM, "cannot allocate %llu bytes of exchange staging", (unsigned long long)(largest * 4));
         }
         if (!g->agree(rc1, g->deadline_ms)) {
@@ -895,22 +916,6 @@ int group_compute(fsk_engine* lead, const int32_t* tokens, const int64_t* offset
 void group_destroy(fsk_engine* lead) {
     fsk_group* g = lead->group;
     lead->group = nullptr;
-    for (int r = 0; r < g->R(); ++r) {  // nothing of the exchange may still be in flight
-        DeviceScope on(g->device[(size_t)r]);
-        if (g->xstream[(size_t)r]) (void)hipStreamSynchronize(g->xstream[(size_t)r]);
-        (void)hipStreamSynchronize(g->member[(size_t)r]->stream);
-    }
-    g->pool.shutdown();
-    g->coll.reset();
-    for (int r = 0; r < g->R(); ++r) {
-        DeviceScope on(g->device[(size_t)r]);
-        g->stage[(size_t)r].release();
-        if (g->ev_xdone[(size_t)r]) (void)hipEventDestroy(g->ev_xdone[(size_t)r]);
-        for (hipEvent_t ev : g->ev_cb[(size_t)r]) if (ev) (void)hipEventDestroy(ev);
-        for (hipEvent_t ev : g->ev_xb[(size_t)r]) if (ev) (void)hipEventDestroy(ev);
-        if (g->xstream[(size_t)r]) (void)hipStreamDestroy(g->xstream[(size_t)r]);
-    }
-    for (fsk_engine* e : g->member) one_destroy(e);
     delete g;
 }
 
@@ -932,18 +937,8 @@ int fsk_create_multi(const fsk_config* cfg, const int32_t* devices, int32_t ndev
     for (int a = 0; a < ndev; ++a)
         for (int b = a + 1; b < ndev; ++b) distinct = distinct && devices[a] != devices[b];
     std::unique_ptr<fsk_group> g(new fsk_group);
-    auto undo = [&](int rc, const std::string& msg) {
-        g->coll.reset();
-        for (size_t r = 0; r < g->member.size(); ++r) {
-            DeviceScope on(g->device[r]);
-            if (r < g->ev_xdone.size() && g->ev_xdone[r]) (void)hipEventDestroy(g->ev_xdone[r]);
-            if (r < g->ev_cb.size())
-                for (hipEvent_t ev : g->ev_cb[r]) if (ev) (void)hipEventDestroy(ev);
-            if (r < g->ev_xb.size())
-                for (hipEvent_t ev : g->ev_xb[r]) if (ev) (void)hipEventDestroy(ev);
-            if (r < g->xstream.size() && g->xstream[r]) (void)hipStreamDestroy(g->xstream[r]);
-        }
-        for (fsk_engine* e : g->member) one_destroy(e);
+    g->x.resize((size_t)ndev);
+    auto undo = [&](int rc, const std::string& msg) {  // (what has been made so far goes with g)
         set_create_error(msg);
         return rc;
     };
@@ -956,20 +951,17 @@ int fsk_create_multi(const fsk_config* cfg, const int32_t* devices, int32_t ndev
         g->member.push_back(e);
         g->device.push_back(devices[r]);
     }
-    g->xstream.assign((size_t)ndev, nullptr);
-    g->ev_xdone.assign((size_t)ndev, nullptr);
-    g->ev_cb.assign((size_t)ndev, std::vector<hipEvent_t>(MAX_BANDS, nullptr));
-    g->ev_xb.assign((size_t)ndev, std::vector<hipEvent_t>(MAX_BANDS, nullptr));
-    g->stage.resize((size_t)ndev);
     for (int r = 0; r < ndev; ++r) {
         DeviceScope on(devices[r]);
-        if (on.err != hipSuccess || hipStreamCreateWithFlags(&g->xstream[(size_t)r], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_xdone[(size_t)r], hipEventDisableTiming) != hipSuccess)
+        fsk_group::Exchange& x = g->x[(size_t)r];
+        if (on.err != hipSuccess || x.xstream.create(hipStreamNonBlocking) != hipSuccess || x.ev_xdone.create(hipEventDisableTiming) != hipSuccess)
             return undo(FSK_EDEVICE, "cannot create the exchange stream / events on device " + std::to_string(devices[r]));
-        for (auto* evs : {&g->ev_cb[(size_t)r], &g->ev_xb[(size_t)r]})
-            for (hipEvent_t& ev : *evs)
-                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+        for (auto* evs : {&x.ev_cb, &x.ev_xb}) {
+            *evs = std::vector<Event>(MAX_BANDS);
+            for (Event& ev : *evs)
+                if (ev.create(hipEventDisableTiming) != hipSuccess)
                     return undo(FSK_EDEVICE, "cannot create the band events on device " + std::to_string(devices[r]));
+        }
     }
     // what fsk_config leaves open comes from engine 0's tuning (FSK_TUNING at its fsk_create): the collective, and the
     // fail-fast bound — fsk_config.deadline_ms, else the tuning's (two minutes by default); negative: no deadline

@@ -15,6 +15,7 @@
 #pragma once
 #include <ucontext.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -279,26 +280,34 @@ namespace emu { inline int& cur_device() { static thread_local int d = 0; return
 static inline hipError_t hipSetDevice(int d) { if (d < 0 || d >= 8) return 1; emu::cur_device() = d; return 0; }
 static inline hipError_t hipGetDevice(int* d) { *d = emu::cur_device(); return 0; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 8; return 0; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
+// what is alive: device allocations, pinned allocations, streams, events (emu_live_counts in rccl_stub.cpp; the lifecycle
+// tests assert that a destroyed engine leaves all four where they were)
+namespace emu {
+inline std::atomic<int64_t> live_device{0}, live_pinned{0}, live_streams{0}, live_events{0};
+}
+static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); if (*p) ++emu::live_device; return *p ? 0 : 2; }
 template <typename T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-static inline hipError_t hipFree(void* p) { free(p); return 0; }
+static inline hipError_t hipFree(void* p) { if (p) --emu::live_device; free(p); return 0; }
 static inline void __threadfence() {}
 static inline void __threadfence_system() {}
-static inline hipError_t hipHostMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
-static inline hipError_t hipHostFree(void* p) { free(p); return 0; }
+static inline hipError_t hipHostMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); if (*p) ++emu::live_pinned; return *p ? 0 : 2; }
+static inline hipError_t hipHostFree(void* p) { if (p) --emu::live_pinned; free(p); return 0; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return 0; }
-static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return 0; }
-static inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
-enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
+// (create / destroy have external linkage: the engine's Stream and Event types name them as template arguments)
+// (a created stream is a token of its own, never null: "non-null means created" holds here as on the device; the null
+// stream is the default one. Launches and copies run to completion whatever stream they name.)
+enum { hipStreamDefault = 0, hipStreamNonBlocking = 1, hipEventDefault = 0, hipEventDisableTiming = 2 };
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new char; ++emu::live_streams; return 0; }
+static inline hipError_t hipStreamCreate(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamDefault); }
+inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) --emu::live_streams; delete (char*)s; return 0; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 static inline hipError_t hipDeviceSynchronize() { return 0; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emuEvent; return 0; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return 0; }
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new emuEvent; return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new emuEvent; ++emu::live_events; return 0; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDefault); }
+inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) --emu::live_events; delete e; return 0; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return 0; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }

@@ -41,4 +41,6 @@ void emu_rccl_set_fault(int kind, int rank, int nth, int rendezvous_ms);
 // [11] completed collectives, [12] ranks of the last communicator
 void emu_rccl_stats(int64_t out[16]);
 void emu_rccl_reset(void);
+// what hip_emu.h has handed out and not taken back: [0] device allocations, [1] pinned allocations, [2] streams, [3] events
+void emu_live_counts(int64_t out[4]);
 }

@@ -231,4 +231,11 @@ void emu_rccl_reset(void) {
     g_rendezvous_ms = 0;
 }
 
+void emu_live_counts(int64_t out[4]) {
+    out[0] = emu::live_device.load();
+    out[1] = emu::live_pinned.load();
+    out[2] = emu::live_streams.load();
+    out[3] = emu::live_events.load();
+}
+
 }  // extern "C"

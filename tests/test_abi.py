@@ -54,7 +54,7 @@ def test_product_library_holds_no_test_infrastructure(product_lib):
     in tests/ only: the product library neither defines nor needs their symbols, and the package never names tests/."""
     import subprocess
     syms = subprocess.run(["nm", "-D", product_lib.path], capture_output=True, text=True, check=True).stdout
-    for name in ("emu_rccl_set_fault", "emu_rccl_stats", "ncclAllReduce", "ncclCommInitAll", "ncclCommAbort"):
+    for name in ("emu_rccl_set_fault", "emu_rccl_stats", "emu_live_counts", "ncclAllReduce", "ncclCommInitAll", "ncclCommAbort"):
         assert not re.search(r"\b%s\b" % name, syms), name      # (RCCL itself is bound with dlopen: not even an undefined reference)
     blob = open(product_lib.path, "rb").read()
     assert b"fault_kind" not in blob and b"rccl_stub" not in blob
