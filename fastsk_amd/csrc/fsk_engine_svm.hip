@@ -49,59 +49,50 @@ SvmRecords svm_records(unsigned char* base, uint32_t n_wg) {
 static_assert(sizeof(fsk::SvmRecB) <= 256 && sizeof(fsk::SvmRecA) <= 256 && sizeof(fsk::SvmCandI) % 8 == 0 && sizeof(fsk::SvmCandJ) % 8 == 0,
               "record layout");
 
-// one workgroup, alpha / G / y in LDS: launches of up to `chunk` iterations until the status record says done
-template <typename SrcT>
-int solve_wg(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
-             fsk::SvmRecB* status, int64_t* launches) {
-    double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p;  // (plain pointers: a launch takes its arguments by value)
-    const signed char* y = e->svm.d_y.p;
-    fsk::SvmRecB* rb = R.rb;
-    const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (n + 63u) & ~63u);
-    const size_t lds = fsk::svm_wg_lds(n, nt);
-    if (lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svm_wg needs %zu bytes of LDS for %u rows", lds, n);
-    FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svm_wg<SrcT>, lds));
+// THE polling loop of every solve: `enqueue` puts one chunk of iterations on the stream, the n_rec status records (one of a
+// single solve, P of a batch) come back in one copy, until every one says done. Launches that follow a problem's end inside a
+// chunk return at once.
+template <typename Enqueue>
+int svm_poll(fsk_engine* e, const fsk::SvmRecB* rb, fsk::SvmRecB* status, uint32_t n_rec, Enqueue enqueue) {
     for (;;) {
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg<SrcT>), dim3(1), dim3(nt), lds, e->stream, K, diag, n, Cp, Cn, eps, (long long)max_iter, chunk,
-                   alpha, G, y, rb);
-        ++*launches;
-        FSK_HIP(hipMemcpyAsync(status, rb, sizeof *status, hipMemcpyDeviceToHost, e->stream));
+        enqueue();
+        FSK_HIP(hipMemcpyAsync(status, rb, (size_t)n_rec * sizeof(fsk::SvmRecB), hipMemcpyDeviceToHost, e->stream));
         FSK_HIP(hipStreamSynchronize(e->stream));
         FSK_HIP(hipGetLastError());
-        if (status->done) return FSK_OK;
+        bool all = true;
+        for (uint32_t p = 0; p < n_rec; ++p) all = all && status[p].done;
+        if (all) return FSK_OK;
     }
 }
 
-// two launches an iteration: `chunk` (A, B) pairs between two reads of the status record
-template <typename SrcT>
-int solve_two_launch(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, uint32_t chunk, const SvmRecords& R,
-                     uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
-    double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p, *krow = e->svm.d_krow.p;  // (plain pointers: a launch takes its arguments by value)
-    const signed char* y = e->svm.d_y.p;
-    fsk::SvmRecB* rb = R.rb;
-    fsk::SvmRecA* ra = R.ra;
-    fsk::SvmCandI* ci = R.ci;
-    fsk::SvmCandJ* cj = R.cj;
-    for (;;) {
-        for (uint32_t c = 0; c < chunk; ++c) {
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, alpha, G, y,
-                       (const double*)krow, (const fsk::SvmRecB*)rb, ra, ci, (const fsk::SvmCandJ*)cj, n_wg);
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, eps,
-                       (long long)max_iter, (const double*)alpha, (const double*)G, y, krow, rb, (const fsk::SvmRecA*)ra,
-                       (const fsk::SvmCandI*)ci, cj, n_wg);
-            *launches += 2;
-        }
-        FSK_HIP(hipMemcpyAsync(status, rb, sizeof *status, hipMemcpyDeviceToHost, e->stream));
-        FSK_HIP(hipStreamSynchronize(e->stream));
-        FSK_HIP(hipGetLastError());
-        if (status->done) return FSK_OK;
-    }
-}
-
+// One problem. Form 1: one workgroup, alpha / G / y in LDS, a launch of up to `chunk` iterations a chunk; form 2: two launches
+// an iteration, `chunk` (A, B) pairs a chunk.
 template <typename SrcT>
 int solve(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps, int64_t max_iter, int form, uint32_t chunk, const SvmRecords& R,
           uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
-    return form == 1 ? solve_wg<SrcT>(e, K, diag, n, Cp, Cn, eps, max_iter, chunk, R, status, launches)
-                     : solve_two_launch<SrcT>(e, K, diag, n, Cp, Cn, eps, max_iter, chunk, R, n_wg, status, launches);
+    double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p, *krow = e->svm.d_krow.p;  // (plain pointers: a launch takes its arguments by value)
+    const signed char* y = e->svm.d_y.p;
+    if (form == 1) {
+        const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (n + 63u) & ~63u);
+        const size_t lds = fsk::svm_wg_lds(n, nt);
+        if (lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svm_wg needs %zu bytes of LDS for %u rows", lds, n);
+        FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svm_wg<SrcT>, lds));
+        return svm_poll(e, R.rb, status, 1, [=] {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg<SrcT>), dim3(1), dim3(nt), lds, e->stream, K, diag, n, Cp, Cn, eps, (long long)max_iter, chunk,
+                       alpha, G, y, R.rb);
+            ++*launches;
+        });
+    }
+    return svm_poll(e, R.rb, status, 1, [=] {
+        for (uint32_t c = 0; c < chunk; ++c) {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, alpha, G, y,
+                       (const double*)krow, (const fsk::SvmRecB*)R.rb, R.ra, R.ci, (const fsk::SvmCandJ*)R.cj, n_wg);
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, Cp, Cn, eps,
+                       (long long)max_iter, (const double*)alpha, (const double*)G, y, krow, R.rb, (const fsk::SvmRecA*)R.ra,
+                       (const fsk::SvmCandI*)R.ci, R.cj, n_wg);
+            *launches += 2;
+        }
+    });
 }
 
 // rho and the objective as LIBSVM's calculate_rho / calculate_objective_value, in element order, the box of an element by its
@@ -151,6 +142,26 @@ int svm_source(fsk_engine* e, bool build, SvmSource* s) {
     }
     return FSK_OK;
 }
+// THE place that turns the source into a type: f(K) with K the u64 or the fp64 triangle; f's kernels are those of SrcOf<K>
+template <typename F>
+int svm_on_source(const SvmSource& s, F f) { return s.f64 ? f(s.Kf) : f(s.Ku); }
+template <typename P>
+using SrcOf = std::remove_const_t<std::remove_pointer_t<P>>;
+
+// What fsk_svm_train and cv_run check alike: a finalized result, labels (null_text: what to say where the caller's arrays are
+// not all there), one a training sequence, each -1 or +1 (n_pos: how many are +1), and eps.
+int svm_check_problem(fsk_engine* e, const int32_t* labels, const char* null_text, int64_t n, double eps, int64_t* n_pos) {
+    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
+    if (!labels) return e->fail(FSK_EINVAL, "%s", null_text);
+    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
+    *n_pos = 0;
+    for (int64_t t = 0; t < n; ++t) {
+        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
+        *n_pos += labels[t] > 0;
+    }
+    return FSK_OK;
+}
 
 int model_ready(fsk_engine* e) {
     if (!e->finalized || !e->svm.valid) return e->fail(FSK_ESTATE, "no model: call fsk_svm_train on a finalized result first");
@@ -162,14 +173,12 @@ int launch_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dst) {
     const uint32_t blocks = (uint32_t)((r1 - r0 + 3) / 4), n_train = (uint32_t)e->n_train, a = (uint32_t)r0, b = (uint32_t)r1;
     SvmSource src;
     { int rc = svm_source(e, false, &src); if (rc) return rc; }
-    const double *diag = src.diag, *coef = e->svm.d_coef.p, *Kf = src.Kf;
-    const u64* Ku = src.Ku;
+    const double *diag = src.diag, *coef = e->svm.d_coef.p;
     const double rho = e->svm.rho;
-    if (src.f64)
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision<double>), dim3(blocks), dim3(256), 0, e->stream, Kf, diag, coef, n_train, a, b, rho, dst);
-    else
-        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision<u64>), dim3(blocks), dim3(256), 0, e->stream, Ku, diag, coef, n_train, a, b, rho, dst);
-    return FSK_OK;
+    return svm_on_source(src, [=](auto* K) -> int {
+        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision<SrcOf<decltype(K)>>), dim3(blocks), dim3(256), 0, e->stream, K, diag, coef, n_train, a, b, rho, dst);
+        return FSK_OK;
+    });
 }
 
 int decision_args(fsk_engine* e, int64_t r0, int64_t r1, const double* out) {
@@ -203,39 +212,32 @@ size_t svm_batch_record_bytes(uint32_t P, uint32_t total_wg) {
 }
 static_assert(sizeof(fsk::SvmRecB) % 8 == 0 && sizeof(fsk::SvmRecA) % 8 == 0 && sizeof(fsk::SvmProb) == 40, "batch record layout");
 
-// enqueue `chunk` iterations for every problem, read the P status records in one copy, until every problem is done
+// the batch in the two forms of solve(): a chunk is `chunk` iterations of every problem that is not done
 template <typename SrcT>
 int solve_batch(fsk_engine* e, const SrcT* K, const double* diag, const SvmBatch& B, double eps, int64_t max_iter, int form, uint32_t chunk,
-                std::vector<fsk::SvmRecB>& status, int64_t* launches) {
-    const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (B.max_n + 63u) & ~63u);
-    const size_t lds = fsk::svm_wg_lds(B.max_n, nt);
+                fsk::SvmRecB* status, int64_t* launches) {
     if (form == 1) {
+        const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (B.max_n + 63u) & ~63u);
+        const size_t lds = fsk::svm_wg_lds(B.max_n, nt);
         if (lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svm_wg_batch needs %zu bytes of LDS for %u rows", lds, B.max_n);
         FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svm_wg_batch<SrcT>, lds));
-    }
-    for (;;) {
-        if (form == 1) {
+        return svm_poll(e, B.rb, status, B.P, [=] {
             FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_wg_batch<SrcT>), dim3(B.P), dim3(nt), lds, e->stream, K, diag, B.probs, B.idx, B.y, eps,
                        (long long)max_iter, chunk, B.alpha, B.G, B.rb);
             ++*launches;
-        } else {
-            for (uint32_t c = 0; c < chunk; ++c) {
-                FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
-                           B.probs, B.idx, B.y, B.alpha, B.G, (const double*)B.krow, (const fsk::SvmRecB*)B.rb, B.ra, B.ci,
-                           (const fsk::SvmCandJ*)B.cj);
-                FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
-                           B.probs, B.idx, B.y, eps, (long long)max_iter, (const double*)B.alpha, (const double*)B.G, B.krow, B.rb,
-                           (const fsk::SvmRecA*)B.ra, (const fsk::SvmCandI*)B.ci, B.cj);
-                *launches += 2;
-            }
-        }
-        FSK_HIP(hipMemcpyAsync(status.data(), B.rb, (size_t)B.P * sizeof(fsk::SvmRecB), hipMemcpyDeviceToHost, e->stream));
-        FSK_HIP(hipStreamSynchronize(e->stream));
-        FSK_HIP(hipGetLastError());
-        bool all = true;
-        for (uint32_t p = 0; p < B.P; ++p) all = all && status[p].done;
-        if (all) return FSK_OK;
+        });
     }
+    return svm_poll(e, B.rb, status, B.P, [=] {
+        for (uint32_t c = 0; c < chunk; ++c) {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_i_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                       B.probs, B.idx, B.y, B.alpha, B.G, (const double*)B.krow, (const fsk::SvmRecB*)B.rb, B.ra, B.ci,
+                       (const fsk::SvmCandJ*)B.cj);
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_select_j_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                       B.probs, B.idx, B.y, eps, (long long)max_iter, (const double*)B.alpha, (const double*)B.G, B.krow, B.rb,
+                       (const fsk::SvmRecA*)B.ra, (const fsk::SvmCandI*)B.ci, B.cj);
+            *launches += 2;
+        }
+    });
 }
 
 // (#{pos > neg} + 0.5 #{pos == neg}) / (n_pos n_neg) and the share of rows on the right side of zero
@@ -272,25 +274,20 @@ int cv_ready(fsk_engine* e) {
 int cv_run(fsk_engine* e, SvmCvState& S, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
            double eps, int64_t max_iter) {
     const double t0 = now_ms();
-    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
     if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
-    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);
-    if (!labels || !fold || !Cs) return e->fail(FSK_EINVAL, "null labels, fold or Cs");
-    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
+    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);  // (before the arrays: an empty Cs may be null)
+    int64_t n_pos = 0;
+    { int rcc = svm_check_problem(e, fold && Cs ? labels : nullptr, "null labels, fold or Cs", n, eps, &n_pos); if (rcc) return rcc; }
     if ((int64_t)n_C * n_folds > FSK_SVM_CV_MAX_PROBLEMS)
         return e->fail(FSK_EINVAL, "%d folds x %d values of C are more than %d problems", n_folds, n_C, FSK_SVM_CV_MAX_PROBLEMS);
     for (int32_t c = 0; c < n_C; ++c)
         if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
-    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
     const uint32_t F = (uint32_t)n_folds, nC = (uint32_t)n_C, P = F * nC, nn = (uint32_t)n;
     std::vector<int64_t> rows(F, 0), rows_pos(F, 0);
-    int64_t n_pos = 0;
     for (int64_t t = 0; t < n; ++t) {
-        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
         if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
         ++rows[fold[t]];
         rows_pos[fold[t]] += labels[t] > 0;
-        n_pos += labels[t] > 0;
     }
     for (uint32_t f = 0; f < F; ++f) {
         if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
@@ -367,8 +364,7 @@ int cv_run(fsk_engine* e, SvmCvState& S, const int32_t* labels, int64_t n, const
 
     std::vector<fsk::SvmRecB> status(P);
     int64_t launches = 0;
-    const int rc = src.f64 ? solve_batch<double>(e, src.Kf, src.diag, B, eps, max_iter, form, chunk, status, &launches)
-                           : solve_batch<u64>(e, src.Ku, src.diag, B, eps, max_iter, form, chunk, status, &launches);
+    const int rc = svm_on_source(src, [&](auto* K) { return solve_batch(e, K, src.diag, B, eps, max_iter, form, chunk, status.data(), &launches); });
     if (rc) return rc;
     S.alpha.resize(total);
     FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -400,14 +396,13 @@ int cv_run(fsk_engine* e, SvmCvState& S, const int32_t* labels, int64_t n, const
     FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
     {
         const dim3 grid((nn + 3) / 4, nC);
-        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p, *Kf = src.Kf;
+        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p;
         const int32_t* df = S.d_fold.p;
-        const u64* Ku = src.Ku;
         double* out = S.d_oof.p;
-        if (src.f64)
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<double>), grid, dim3(256), 0, e->stream, Kf, diag, dc, dr, df, F, nn, out);
-        else
-            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<u64>), grid, dim3(256), 0, e->stream, Ku, diag, dc, dr, df, F, nn, out);
+        svm_on_source(src, [=](auto* K) -> int {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<SrcOf<decltype(K)>>), grid, dim3(256), 0, e->stream, K, diag, dc, dr, df, F, nn, out);
+            return FSK_OK;
+        });
     }
     S.oof.resize((size_t)nC * nn);
     FSK_HIP(hipMemcpyAsync(S.oof.data(), S.d_oof.p, S.oof.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -519,16 +514,9 @@ extern "C" {
 int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, double eps, int64_t max_iter) {
     if (!e) return FSK_EINVAL;
     const double t0 = now_ms();
-    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
-    if (!labels) return e->fail(FSK_EINVAL, "null labels");
-    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
-    if (!(C > 0.0) || !std::isfinite(C)) return e->fail(FSK_EINVAL, "C must be a positive finite number");
-    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
     int64_t n_pos = 0;
-    for (int64_t t = 0; t < n; ++t) {
-        if (labels[t] != 1 && labels[t] != -1) return e->fail(FSK_EINVAL, "label %lld is %d: labels must be -1 or +1", (long long)t, labels[t]);
-        n_pos += labels[t] > 0;
-    }
+    { int rcc = svm_check_problem(e, labels, "null labels", n, eps, &n_pos); if (rcc) return rcc; }
+    if (!(C > 0.0) || !std::isfinite(C)) return e->fail(FSK_EINVAL, "C must be a positive finite number");
     if (n_pos == 0 || n_pos == n) return e->fail(FSK_EINVAL, "only one class is present");
     if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
     FSK_ON_DEVICE(e);
@@ -564,8 +552,7 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
 
     fsk::SvmRecB status{};
     int64_t launches = 0;
-    const int rc = src.f64 ? solve<double>(e, src.Kf, src.diag, nn, Cp, Cn, eps, max_iter, form, chunk, R, n_wg, &status, &launches)
-                           : solve<u64>(e, src.Ku, src.diag, nn, Cp, Cn, eps, max_iter, form, chunk, R, n_wg, &status, &launches);
+    const int rc = svm_on_source(src, [&](auto* K) { return solve(e, K, src.diag, nn, Cp, Cn, eps, max_iter, form, chunk, R, n_wg, &status, &launches); });
     if (rc) return rc;
     FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, e->stream));

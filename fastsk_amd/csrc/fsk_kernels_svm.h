@@ -181,15 +181,30 @@ __host__ __device__ inline size_t svm_wg_lds(uint32_t n, uint32_t nt) {
 }
 
 // =============================================================================================
+// ROW MAPS. A problem is n elements; rows(e) is the row of the triangle that element e stands for. The single solve is the
+// whole training set (element e is row e), a problem of a batch is a strictly ascending list of training rows (fsk_svm_cv),
+// so the lowest element is the lowest row and every tie falls as in the single solve on the sub-matrix. The iterations below
+// are written once over the map: each kernel is an instantiation with one of the two, there is no run-time "batch or not".
+// KEPT: whether the workgroup form keeps the rows it read in step 2 for step 4 (a list's are loads; e is e again for nothing).
+struct SvmRowsAll {
+    static constexpr bool KEPT = false;
+    __device__ __forceinline__ uint32_t operator()(uint32_t e) const { return e; }
+};
+struct SvmRowsList {
+    static constexpr bool KEPT = true;
+    const uint32_t* idx;
+    __device__ __forceinline__ uint32_t operator()(uint32_t e) const { return idx[e]; }
+};
+
+// =============================================================================================
 // ONE WORKGROUP (n <= svm_wg_max <= 8192): alpha, G and y live in LDS (17 bytes an element: 139,264 bytes at 8192, beside
 // 17 KB of reduction scratch — one workgroup may take all 160 KiB of a CU), up to `chunk` iterations a launch. The state is
 // loaded from and written back to device memory around them, so no launch runs unbounded. Element e belongs to thread
 // e mod blockDim.x, which alone writes its alpha and G. Seven barriers an iteration (two a reduction, one before the writes).
-template <typename SrcT>
-__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
-                                                           long long max_iter, uint32_t chunk, double* alpha, double* G,
-                                                           const signed char* y, SvmRecB* rec) {
-    FSK_DYN_SHARED(unsigned char, smem);
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svm_wg_iterations(unsigned char* smem, const SrcT* K, const double* diag, const Rows rows, uint32_t n, double Cp,
+                                                  double Cn, double eps, long long max_iter, uint32_t chunk, double* alpha, double* G,
+                                                  const signed char* y, SvmRecB* rec) {
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     const size_t n8 = ((size_t)n + 7) & ~(size_t)7;
     double* sA = reinterpret_cast<double*>(smem);
@@ -225,17 +240,21 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
         gmax = vmax; gmin = vmin;
         if (__dsub_rn(gmax, gmin) <= eps) { done = 1; converged = 1; break; }
         if (iter >= max_iter) { done = 1; break; }
-        const uint32_t i = (uint32_t)imax;
-        // ---- 2. j (row i stays in registers for step 4)
+        const uint32_t i = (uint32_t)imax, ri = rows(i);
+        // ---- 2. j (row i, and the elements' rows where they are kept, stay in registers for step 4)
         double kit[SVM_WG_ITEMS];
+        uint32_t row[SVM_WG_ITEMS];
         double obj = svm_inf();
         int j = SVM_NONE;
 #pragma unroll
         for (int q = 0; q < SVM_WG_ITEMS; ++q) {
             const uint32_t e = tid + (uint32_t)q * nt;
             kit[q] = 0.0;
+            if constexpr (Rows::KEPT) row[q] = 0;
             if (e < n) {
-                kit[q] = svm_cell(K, diag, i, e);
+                const uint32_t r = rows(e);
+                if constexpr (Rows::KEPT) row[q] = r;
+                kit[q] = svm_cell(K, diag, ri, r);
                 const int ye = sY[e];
                 double o;
                 if (svm_in_low(ye, sA[e], Cn) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
@@ -246,10 +265,11 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
         // a NaN objective wins no comparison): the solve ends, not converged, the step not taken
         if (j == SVM_NONE) { done = 1; break; }
         // ---- 3. the step, by every thread alike
+        const uint32_t rj = rows((uint32_t)j);
         const int yi = sY[i], yj = sY[j];
         const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
         double ai = ai0, aj = aj0;
-        svm_step(yi, yj, svm_cell(K, diag, i, (uint32_t)j), Gi, Gj, Cp, Cn, &ai, &aj);
+        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
         __syncthreads();  // (everybody has read alpha and G of i and j)
         // ---- 4. G, alpha
@@ -257,7 +277,9 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
         for (int q = 0; q < SVM_WG_ITEMS; ++q) {
             const uint32_t e = tid + (uint32_t)q * nt;
             if (e < n) {
-                sG[e] = svm_new_G(sG[e], sY[e], yi, yj, kit[q], svm_cell(K, diag, (uint32_t)j, e), dai, daj);
+                uint32_t r = e;
+                if constexpr (Rows::KEPT) r = row[q];
+                sG[e] = svm_new_G(sG[e], sY[e], yi, yj, kit[q], svm_cell(K, diag, rj, r), dai, daj);
                 if (e == i) sA[e] = ai;
                 if (e == (uint32_t)j) sA[e] = aj;
             }
@@ -272,6 +294,14 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const 
     }
 }
 
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
+                                                           long long max_iter, uint32_t chunk, double* alpha, double* G,
+                                                           const signed char* y, SvmRecB* rec) {
+    FSK_DYN_SHARED(unsigned char, smem);
+    svm_wg_iterations(smem, K, diag, SvmRowsAll{}, n, Cp, Cn, eps, max_iter, chunk, alpha, G, y, rec);
+}
+
 // =============================================================================================
 // TWO LAUNCHES AN ITERATION (any n): 256 threads a workgroup, one element a thread, no barrier across workgroups — what one
 // launch's workgroups tell each other travels through device memory to the NEXT launch, where every workgroup reduces the
@@ -280,11 +310,10 @@ constexpr int SVM_THREADS = 256;
 
 // LAUNCH A: finish the pending step — j from the workgroups' candidates, the scalar step, this workgroup's slice of G, alpha
 // of i and j by the workgroups that hold them — then this workgroup's share of the next step 1.
-template <typename SrcT>
-__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double* alpha,
-                                                              double* G, const signed char* y, const double* krow,
-                                                              const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i,
-                                                              const SvmCandJ* cand_j, uint32_t n_wg) {
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svm_select_i(const SrcT* K, const double* diag, const Rows rows, uint32_t n, double Cp, double Cn, double* alpha,
+                                             double* G, const signed char* y, const double* krow, const SvmRecB* rb, SvmRecA* ra,
+                                             SvmCandI* cand_i, const SvmCandJ* cand_j, uint32_t n_wg) {
     __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
     __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
     const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
@@ -316,7 +345,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, con
         svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, Cp, Cn, &ai, &aj);
         const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
         if (mine) {
-            g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, (uint32_t)j, t), dai, daj);
+            g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, rows((uint32_t)j), rows(t)), dai, daj);
             G[t] = g;
             if (t == (uint32_t)i) { a = ai; alpha[t] = a; }
             if (t == (uint32_t)j) { a = aj; alpha[t] = a; }
@@ -338,11 +367,10 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, con
 
 // LAUNCH B: i, Gmax and Gmin from the workgroups' candidates; the stop tests; row i (kept in krow for launch A), this
 // workgroup's candidate for j.
-template <typename SrcT>
-__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
-                                                              long long max_iter, const double* alpha, const double* G,
-                                                              const signed char* y, double* krow, SvmRecB* rb, const SvmRecA* ra,
-                                                              const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svm_select_j(const SrcT* K, const double* diag, const Rows rows, uint32_t n, double Cp, double Cn, double eps,
+                                             long long max_iter, const double* alpha, const double* G, const signed char* y, double* krow,
+                                             SvmRecB* rb, const SvmRecA* ra, const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
     __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
     __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
     const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
@@ -375,7 +403,7 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, con
     double obj = svm_inf(), kit = 0.0, a = 0.0, g = 0.0;
     int j = SVM_NONE, yt = 1;
     if (t < n) {
-        kit = svm_cell(K, diag, i, t);
+        kit = svm_cell(K, diag, rows(i), rows(t));
         krow[t] = kit;
         yt = (int)y[t]; a = alpha[t]; g = G[t];
         double o;
@@ -394,6 +422,22 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, con
         rb->ai = alpha[i]; rb->Gi = G[i]; rb->i = (int)i; rb->yi = (int)y[i];
         rb->done = 0; rb->converged = 0; rb->pending = 1;
     }
+}
+
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double* alpha,
+                                                              double* G, const signed char* y, const double* krow,
+                                                              const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i,
+                                                              const SvmCandJ* cand_j, uint32_t n_wg) {
+    svm_select_i(K, diag, SvmRowsAll{}, n, Cp, Cn, alpha, G, y, krow, rb, ra, cand_i, cand_j, n_wg);
+}
+
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j(const SrcT* K, const double* diag, uint32_t n, double Cp, double Cn, double eps,
+                                                              long long max_iter, const double* alpha, const double* G,
+                                                              const signed char* y, double* krow, SvmRecB* rb, const SvmRecA* ra,
+                                                              const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
+    svm_select_j(K, diag, SvmRowsAll{}, n, Cp, Cn, eps, max_iter, alpha, G, y, krow, rb, ra, cand_i, cand_j, n_wg);
 }
 
 // =============================================================================================
@@ -419,11 +463,11 @@ __global__ __launch_bounds__(256) void k_svm_decision(const SrcT* K, const doubl
 }
 
 // =============================================================================================
-// A BATCH OF PROBLEMS ON ONE TRIANGLE (fsk_svm_cv: folds x values of C). Problem p is n of the training rows — element e is
-// row idx[e], the list strictly ascending, so the lowest element is the lowest row and every tie falls as in the single
-// solve on the sub-matrix — with labels and Cp, Cn of its own. The kernels below are the three above with the problem as one
-// more grid dimension and every cell read through idx; the arithmetic of an iteration is the same to the operation. They
-// are kernels of their own, not a mode of the single-problem ones: those keep their code and their launches.
+// A BATCH OF PROBLEMS ON ONE TRIANGLE (fsk_svm_cv: folds x values of C). Problem p is n of the training rows, a strictly
+// ascending list (SvmRowsList), with labels and Cp, Cn of its own. Its kernels are the iterations above instantiated over
+// that list, with the problem as one more grid dimension: what is written here is what is theirs alone — which problem a
+// workgroup serves, the workgroups that have nothing to do, the problem's slices of the batch's arrays. The single-problem
+// kernels keep their names, arguments and launches; the two sets share source, not a run-time mode.
 struct SvmProb {
     double Cp, Cn;               // the boxes of its rows of label +1 / -1
     unsigned long long idx_off;  // idx and y of the problem start here (the problems of one fold share them)
@@ -444,92 +488,8 @@ __global__ __launch_bounds__(SVM_WG_THREADS) void k_svm_wg_batch(const SrcT* K, 
     SvmRecB* rec = recs + blockIdx.x;
     if (rec->done) return;  // (the whole workgroup: nobody writes the record before the end of the launch)
     const SvmProb pr = probs[blockIdx.x];
-    const uint32_t tid = threadIdx.x, nt = blockDim.x, n = pr.n;
-    const double Cp = pr.Cp, Cn = pr.Cn;
-    const uint32_t* idx = idx_all + pr.idx_off;
-    const signed char* y = y_all + pr.idx_off;
-    double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
-    const size_t n8 = ((size_t)n + 7) & ~(size_t)7;
-    double* sA = reinterpret_cast<double*>(smem);
-    double* sG = sA + n8;
-    SvmRed red;
-    red.v = sG + n8;
-    red.pv = red.v + nt;
-    red.i = reinterpret_cast<int*>(red.pv + SVM_PART);
-    red.w = red.i + nt;
-    red.pi = red.w + nt;
-    red.pw = red.pi + SVM_PART;
-    signed char* sY = reinterpret_cast<signed char*>(red.pw + SVM_PART);
-
-    for (uint32_t e = tid; e < n; e += nt) { sA[e] = alpha[e]; sG[e] = G[e]; sY[e] = y[e]; }
-    long long iter = rec->iter;
-    double gmax = rec->gmax, gmin = rec->gmin;
-    int done = 0, converged = 0;
-    __syncthreads();
-
-    for (uint32_t c = 0; c < chunk; ++c) {
-        // ---- 1. i, Gmax, Gmin
-        double vmax = -svm_inf(), vmin = svm_inf();
-        int imax = SVM_NONE, none = 0;
-        for (uint32_t e = tid; e < n; e += nt) {
-            const int ye = sY[e];
-            const double a = sA[e], v = svm_v(ye, sG[e]);
-            if (svm_in_up(ye, a, Cp) && svm_better_max(v, (int)e, vmax, imax)) { vmax = v; imax = (int)e; }
-            if (svm_in_low(ye, a, Cn) && v < vmin) vmin = v;
-        }
-        svm_reduce<true>(red, &vmax, &imax, &none);
-        int at = 0;
-        svm_reduce<false>(red, &vmin, &at, &none);
-        gmax = vmax; gmin = vmin;
-        if (__dsub_rn(gmax, gmin) <= eps) { done = 1; converged = 1; break; }
-        if (iter >= max_iter) { done = 1; break; }
-        const uint32_t i = (uint32_t)imax, ri = idx[i];
-        // ---- 2. j (row i and the elements' rows stay in registers for step 4)
-        double kit[SVM_WG_ITEMS];
-        uint32_t row[SVM_WG_ITEMS];
-        double obj = svm_inf();
-        int j = SVM_NONE;
-#pragma unroll
-        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
-            const uint32_t e = tid + (uint32_t)q * nt;
-            kit[q] = 0.0;
-            row[q] = 0;
-            if (e < n) {
-                row[q] = idx[e];
-                kit[q] = svm_cell(K, diag, ri, row[q]);
-                const int ye = sY[e];
-                double o;
-                if (svm_in_low(ye, sA[e], Cn) && svm_j_objective(gmax, svm_v(ye, sG[e]), kit[q], &o) && svm_better_min(o, (int)e, obj, j)) { obj = o; j = (int)e; }
-            }
-        }
-        svm_reduce<false>(red, &obj, &j, &none);
-        if (j == SVM_NONE) { done = 1; break; }  // no candidate: as in k_svm_wg
-        // ---- 3. the step, by every thread alike
-        const uint32_t rj = idx[j];
-        const int yi = sY[i], yj = sY[j];
-        const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
-        double ai = ai0, aj = aj0;
-        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, Cp, Cn, &ai, &aj);
-        const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
-        __syncthreads();  // (everybody has read alpha and G of i and j)
-        // ---- 4. G, alpha
-#pragma unroll
-        for (int q = 0; q < SVM_WG_ITEMS; ++q) {
-            const uint32_t e = tid + (uint32_t)q * nt;
-            if (e < n) {
-                sG[e] = svm_new_G(sG[e], sY[e], yi, yj, kit[q], svm_cell(K, diag, rj, row[q]), dai, daj);
-                if (e == i) sA[e] = ai;
-                if (e == (uint32_t)j) sA[e] = aj;
-            }
-        }
-        ++iter;
-    }
-    __syncthreads();
-    for (uint32_t e = tid; e < n; e += nt) { alpha[e] = sA[e]; G[e] = sG[e]; }
-    if (tid == 0) {
-        rec->iter = iter; rec->gmax = gmax; rec->gmin = gmin;
-        rec->done = done; rec->converged = converged; rec->pending = 0;
-    }
+    svm_wg_iterations(smem, K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, pr.Cn, eps, max_iter, chunk, alpha_all + pr.st_off,
+                      G_all + pr.st_off, y_all + pr.idx_off, rec);
 }
 
 // The two launches with the problem in blockIdx.y: the grid is (the largest problem's workgroups, problems), and a workgroup
@@ -541,67 +501,11 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_i_batch(const SrcT* 
                                                                     const uint32_t* idx_all, const signed char* y_all, double* alpha_all,
                                                                     double* G_all, const double* krow_all, const SvmRecB* rbs, SvmRecA* ras,
                                                                     SvmCandI* cand_i_all, const SvmCandJ* cand_j_all) {
-    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
-    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
-    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
     const SvmProb pr = probs[blockIdx.y];
-    const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
+    const uint32_t n_wg = (pr.n + SVM_THREADS - 1) / SVM_THREADS;
     if (blockIdx.x >= n_wg) return;
-    const double Cp = pr.Cp, Cn = pr.Cn;
-    const uint32_t* idx = idx_all + pr.idx_off;
-    const signed char* y = y_all + pr.idx_off;
-    double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
-    const double* krow = krow_all + pr.st_off;
-    const SvmRecB* rb = rbs + blockIdx.y;
-    SvmRecA* ra = ras + blockIdx.y;
-    SvmCandI* cand_i = cand_i_all + pr.wg_off;
-    const SvmCandJ* cand_j = cand_j_all + pr.wg_off;
-    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
-    if (rb->done) {
-        if (blockIdx.x == 0 && tid == 0) { ra->iter = rb->iter; ra->done = 1; }
-        return;
-    }
-    long long iter = rb->iter;
-    const bool mine = t < n;
-    const int yt = mine ? (int)y[t] : 1;
-    double a = mine ? alpha[t] : 0.0, g = mine ? G[t] : 0.0;
-    if (rb->pending) {
-        double obj = svm_inf();
-        int j = SVM_NONE, w = 0;
-        for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
-            const double o = cand_j[q].obj;
-            const int oj = cand_j[q].j;
-            if (svm_better_min(o, oj, obj, j)) { obj = o; j = oj; w = (int)q; }
-        }
-        svm_reduce<false>(red, &obj, &j, &w);
-        if (j == SVM_NONE) {  // no workgroup had a candidate: as in k_svm_select_i
-            if (blockIdx.x == 0 && tid == 0) { ra->iter = iter; ra->done = 2; }
-            return;
-        }
-        const SvmCandJ cj = cand_j[w];
-        const int i = rb->i, yi = rb->yi;
-        double ai = rb->ai, aj = cj.aj;
-        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, Cp, Cn, &ai, &aj);
-        const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
-        if (mine) {
-            g = svm_new_G(g, yt, yi, cj.yj, krow[t], svm_cell(K, diag, idx[j], idx[t]), dai, daj);
-            G[t] = g;
-            if (t == (uint32_t)i) { a = ai; alpha[t] = a; }
-            if (t == (uint32_t)j) { a = aj; alpha[t] = a; }
-        }
-        ++iter;
-    }
-    const double v = svm_v(yt, g);
-    double vmax = -svm_inf(), vmin = svm_inf();
-    int imax = SVM_NONE, none = 0, at = 0;
-    if (mine && svm_in_up(yt, a, Cp)) { vmax = v; imax = (int)t; }
-    if (mine && svm_in_low(yt, a, Cn)) vmin = v;
-    svm_reduce<true>(red, &vmax, &imax, &none);
-    svm_reduce<false>(red, &vmin, &at, &none);
-    if (tid == 0) {
-        cand_i[blockIdx.x].vmax = vmax; cand_i[blockIdx.x].vmin = vmin; cand_i[blockIdx.x].imax = imax;
-        if (blockIdx.x == 0) { ra->iter = iter; ra->done = 0; }
-    }
+    svm_select_i(K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, pr.Cn, alpha_all + pr.st_off, G_all + pr.st_off, y_all + pr.idx_off,
+                 krow_all + pr.st_off, rbs + blockIdx.y, ras + blockIdx.y, cand_i_all + pr.wg_off, cand_j_all + pr.wg_off, n_wg);
 }
 
 template <typename SrcT>
@@ -610,68 +514,12 @@ __global__ __launch_bounds__(SVM_THREADS) void k_svm_select_j_batch(const SrcT* 
                                                                     long long max_iter, const double* alpha_all, const double* G_all,
                                                                     double* krow_all, SvmRecB* rbs, const SvmRecA* ras,
                                                                     const SvmCandI* cand_i_all, SvmCandJ* cand_j_all) {
-    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
-    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
-    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
     const SvmProb pr = probs[blockIdx.y];
-    const uint32_t n = pr.n, n_wg = (n + SVM_THREADS - 1) / SVM_THREADS;
+    const uint32_t n_wg = (pr.n + SVM_THREADS - 1) / SVM_THREADS;
     if (blockIdx.x >= n_wg) return;
-    const double Cp = pr.Cp, Cn = pr.Cn;
-    const uint32_t* idx = idx_all + pr.idx_off;
-    const signed char* y = y_all + pr.idx_off;
-    const double *alpha = alpha_all + pr.st_off, *G = G_all + pr.st_off;
-    double* krow = krow_all + pr.st_off;
-    SvmRecB* rb = rbs + blockIdx.y;
-    const SvmRecA* ra = ras + blockIdx.y;
-    const SvmCandI* cand_i = cand_i_all + pr.wg_off;
-    SvmCandJ* cand_j = cand_j_all + pr.wg_off;
-    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
-    if (ra->done) {
-        if (ra->done == 2 && blockIdx.x == 0 && tid == 0) { rb->iter = ra->iter; rb->done = 1; rb->converged = 0; rb->pending = 0; }
-        return;
-    }
-    const long long iter = ra->iter;
-    double vmax = -svm_inf(), vmin = svm_inf();
-    int imax = SVM_NONE, none = 0, at = 0;
-    for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
-        const double x = cand_i[q].vmax, m = cand_i[q].vmin;
-        const int xi = cand_i[q].imax;
-        if (svm_better_max(x, xi, vmax, imax)) { vmax = x; imax = xi; }
-        if (m < vmin) vmin = m;
-    }
-    svm_reduce<true>(red, &vmax, &imax, &none);
-    svm_reduce<false>(red, &vmin, &at, &none);
-    const bool converged = __dsub_rn(vmax, vmin) <= eps;
-    if (converged || iter >= max_iter) {
-        if (blockIdx.x == 0 && tid == 0) {
-            rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
-            rb->done = 1; rb->converged = converged ? 1 : 0; rb->pending = 0;
-        }
-        return;
-    }
-    const uint32_t i = (uint32_t)imax;
-    double obj = svm_inf(), kit = 0.0, a = 0.0, g = 0.0;
-    int j = SVM_NONE, yt = 1;
-    if (t < n) {
-        kit = svm_cell(K, diag, idx[i], idx[t]);
-        krow[t] = kit;
-        yt = (int)y[t]; a = alpha[t]; g = G[t];
-        double o;
-        if (svm_in_low(yt, a, Cn) && svm_j_objective(vmax, svm_v(yt, g), kit, &o) && svm_better_min(o, (int)t, obj, j)) { obj = o; j = (int)t; }
-    }
-    svm_reduce<false>(red, &obj, &j, &none);
-    if (j == SVM_NONE) {
-        if (tid == 0) { cand_j[blockIdx.x].obj = svm_inf(); cand_j[blockIdx.x].j = SVM_NONE; }
-    } else if (t == (uint32_t)j) {
-        SvmCandJ c;
-        c.obj = obj; c.aj = a; c.Gj = g; c.Kij = kit; c.j = j; c.yj = yt;
-        cand_j[blockIdx.x] = c;
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
-        rb->ai = alpha[i]; rb->Gi = G[i]; rb->i = (int)i; rb->yi = (int)y[i];
-        rb->done = 0; rb->converged = 0; rb->pending = 1;
-    }
+    svm_select_j(K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, pr.Cn, eps, max_iter, alpha_all + pr.st_off, G_all + pr.st_off,
+                 y_all + pr.idx_off, krow_all + pr.st_off, rbs + blockIdx.y, ras + blockIdx.y, cand_i_all + pr.wg_off, cand_j_all + pr.wg_off,
+                 n_wg);
 }
 
 // OUT-OF-FOLD DECISION VALUES: for the value of C blockIdx.y and training row t, out[c][t] = sum_i coef_p[i] K(t, i) - rho_p

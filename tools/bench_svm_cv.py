@@ -20,7 +20,10 @@ problems' iteration counts, and
 What does not run says so in the JSON. The prediction written down before the first measurement: while P <= 256 compute units
 the batch costs about what its slowest problem costs alone (`slowest_problem_alone_ms`, from per_problem, beside it).
 
-    tools/bench_svm_cv.py [--cases ep300,ep47848,dna32k] [--max-iter 40000] [--out profiles/svm_cv.json]"""
+With --parent-lib none of that runs: the batched call alone, in turns with the same call on another build (versus_parent).
+
+    tools/bench_svm_cv.py [--cases ep300,ep47848,dna32k] [--max-iter 40000] [--out profiles/svm_cv.json]
+                          [--parent-lib PATH [--parent-seat first|second] [--rounds 5] [--key SUFFIX]]"""
 import argparse
 import json
 import os
@@ -59,6 +62,44 @@ def timed(fn):
     t0 = time.perf_counter()
     r = fn()
     return r, 1e3 * (time.perf_counter() - t0)
+
+
+def versus_parent(name, parent_path, parent_first, rounds, max_iter, eps, folds):
+    """--parent-lib: the batch alone, this library and another build of it (the parent commit's) in turns on one device, as
+    tools/bench_svm_weighted.py does for the single solve: both series of milliseconds a call (fsk_svm_cv_info.ms), this
+    library's median against the other's own spread, and whether every problem and out-of-fold value is the other's bit for bit."""
+    import statistics
+    import fastsk_amd
+    from fastsk_amd import _native
+    case = CASES[name]
+    tok, off, y = case["data"]()
+    fold = fastsk_amd.stratified_folds(y, folds, seed=0)
+    libs = [_native.Library(parent_path), None] if parent_first else [None, _native.Library(parent_path)]
+    engines, ms, last = [], ([], []), [None, None]
+    for lib in libs:   # (the seat: whose engine is made first and solves first)
+        e = _native.Engine(case["g"], case["m"], lib=lib)
+        e.load_sequences(tok, off, len(off) - 1, 0)
+        e.accumulate(np.arange(case["combos"] or e.lib.num_combos(case["g"], case["m"]), dtype=np.int32))
+        e.finalize()
+        if case["wg_max"] is not None:
+            e.set_tuning("svm_wg_max", case["wg_max"])
+        e.svm_cv(y, fold, case["Cs"], eps, 50)   # warm: code objects, buffers
+        engines.append(e)
+    for _ in range(rounds):
+        for k, e in enumerate(engines):
+            last[k] = e.svm_cv(y, fold, case["Cs"], eps, max_iter)
+            ms[k].append(round(last[k]["ms"], 3))
+    same = last[0]["problems"] == last[1]["problems"] and np.array_equal(last[0]["decision"], last[1]["decision"]) and \
+        last[0]["launches"] == last[1]["launches"] and last[0]["form"] == last[1]["form"]
+    mine, theirs = (ms[1], ms[0]) if parent_first else (ms[0], ms[1])
+    med = statistics.median(mine)
+    for e in engines:
+        e.close()
+    return dict(case=name, n_train=len(y), problems=len(last[0]["problems"]), form=last[0]["form"], launches=last[0]["launches"],
+                iterations=[q["iterations"] for q in last[0]["problems"]], parent_seat="first" if parent_first else "second", ms=mine,
+                median_ms=med, parent=dict(ms=theirs, median_ms=statistics.median(theirs), lowest=min(theirs), highest=max(theirs)),
+                results_equal_the_parents=bool(same), median_within_the_parents_spread=bool(min(theirs) <= med <= max(theirs)),
+                median_over_parents_median=round(med / statistics.median(theirs), 4))
 
 
 def run_case(name, max_iter, eps, folds, subset_max_n, host_max_n):
@@ -136,16 +177,25 @@ def main():
     ap.add_argument("--folds", type=int, default=5)
     ap.add_argument("--subset-max-n", type=int, default=8192)
     ap.add_argument("--host-max-n", type=int, default=8192)
+    ap.add_argument("--parent-lib", default=None, help="another build of libfastsk_amd.so: time the batch alone against it, in turns (nothing else runs)")
+    ap.add_argument("--parent-seat", choices=("first", "second"), default="first", help="whose engine is made first and solves first in a round")
+    ap.add_argument("--rounds", type=int, default=5, help="--parent-lib: calls a library")
+    ap.add_argument("--key", default="", help="a suffix for the JSON keys of this run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "svm_cv.json"))
     args = ap.parse_args()
     cur = {}
     if os.path.exists(args.out):
         with open(args.out) as f:
             cur = json.load(f)
+    if args.parent_lib:
+        import torch  # noqa: F401  (one HIP runtime for both libraries: torch's, loaded first)
     for name in args.cases.split(","):
-        res = run_case(name, args.max_iter, args.eps, args.folds, args.subset_max_n, args.host_max_n)
+        if args.parent_lib:
+            res = versus_parent(name, args.parent_lib, args.parent_seat == "first", args.rounds, args.max_iter, args.eps, args.folds)
+        else:
+            res = run_case(name, args.max_iter, args.eps, args.folds, args.subset_max_n, args.host_max_n)
         print(json.dumps(res), flush=True)
-        cur["case_" + name] = res
+        cur["case_" + name + args.key] = res
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(cur, f, indent=1, sort_keys=True)
