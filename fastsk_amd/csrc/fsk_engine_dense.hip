@@ -201,7 +201,9 @@ int accumulate_dense(fsk_engine* e, const int32_t* combos, int n, u64* K, int64_
     }
     // Shift classes (fsk_engine_dense_shift.hip): one weighted Gram product per chain of combinations that differ by a shift of
     // all kept positions, the other members by edge lookups. Checked per call; any other call runs as it always did. The
-    // 16384 tiles of the default are a condition, not a tuned number: from there a tile has one workgroup anyway.
+    // 16384 tiles of the default are a condition, not a tuned number: from there a tile has one workgroup anyway. chunk == n
+    // also is the u32 bound of the one base launch over all groups (k_dense_tile_shift_all, whose sums hold every base at
+    // once): the whole list, and so its n_bases <= n chain bases, fits by_overflow slots, n_bases * maxW^2 < 2^32.
     const bool use_shift = e->tune.dense_shift >= 0 && chunk == n && n >= 2 && !compact && !e->revcomp && !e->wild && !e->cw &&
                            !(e->mm_on() && !e->mm_plain) && Vq8 <= 32 && first_test_tile == 0xffffffffu && !e->cfg.skip_test_block &&
                            ((e->tune.tile_splits == 0 && n_tiles >= 16384) || (e->tune.tile_splits == 1 && e->tune.dense_shift > 0)) &&

@@ -6,11 +6,17 @@
 //   dense_shift_plan   host arithmetic on the kept positions: shapes -> chains -> slot order (chain bases first, grouped by
 //                      chain length), the groups of the base launch, the derived steps. Cached by the combination list.
 //   k_dense_edge_keys  the two keys of every (sequence, derived step), once per counted list
-//   k_dense_tile_shift the body of the headline kernel (fsk_tile_kernel_dma.inc, FSK_DMA_SHIFT) over the chain bases, one
-//                      launch per group of equal chain length n, whose sums leave as (u64) sum x n: the first launch stores
-//                      when the pass may (every cell j <= i, zeros included), the later ones add their non-zero cells. (One
-//                      launch that flushes and clears at every group end keeps 64 sums, the flush's index arithmetic and the
-//                      pipeline's state live at once: 128 VGPRs and 92 bytes of scratch a lane from the compiler.)
+//   k_dense_tile_shift_all  the body of the headline kernel (fsk_tile_kernel_dma.inc, FSK_DMA_SHIFT 2) over the chain bases in
+//                      ONE launch (tuning dense_shift_one_launch; by default from 16384 tiles): the groups of equal chain
+//                      length run longest first in one pipeline, and at a group's end the sums leave as (u64) sum x (the
+//                      length minus the next group's) without being cleared, so a base of length n has left n times at the
+//                      end. A tile's first flush stores when the pass may (every cell j <= i, zeros included), the later
+//                      ones add their non-zero cells. The flush makes its row and column indices from an opaque copy of the
+//                      thread index: made from threadIdx they are hoisted in front of the pipeline and spill (128 VGPRs and
+//                      88 bytes of scratch a lane; 122 and none as written).
+//   k_dense_tile_shift the same body (FSK_DMA_SHIFT 1) as one launch per group, whose sums leave as (u64) sum x n: where the
+//                      one launch does not run (dense_shift_one_launch = -1, the shift path forced below 16384 tiles, a plan
+//                      whose group was cut at by_overflow slots)
 //   k_dense_keymajor   the count panels once more per counted list as key-major planes (a dword = one key of 8 sequences)
 //   k_dense_shift_packed  the derived steps from those planes, eight cells an LDS read (tuning dense_shift_packed)
 //   k_dense_shift_fix  the derived steps from the count panels themselves: dense_shift_packed = -1, and whenever the key-major
@@ -30,6 +36,12 @@ namespace fsk {
 #define FSK_DMA_SHIFT 1
 #define FSK_DMA_KERNEL k_dense_tile_shift
 #define FSK_DMA_COMPACT 0
+#include "fsk_tile_kernel_dma.inc"
+#undef FSK_DMA_KERNEL
+#undef FSK_DMA_SHIFT
+
+#define FSK_DMA_SHIFT 2
+#define FSK_DMA_KERNEL k_dense_tile_shift_all
 #include "fsk_tile_kernel_dma.inc"
 #undef FSK_DMA_KERNEL
 #undef FSK_DMA_COMPACT
@@ -94,6 +106,19 @@ bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overfl
                 lower = upper;
             }
         }
+        // the one launch over all groups: the sums are not cleared at a group's end, so group g leaves multiplied by its chain
+        // length minus the next group's (the last by its own) and a base of length n has left n times at the end. Lengths
+        // fall strictly from group to group unless a group was cut at by_overflow slots: then the table stays empty.
+        bool falling = true;
+        for (size_t gi = 2; gi + 1 < p.groups.size(); gi += 2) falling = falling && p.groups[gi + 1] < p.groups[gi - 1];
+        if (falling) {
+            for (size_t gi = 0; gi + 1 < p.groups.size(); gi += 2) {
+                p.group_steps.push_back(p.groups[gi]);
+                p.group_steps.push_back(p.groups[gi + 1] - (gi + 3 < p.groups.size() ? p.groups[gi + 3] : 0u));
+            }
+            p.group_steps.push_back(0xffffffffu);
+            p.group_steps.push_back(0u);
+        }
     }
     return !p.steps.empty() && n <= 32768 && ((u64)2 * e->maxW + 32) * p.wsum < ((u64)1 << 31);
 }
@@ -102,9 +127,12 @@ bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overfl
 int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad) {
     ShiftPlan& p = e->shift;
     const uint32_t n_steps = (uint32_t)(p.steps.size() / 2), np_seq = panels_pad * fsk::PANEL;
-    FSK_HIP(e->d_shift_steps.reserve(p.steps.size()));
+    FSK_HIP(e->d_shift_steps.reserve(p.steps.size() + p.group_steps.size()));  // the step table, the one launch's group table behind it
     FSK_HIP(e->d_edge_keys.reserve((size_t)n_steps * np_seq));
     FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p, p.steps.data(), p.steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    if (!p.group_steps.empty())
+        FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p + p.steps.size(), p.group_steps.data(), p.group_steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               e->stream));
     FSK_LAUNCH(fsk::k_dense_edge_keys, dim3(panels_pad, (n_steps + 3u) / 4u), dim3(256), 0, e->stream, e->view(), e->cfg.g, e->k, e->sigma, chunk_pos,
                (const uint32_t*)e->d_shift_steps.p, n_steps, np_seq, e->d_edge_keys.p);
     FSK_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors are pageable memory)
@@ -159,13 +187,26 @@ int dense_shift_keymajor(fsk_engine* e, uint32_t panels_pad, int nb, uint32_t Vq
 // the tile pass of accumulate_dense: the weighted base products, then the corrections
 int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t nst, u64* K, int store, uint32_t panels_pad) {
     const ShiftPlan& p = e->shift;
-    int slot0 = 0;
-    for (size_t gi = 0; gi + 1 < p.groups.size(); gi += 2) {  // {end slot, chain length}
-        const int end = (int)p.groups[gi];
-        FSK_LAUNCH(fsk::k_dense_tile_shift, dim3((uint32_t)n_tiles, 1), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
-                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, nb, Vq8, nst, (uint32_t)e->N, K, end - slot0, gi == 0 ? store : 0,
-                   slot0, p.groups[gi + 1]);
-        slot0 = end;
+    // One launch over all groups (tuning dense_shift_one_launch), from the size at which the shift path runs by its own default
+    // rule. Its u32 sums hold all bases at once, n_bases * maxW^2 < 2^32: the path's condition chunk == n says the whole list,
+    // and so its bases, fit by_overflow = (2^32 - 1) / maxW^2 slots. A plan with a group cut at by_overflow slots has no table.
+    const bool one_launch = !p.group_steps.empty() && (e->tune.dense_shift_one_launch > 0 ||
+                                                       (e->tune.dense_shift_one_launch == 0 && e->tune.tile_splits == 0 && n_tiles >= 16384));
+    int base_launches = 1;
+    if (one_launch) {
+        FSK_LAUNCH(fsk::k_dense_tile_shift_all, dim3((uint32_t)n_tiles, 1), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4.p,
+                   (const uint32_t*)e->d_C4H.p, (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, nb, Vq8, nst, (uint32_t)e->N, K,
+                   (int)p.n_bases, store, (const uint32_t*)e->d_shift_steps.p + p.steps.size());
+    } else {
+        base_launches = (int)(p.groups.size() / 2);
+        int slot0 = 0;
+        for (size_t gi = 0; gi + 1 < p.groups.size(); gi += 2) {  // {end slot, chain length}
+            const int end = (int)p.groups[gi];
+            FSK_LAUNCH(fsk::k_dense_tile_shift, dim3((uint32_t)n_tiles, 1), dim3(256), 0, e->stream, (const uint32_t*)e->d_C4.p,
+                       (const uint32_t*)e->d_C4H.p, (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, nb, Vq8, nst, (uint32_t)e->N, K,
+                       end - slot0, gi == 0 ? store : 0, slot0, p.groups[gi + 1]);
+            slot0 = end;
+        }
     }
     if (e->ld.shift_packed) {
         const auto k_packed = e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true> : fsk::k_dense_shift_packed<false>;
@@ -177,7 +218,7 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
                    (const uint16_t*)e->d_edge_keys.p, panels_pad * fsk::PANEL, nb, Vq8, (uint32_t)e->N, K);
     }
-    e->st.launches += (int32_t)(p.groups.size() / 2);  // (the groups and the corrections; the caller counts one)
+    e->st.launches += (int32_t)base_launches;  // (the base launches and the corrections; the caller counts one)
     return FSK_OK;
 }
 

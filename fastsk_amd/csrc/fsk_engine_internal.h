@@ -143,6 +143,7 @@ using fsk_detail::Event;
     X(dense_shift, 0, -1, 1, "dense: one weighted Gram product per chain of shifted combinations, the other members by edge lookups (fsk_engine_dense_shift.hip) — 1 = whenever the call is eligible, -1 = never (0: when eligible, tile_splits = 0 and the launch has 16384 tiles or more, the size from which a tile has one workgroup anyway)") \
     X(dense_shift_packed, 0, -1, 0, "dense, shift classes: the derived steps from key-major planes, eight cells an LDS read (k_dense_keymajor, k_dense_shift_packed; chains cut at nine members) — 0 = whenever the shift path runs and the planes fit, -1 = never: k_dense_shift_fix on the count panels") \
     X(dense_shift_inplace, 1, 0, 1, "dense, shift classes: k_dense_shift_packed stages a chain's first planes and makes every further step's in LDS, one nibble up and one down a sequence (a step that meets a count above 15 in its tile, and the step behind it, are staged) — 0 = every step staged") \
+    X(dense_shift_one_launch, 0, -1, 1, "dense, shift classes: every chain-length group of the base products in ONE launch that flushes at the group ends without clearing (k_dense_tile_shift_all) — 1 = whenever the shift path runs, -1 = never: one k_dense_tile_shift launch a group (0: where the shift path runs by its own default rule, tile_splits = 0 and 16384 tiles or more)") \
     X(dense_shift_plane_kb, 0, 0, (int64_t)1 << 40, "dense, shift classes: the key-major planes and offsets may take this many KiB at most (0: half of the free memory; tests: the planes do not fit)") \
     X(dense_chunk, 0, 0, 1 << 24, "dense: cap of the count kernel's staging chunk, in windows (0: none)")                             \
     X(variance_dense_slots, 1, 0, 1, "variance mode, dense: 0 = zero fill + k_welford per iteration instead of storing slot triangles") \
@@ -218,12 +219,14 @@ struct SxScratch {
 
 // The shift-class plan of a combination list (fsk_engine_dense_shift.hip): the count panels' slot order — chain bases first,
 // grouped by chain length, then the derived members —, the base launch's groups {end slot, weight} and the derived steps
-// {upper slot << 16 | lower slot, weight}.
+// {upper slot << 16 | lower slot, weight}. For the one base launch over all groups (k_dense_tile_shift_all) the groups once
+// more as {end slot, weight step}: the chain length minus the next group's, the last group's length itself, and {~0, 0} behind
+// them; empty when a group was cut at by_overflow slots (two groups of one length: the per-group launches run).
 struct ShiftPlan {
     std::vector<int32_t> combos;   // the list the plan was made for
     u64 by_overflow = 0;           // ... and the most slots a u32 sum takes
     std::vector<int32_t> order;    // slot -> place in the list
-    std::vector<uint32_t> groups, steps;
+    std::vector<uint32_t> groups, steps, group_steps;
     uint32_t n_bases = 0;
     uint32_t max_chain = 0;        // members a chain was cut after (0: never)
     u64 wsum = 0;                  // sum of the steps' weights

@@ -10,6 +10,12 @@
 // and once more, in fsk_engine_dense_shift.hip, with FSK_DMA_SHIFT 1:
 //   k_dense_tile_shift   a group of chain bases of the shift-class plan, slots [slot0, slot0 + slots_per_split) of the n_slots
 //       counted: every sum leaves multiplied by `weight`, the group's chain length, the product taken in 64 bits.
+// and, there too, with FSK_DMA_SHIFT 2:
+//   k_dense_tile_shift_all   every group of the plan in ONE launch, longest chains first: slots [0, slots_per_split) in one
+//       pipeline, and where the slot crosses a group's end (`groups`: pairs {end slot, weight step}, a pair {~0, 0} behind the
+//       last) the sums leave as (u64) sum x step WITHOUT being cleared: step_g = n_g - n_(g+1) (n past the last group = 0), so
+//       a base of chain length n leaves n times in all. The first flush stores where the pass may, every later one adds. The
+//       next stage's loads stay in flight under a flush; the sums hold all bases at once, which the caller's bound covers.
 // Two plain functions rather than one template: instantiations of one template share register-
 // allocation context on hipcc, and a second variant must not perturb the common one.
 //
@@ -60,8 +66,10 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
 #if FSK_DMA_COMPACT
                                                         , const uint16_t* vc
 #endif
-#if FSK_DMA_SHIFT
+#if FSK_DMA_SHIFT == 1
                                                         , int slot0, uint32_t weight
+#elif FSK_DMA_SHIFT == 2
+                                                        , const uint32_t* groups
 #endif
 ) {
     constexpr int MAXF = 4;           // flagged rows whose hi plane is fetched per round
@@ -80,8 +88,10 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     const uint32_t tile = tile_tab[blockIdx.x];
     const uint32_t ti = tile >> 16, tj = tile & 0xffffu;
-#if FSK_DMA_SHIFT
+#if FSK_DMA_SHIFT == 1
     const int s0 = slot0;
+#elif FSK_DMA_SHIFT == 2
+    const int s0 = 0;
 #else
     const int s0 = blockIdx.y * slots_per_split;
 #endif
@@ -203,6 +213,35 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
     const int chunk_slots = (int)(MASK_WORDS / nst) > 0 ? (int)(MASK_WORDS / nst) : 1;
 #define FSK_ROWS_OF(sl) Vq8
 #endif
+#if FSK_DMA_SHIFT == 2
+    // The group at hand: its end slot and weight step (workgroup-uniform; the table ends with {~0, 0}), whether its flush is
+    // the tile's first. The mask chunks below know nothing of the groups: a group's end may fall inside a chunk.
+    int g_end = __builtin_amdgcn_readfirstlane((int)groups[0]);
+    uint32_t g_step = (uint32_t)__builtin_amdgcn_readfirstlane((int)groups[1]);
+    int g_at = 0;
+    // The sums leave multiplied by `step` and stay. Row and column indices are made from an opaque copy of the thread index
+    // HERE: made from `tid` they are loop-invariant, the compiler hoists all sixteen in front of the pipeline and the 64 sums
+    // no longer fit beside them (23 spilled registers, 88 bytes of scratch a lane).
+    auto flush_group = [&](uint32_t step, bool st) {
+        const uint32_t t = fsk_hw::vgpr_copy((uint32_t)tid);
+        const uint32_t fy = t >> 4, fx = t & 15u;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const u64 i = (u64)ti * TILE + tile_index(fy, (uint32_t)a);
+            if (i >= N) continue;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const u64 j = (u64)tj * TILE + tile_index(fx, (uint32_t)b);
+                // st (workgroup-uniform): the tile's first flush of a pass that may store writes every cell j <= i, zeros too
+                if (j <= i && (st || acc[a][b] != 0u)) {
+                    const uint32_t lo = fsk_hw::vgpr_copy(acc[a][b]);  // a copy: see the header
+                    if (st) K[tri_index(i, j)] = (u64)lo * step;
+                    else atomicAdd(&K[tri_index(i, j)], (u64)lo * step);
+                }
+            }
+        }
+    };
+#endif
     for (int c0 = s0; c0 < s1; c0 += chunk_slots) {
         const int c1 = c0 + chunk_slots < s1 ? c0 + chunk_slots : s1;
         __syncthreads();  // the previous chunk's masks and stage buffers are no longer read
@@ -296,6 +335,18 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
                     first = false;
                 }
             }
+#if FSK_DMA_SHIFT == 2
+            // The group's last stage has been multiplied: flush under the next stage's loads. A lane is the only writer of its
+            // cells in this launch, and its store of a cell is ordered before its own later add to it by the vmcnt(0) of
+            // wait_loads() just below: stores and atomics count into vmcnt like the loads, so that wait — which every stage
+            // has, and the last stage of a chunk too — is passed only when this flush has been acknowledged.
+            if (nslot != slot && nslot == g_end) {
+                flush_group(g_step, store != 0 && g_at == 0);
+                ++g_at;
+                g_end = __builtin_amdgcn_readfirstlane((int)groups[2 * g_at]);
+                g_step = (uint32_t)__builtin_amdgcn_readfirstlane((int)groups[2 * g_at + 1]);
+            }
+#endif
             wait_loads();     // this wave's part of the next stage has landed
             __syncthreads();  // ... everyone's has, and everyone is done with the current buffer
             slot = nslot;
@@ -315,7 +366,7 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
 #pragma unroll
             for (int b = 0; b < 8; ++b) blk[(a * 8 + b) * 256 + tid] = acc[a][b];
     }
-#else
+#elif FSK_DMA_SHIFT != 2
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
         const u64 i = (u64)ti * TILE + tile_index((uint32_t)ty, (uint32_t)a);
@@ -328,7 +379,7 @@ __global__ __launch_bounds__(256, 4) void FSK_DMA_KERNEL(const uint32_t* C4, con
             // are stored, not added: the pass needs no 8 N^2/2-byte fill in front of it.
             if (j <= i && (store || acc[a][b] != 0u)) {
                 const uint32_t lo = fsk_hw::vgpr_copy(acc[a][b]);  // a copy: see the header
-#if FSK_DMA_SHIFT
+#if FSK_DMA_SHIFT == 1
                 if (store) K[tri_index(i, j)] = (u64)lo * weight;
                 else atomicAdd(&K[tri_index(i, j)], (u64)lo * weight);
 #else
