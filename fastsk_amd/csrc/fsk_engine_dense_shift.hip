@@ -120,16 +120,42 @@ bool dense_shift_plan(fsk_engine* e, const int32_t* combos, int n, u64 by_overfl
             p.group_steps.push_back(0u);
         }
     }
+    // (the + 32 is k_dense_shift_fix's bias a cell and unit of weight; k_dense_shift_packed's is 30, for which the bound is
+    // slightly conservative)
     return !p.steps.empty() && n <= 32768 && ((u64)2 * e->maxW + 32) * p.wsum < ((u64)1 << 31);
+}
+
+// Bit 8 of a step's weight word: "unpack after this step" (k_dense_shift_packed adds the prefix sums of a batch of steps byte
+// to byte and hands the bytes to its int32 sums where the flag stands; every reader masks the weight with & 255). Set by the
+// bound alone: the step at position r (0-based) of its chain adds at most 30 (r + 1) to a byte, the table is walked in order
+// with the running bound, and the flag goes on the step before the one that would pass 255 — a batch may span chains — and on
+// the last step. Chains are cut at nine members, so one step is at most 240 and the walk never fails (a plan with uncut chains
+// runs k_dense_shift_fix only, which masks the flags off). batch = false: on every step. The flags are a schedule, not part of
+// the plan: they go into the uploaded copy only.
+static void dense_shift_unpack_flags(std::vector<uint32_t>& steps, uint32_t n_bases, bool batch) {
+    const size_t n_steps = steps.size() / 2;
+    uint32_t r = 0, bound = 0;
+    for (size_t s = 0; s < n_steps; ++s) {
+        r = (steps[2 * s] & 0xffffu) < n_bases ? 0u : r + 1u;
+        const uint32_t add = 30u * (r + 1u);
+        if (s > 0 && (!batch || bound + add > 255u)) {
+            steps[2 * s - 1] |= 256u;
+            bound = 0;
+        }
+        bound += add;
+    }
+    if (n_steps > 0) steps[2 * n_steps - 1] |= 256u;
 }
 
 // the plan's tables on the device, and the edge keys of the list just counted (chunk_pos: its kept positions in slot order)
 int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad) {
     ShiftPlan& p = e->shift;
     const uint32_t n_steps = (uint32_t)(p.steps.size() / 2), np_seq = panels_pad * fsk::PANEL;
+    std::vector<uint32_t> steps = p.steps;
+    dense_shift_unpack_flags(steps, p.n_bases, e->tune.dense_shift_batch != 0);
     FSK_HIP(e->d_shift_steps.reserve(p.steps.size() + p.group_steps.size()));  // the step table, the one launch's group table behind it
     FSK_HIP(e->d_edge_keys.reserve((size_t)n_steps * np_seq));
-    FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p, p.steps.data(), p.steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p, steps.data(), steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     if (!p.group_steps.empty())
         FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p + p.steps.size(), p.group_steps.data(), p.group_steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                e->stream));
@@ -212,7 +238,7 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
         const auto k_packed = e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true> : fsk::k_dense_shift_packed<false>;
         FSK_LAUNCH(k_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
-                   (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, p.n_bases, (uint32_t)(32u * p.wsum), (uint32_t)e->N, K);
+                   (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, p.n_bases, (uint32_t)(30u * p.wsum), (uint32_t)e->N, K);
     } else {
         FSK_LAUNCH(fsk::k_dense_shift_fix, dim3((uint32_t)n_tiles), dim3(512), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),

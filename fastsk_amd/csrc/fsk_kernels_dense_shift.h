@@ -259,15 +259,21 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 //     row term is worked on, and each group of 8 is waited for once, with a count (fsk_hw::first_use): 4 waits a step;
 //   - the step table and the row masks of the NEXT step are loaded behind the step's last lookup (they are uniform; a scalar
 //     load in flight shares the LDS reads' counter, returns out of order and turns every wait for an LDS read into a drain);
-//   - (x & m) | 0x10101010 is one v_and_or_b32 (the masks live in registers: the instruction takes no literal), and the two
-//     offsets of a key pair leave their dword, with the lane's term and the stage's base, by one fsk_hw::xor_word each.
+//   - ~d & m is one three-input bit operation and R + (s & m) + (~d & m) one v_add3_u32 (the mask lives in a register: the
+//     instructions take no literal), and the two offsets of a key pair leave their dword, with the lane's term and the stage's
+//     base, by one fsk_hw::xor_word each;
+//   - a byte leaves for its int32 sum once a BATCH of steps, not once a step (below).
 //
-// Byte-parallel sums (m = 0x0f0f0f0f): ((s & m) | 0x10101010) - (d & m) holds four differences + 16, each in [1, 31], no borrow
-// between bytes; the odd nibbles the same after >> 4. Weights are prefix sums, not multiplies: inside a chain
-// sum_u (t1 - u) D_u = sum_r R_r with R_r = sum_{u <= r} D_u, and R stays packed in bytes (R += D': the stored R of step r of a
-// chain lies in [r + 1, 31 (r + 1)] — a byte for the 8 steps dense_shift_plan cuts chains to). Every byte of R is added to its
-// int32 sum (fsk_hw::add_byte). R restarts where a step's lower slot is a chain base. The bias, 16 (r + 1) a term and step, is
-// 32 x the sum of the launch's weights a cell (`bias`), taken off at the flush: the + 32 of the host's bound.
+// Byte-parallel sums (m = 0x0f0f0f0f): (s & m) + (~d & m) holds four differences + 15, each in [0, 30], no borrow between bytes;
+// the odd nibbles the same after >> 4. Weights are prefix sums, not multiplies: inside a chain
+// sum_u (t1 - u) D_u = sum_r R_r with R_r = sum_{u <= r} D_u, and R stays packed in bytes (R += D': the R of step r of a chain
+// lies in [0, 30 (r + 1)] — a byte for the 8 steps dense_shift_plan cuts chains to). R restarts where a step's lower slot is a
+// chain base. The sum over r stays in bytes as well: Q += R every step (two adds a lookup pair), and only where the step's weight
+// word carries bit 8 — "unpack after this step", one scalar branch a step — every byte of Q is added to its int32 sum
+// (fsk_hw::add_byte, 128 a lane) and Q starts again. The host sets the flag by the bound (dense_shift_unpack_flags: 30 (r + 1) a
+// step against a byte's 255, on the step before the one that would pass it and on the last step); Q does not restart at a chain
+// base, so a batch may span chains: 125 unpacks for the 330 steps of the headline plan. Tuning dense_shift_batch = 0 flags every
+// step. The bias, 15 (r + 1) a term and step, is 30 x the sum of the launch's weights a cell (`bias`), taken off at the flush.
 //
 // Counts above 15: a step runs a second, workgroup-uniform pass when the row mask of EITHER side is set, and that pass reads the
 // key-major HI planes of BOTH sides, staged over the buffer just used, nibble by nibble at 16 x the step's weight (exact, and
@@ -296,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     // (the two masks in registers the compiler cannot see through, one of them scalar: see above)
-    const uint32_t M4 = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(0x0f0f0f0fu)), B4 = fsk_hw::vgpr_copy(0x10101010u);
+    const uint32_t M4 = (uint32_t)__builtin_amdgcn_readfirstlane(fsk_hw::vgpr_copy(0x0f0f0f0fu));
     const uint32_t tr = (w >> 1) * 8u + (lane >> 3), tc = (w & 1u) * 8u + (lane & 7u);
     const uint32_t tile = tile_tab[blockIdx.x];
     const uint32_t ti = tile >> 16, tj = tile & 0xffffu;
@@ -304,12 +310,14 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
     const size_t pair_stride = (size_t)n_slots * slot_stride;
     const uint32_t side_bytes = Vq8 * 512u;
 
-    uint32_t acc[8][8], Rr[2][8], Rc[2][8];  // acc[er][ec]; R[even / odd nibbles][ec (row term) or er (column term)]
+    // acc[er][ec]; R, Q[even / odd nibbles][ec (row term) or er (column term)]: the prefix sums, and their byte sums over a batch
+    uint32_t acc[8][8], Rr[2][8], Rc[2][8], Qr[2][8], Qc[2][8];
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[a][b] = 0u;
         Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
+        Qr[0][a] = Qr[1][a] = Qc[0][a] = Qc[1][a] = 0u;
     }
 
     const fsk_hw::lds_addr_t lds_wave = fsk_hw::lds_address(P) + w * 1024u;
@@ -343,7 +351,8 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
     auto lds_at = [&](uint32_t byte_off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(P) + byte_off); };
 
     // (the step table runs two steps ahead and the masks one, both loaded at the END of a step and landed by its barrier)
-    uint32_t sl = steps[0], wt = steps[1] & 255u, fl = flagged(sl);
+    // (wt is the whole weight word: bits 0..7 the weight, bit 8 "unpack after this step")
+    uint32_t sl = steps[0], wt = steps[1], fl = flagged(sl);
     uint32_t sn = n_steps > 1u ? steps[2] : 0u, wn = n_steps > 1u ? steps[3] : 0u;
     uint32_t s2 = 0u, w2 = 0u, fl_nx = 0u;  // (in place: the table entry of step s + 2 and the masks of step s + 1, at the head of step s)
     if constexpr (INPLACE) {
@@ -385,20 +394,16 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
         auto read_A = [&](int e) { dA[e] = lds_at(fsk_hw::xor_word<0>(oC[e], xA)); sA[e] = lds_at(fsk_hw::xor_word<1>(oC[e], xA)); };
         auto read_B = [&](int e) { dB[e] = lds_at(fsk_hw::xor_word<0>(oR[e], xB)); sB[e] = lds_at(fsk_hw::xor_word<1>(oR[e], xB)); };
         auto row_term = [&](int e) {  // column ec = e of this lane, its 8 rows
-            Rr[0][e] += ((sA[e] & M4) | B4) - (dA[e] & M4);
-            Rr[1][e] += (((sA[e] >> 4) & M4) | B4) - ((dA[e] >> 4) & M4);
-            acc[0][e] = fsk_hw::add_byte<0>(acc[0][e], Rr[0][e]); acc[1][e] = fsk_hw::add_byte<0>(acc[1][e], Rr[1][e]);
-            acc[2][e] = fsk_hw::add_byte<1>(acc[2][e], Rr[0][e]); acc[3][e] = fsk_hw::add_byte<1>(acc[3][e], Rr[1][e]);
-            acc[4][e] = fsk_hw::add_byte<2>(acc[4][e], Rr[0][e]); acc[5][e] = fsk_hw::add_byte<2>(acc[5][e], Rr[1][e]);
-            acc[6][e] = fsk_hw::add_byte<3>(acc[6][e], Rr[0][e]); acc[7][e] = fsk_hw::add_byte<3>(acc[7][e], Rr[1][e]);
+            Rr[0][e] += (sA[e] & M4) + (~dA[e] & M4);
+            Rr[1][e] += ((sA[e] >> 4) & M4) + (~(dA[e] >> 4) & M4);
+            Qr[0][e] += Rr[0][e];
+            Qr[1][e] += Rr[1][e];
         };
         auto col_term = [&](int e) {  // row er = e of this lane, its 8 columns
-            Rc[0][e] += ((sB[e] & M4) | B4) - (dB[e] & M4);
-            Rc[1][e] += (((sB[e] >> 4) & M4) | B4) - ((dB[e] >> 4) & M4);
-            acc[e][0] = fsk_hw::add_byte<0>(acc[e][0], Rc[0][e]); acc[e][1] = fsk_hw::add_byte<0>(acc[e][1], Rc[1][e]);
-            acc[e][2] = fsk_hw::add_byte<1>(acc[e][2], Rc[0][e]); acc[e][3] = fsk_hw::add_byte<1>(acc[e][3], Rc[1][e]);
-            acc[e][4] = fsk_hw::add_byte<2>(acc[e][4], Rc[0][e]); acc[e][5] = fsk_hw::add_byte<2>(acc[e][5], Rc[1][e]);
-            acc[e][6] = fsk_hw::add_byte<3>(acc[e][6], Rc[0][e]); acc[e][7] = fsk_hw::add_byte<3>(acc[e][7], Rc[1][e]);
+            Rc[0][e] += (sB[e] & M4) + (~dB[e] & M4);
+            Rc[1][e] += ((sB[e] >> 4) & M4) + (~(dB[e] >> 4) & M4);
+            Qc[0][e] += Rc[0][e];
+            Qc[1][e] += Rc[1][e];
         };
 #pragma unroll
         for (int e = 0; e < 8; ++e) read_A(e);
@@ -418,12 +423,29 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
         fsk_hw::first_use(dB[4], sB[4], dB[5], sB[5], dB[6], sB[6], dB[7], sB[7]);
 #pragma unroll
         for (int e = 4; e < 8; ++e) col_term(e);
+        if ((wt & 256u) != 0u) {  // the batch ends behind this step: every byte of Q joins its int32 sum, and Q starts again
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                acc[0][e] = fsk_hw::add_byte<0>(acc[0][e], Qr[0][e]); acc[1][e] = fsk_hw::add_byte<0>(acc[1][e], Qr[1][e]);
+                acc[2][e] = fsk_hw::add_byte<1>(acc[2][e], Qr[0][e]); acc[3][e] = fsk_hw::add_byte<1>(acc[3][e], Qr[1][e]);
+                acc[4][e] = fsk_hw::add_byte<2>(acc[4][e], Qr[0][e]); acc[5][e] = fsk_hw::add_byte<2>(acc[5][e], Qr[1][e]);
+                acc[6][e] = fsk_hw::add_byte<3>(acc[6][e], Qr[0][e]); acc[7][e] = fsk_hw::add_byte<3>(acc[7][e], Qr[1][e]);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                acc[e][0] = fsk_hw::add_byte<0>(acc[e][0], Qc[0][e]); acc[e][1] = fsk_hw::add_byte<0>(acc[e][1], Qc[1][e]);
+                acc[e][2] = fsk_hw::add_byte<1>(acc[e][2], Qc[0][e]); acc[e][3] = fsk_hw::add_byte<1>(acc[e][3], Qc[1][e]);
+                acc[e][4] = fsk_hw::add_byte<2>(acc[e][4], Qc[0][e]); acc[e][5] = fsk_hw::add_byte<2>(acc[e][5], Qc[1][e]);
+                acc[e][6] = fsk_hw::add_byte<3>(acc[e][6], Qc[0][e]); acc[e][7] = fsk_hw::add_byte<3>(acc[e][7], Qc[1][e]);
+                Qr[0][e] = Qr[1][e] = Qc[0][e] = Qc[1][e] = 0u;
+            }
+        }
         if (fl != 0u) {  // the hi planes over the buffer just used, at 16 x the weight
             __syncthreads();  // everyone is done with the lo planes
             load_stage(KMH, buf, sl);
             fsk_hw::wait_panel_rows();
             __syncthreads();
-            const uint32_t mul = 16u * wt;
+            const uint32_t mul = 16u * (wt & 255u);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 read_A(e);
@@ -466,11 +488,11 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             buf ^= 1u;
         }
         if constexpr (INPLACE) {
-            sl = sn; wt = wn & 255u; fl = fl_nx;
+            sl = sn; wt = wn; fl = fl_nx;
             sn = s2; wn = w2; fl_nx = fl_n;
             s2 = sl_n2; w2 = wt_n2;
         } else {
-            sl = sn; wt = wn & 255u; fl = fl_n;
+            sl = sn; wt = wn; fl = fl_n;
             sn = sl_n2; wn = wt_n2;
         }
     }
