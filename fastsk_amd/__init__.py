@@ -2,7 +2,7 @@
 ``FastSK(g, m, ...).compute_kernel(Xtrain, Xtest)`` path)."""
 from .utils import FastaUtility, Vocabulary  # noqa: F401
 
-__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile", "stratified_folds", "class_weights"]
+__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile", "stratified_folds", "kfold", "class_weights"]
 
 
 def __getattr__(name):
@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "stratified_folds":  # (host only, pure Python)
         from ._native import stratified_folds
         return stratified_folds
+    if name == "kfold":  # (host only, pure Python)
+        from ._native import kfold
+        return kfold
     if name == "class_weights":  # (host only, pure Python)
         from ._native import class_weights
         return class_weights

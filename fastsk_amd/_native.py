@@ -100,6 +100,11 @@ class SvmCvInfo(C.Structure):
                 ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
 
 
+class SvrCvScore(C.Structure):
+    _fields_ = [("C", C.c_double), ("epsilon", C.c_double), ("mse", C.c_double), ("mae", C.c_double), ("r2", C.c_double),
+                ("r", C.c_double), ("reserved", C.c_double * 2)]
+
+
 class SvmPlattInfo(C.Structure):
     _fields_ = [("A", C.c_double), ("B", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32), ("n_folds", C.c_int32),
                 ("form", C.c_int32), ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
@@ -138,7 +143,7 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha", "fsk_rows_build", "fsk_rows_get_block",
            "fsk_rows_get_block_device", "fsk_rows_get_info", "fsk_svm_set_kernel", "fsk_svm_get_kernel",
            "fsk_svm_set_class_weights", "fsk_svm_get_class_weights", "fsk_svm_platt_fit", "fsk_svm_calibrate",
-           "fsk_svm_get_calibration", "fsk_svm_proba"]
+           "fsk_svm_get_calibration", "fsk_svm_proba", "fsk_svr_train", "fsk_svr_get_model", "fsk_svr_cv", "fsk_svr_cv_get"]
 
 
 _hip_shared = False
@@ -298,6 +303,10 @@ class Library:
             "fsk_svm_calibrate": ([vp, vp, i32], C.c_int),
             "fsk_svm_get_calibration": ([vp, vp, C.POINTER(SvmPlattInfo)], C.c_int),
             "fsk_svm_proba": ([vp, i64, i64, vp], C.c_int),
+            "fsk_svr_train": ([vp, vp, i64, C.c_double, C.c_double, C.c_double, i64], C.c_int),
+            "fsk_svr_get_model": ([vp, vp, vp, C.POINTER(C.c_double), C.POINTER(SvmInfo)], C.c_int),
+            "fsk_svr_cv": ([vp, vp, i64, vp, i32, vp, i32, vp, i32, C.c_double, i64], C.c_int),
+            "fsk_svr_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -463,6 +472,19 @@ def stratified_folds(labels, k, seed=0):
         c = met.get(labels[t].item(), 0)
         fold[t] = c % k
         met[labels[t].item()] = c + 1
+    return fold
+
+
+def kfold(n, k, seed=0):
+    """Fold ids 0..k-1 for ``cross_validate_svr`` (host only): the rows in the order
+    ``np.random.Generator(np.random.PCG64(seed)).permutation(n)`` are dealt round-robin, the c-th row met gets fold ``c % k``.
+    -> int32 array [n]."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError("kfold: n must be a non-negative integer")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+        raise ValueError("kfold: k must be an integer of at least 2")
+    fold = np.zeros(int(n), dtype=np.int32)
+    fold[np.random.Generator(np.random.PCG64(seed)).permutation(int(n))] = np.arange(int(n), dtype=np.int32) % np.int32(k)
     return fold
 
 
@@ -961,6 +983,53 @@ class Engine:
         return {"decision": oof, "auc": np.array([s.auc for s in scores]), "accuracy": np.array([s.accuracy for s in scores]),
                 "problems": [q.as_dict() for q in problems], "form": _FORMS.get(info.form, "none"), "launches": info.launches,
                 "ms": info.ms}
+
+    # ---- epsilon-SVR on the resident triangle (the model slot is the C-SVC's: svm_decision serves either)
+    def svr_train(self, targets, C=1.0, epsilon=0.1, eps=1e-3, max_iter=-1):
+        """``fsk_svr_train``: an epsilon-SVR on the train x train part of the finalized result, ``targets`` real-valued.
+        Returns the info of the solve (``svr_model()[3]``)."""
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        if targets.ndim != 1:
+            raise ValueError("targets must be 1-D")
+        self._ck(self.lib.L.fsk_svr_train(self.h, targets.ctypes.data if len(targets) else None, len(targets), float(C), float(epsilon),
+                                          float(eps), int(max_iter)))
+        return self.svr_model()[3]
+
+    def svr_model(self):
+        """(alpha2[2 n_train]: alpha then alpha*, coef[n_train] = alpha - alpha*, rho, info dict) of the last ``svr_train``."""
+        alpha2 = np.empty(2 * self.n_train, dtype=np.float64)
+        coef = np.empty(self.n_train, dtype=np.float64)
+        rho = C.c_double(0.0)
+        info = SvmInfo()
+        self._ck(self.lib.L.fsk_svr_get_model(self.h, alpha2.ctypes.data, coef.ctypes.data, C.byref(rho), C.byref(info)))
+        return alpha2, coef, rho.value, info.as_dict()
+
+    def svr_cv(self, targets, fold, Cs, epsilons, eps=1e-3, max_iter=-1, n_folds=None):
+        """``fsk_svr_cv``: the epsilon-SVR cross-validated over the folds ``fold[t]`` (0..F-1; F = ``n_folds``, the largest id
+        + 1 when None) and the grid ``Cs`` x ``epsilons``, every problem solved side by side. Returns ``oof``
+        [n_C, n_eps, n_train] (out-of-fold predictions), ``mse``, ``mae``, ``r2``, ``r`` [n_C, n_eps], ``problems`` (problem
+        ``(c * n_eps + q) * F + f``: with ``epsilon``), ``form``, ``launches``, ``ms``."""
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        Cs = np.ascontiguousarray(Cs, dtype=np.float64)
+        epsilons = np.ascontiguousarray(epsilons, dtype=np.float64)
+        if targets.ndim != 1 or fold.ndim != 1 or Cs.ndim != 1 or epsilons.ndim != 1:
+            raise ValueError("targets, fold, Cs and epsilons must be 1-D")
+        if len(fold) != len(targets):
+            raise ValueError("%d fold ids for %d targets" % (len(fold), len(targets)))
+        if n_folds is None:
+            n_folds = int(fold.max()) + 1 if len(fold) else 0
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        self._ck(self.lib.L.fsk_svr_cv(self.h, ptr(targets), len(targets), ptr(fold), n_folds, ptr(Cs), len(Cs), ptr(epsilons), len(epsilons),
+                                       float(eps), int(max_iter)))
+        n, nC, nE = len(targets), len(Cs), len(epsilons)
+        oof = np.empty((nC, nE, n), dtype=np.float64)
+        scores, problems, info = (SvrCvScore * (nC * nE))(), (SvmCvProblem * (nC * nE * n_folds))(), SvmCvInfo()
+        self._ck(self.lib.L.fsk_svr_cv_get(self.h, oof.ctypes.data, C.addressof(scores), C.addressof(problems), C.byref(info)))
+        out = {k: np.array([getattr(s, k) for s in scores]).reshape(nC, nE) for k in ("mse", "mae", "r2", "r")}
+        out.update({"oof": oof, "problems": [dict(q.as_dict(), epsilon=q.reserved[0]) for q in problems],
+                    "form": _FORMS.get(info.form, "none"), "launches": info.launches, "ms": info.ms})
+        return out
 
     # ---- the rows kernel: L(r, c) = <K(r, train), K(c, train)> of the finalized result, K2 its cosine normalisation
     def rows_build(self):

@@ -12,6 +12,8 @@
 //     cross_validate_svm(labels, Cs, folds, ...) cross-validates it over folds and values of C in one batch (fsk_svm_cv);
 //     class_weight= on both gives LIBSVM's weighted C-SVC (fsk_svm_set_class_weights), fit_svm(probability=True) and
 //     predict_proba_np(which) Platt's probabilities (fsk_svm_calibrate / fsk_svm_proba);
+//     fit_svr(targets, C, epsilon, ...), predict_np / predict_dlpack(which) and cross_validate_svr(targets, Cs, epsilons, folds, ...)
+//     the epsilon-SVR on real-valued targets (fsk_svr_train / fsk_svr_cv), in the one model slot;
 //     both take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
 //     the kernel, through the rows kernel (fsk_rows_build; get_rows_kernel_block_np, rows_kernel_info);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
@@ -146,6 +148,7 @@ class FastSK {
     std::vector<uint32_t> center_weights_;  // centre-weighted mode: the profile (empty: off)
     std::vector<uint64_t> weights_;      // mismatch-weighted mode: c_0..c_m (empty: off)
     std::vector<int32_t> labels_;        // fit_svm: the labels of the model at hand
+    bool svr_ = false;                   // the model at hand is fit_svr's (the one model slot holds either kind)
     std::vector<int32_t> kept_tokens_;   // the call's input, kept while the test x test block is missing
     std::vector<int64_t> kept_offsets_;
 
@@ -595,6 +598,13 @@ public:
     static std::pair<double, double> parse_class_weight(const py::object& labels, const py::object& spec) {
         return py::module_::import("fastsk_amd._native").attr("class_weights")(labels, spec).cast<std::pair<double, double>>();
     }
+    static py::dict info_dict(const fsk_svm_info& s, const std::string& kernel_type) {
+        py::dict d;
+        d["iterations"] = s.iterations; d["gap"] = s.gap; d["objective"] = s.objective; d["n_sv"] = s.n_sv; d["n_bsv"] = s.n_bsv;
+        d["converged"] = (bool)s.converged; d["form"] = s.form == 1 ? "workgroup" : "two-launch"; d["launches"] = s.launches;
+        d["ms"] = s.ms; d["kernel_type"] = kernel_type;
+        return d;
+    }
     py::dict fit_svm(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter,
                      const std::string& kernel_type, py::object class_weight, bool probability, int32_t calibration_folds, uint64_t seed) {
         const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
@@ -612,12 +622,11 @@ public:
         }
         check(rc);
         labels_.assign(labels.data(), labels.data() + labels.shape(0));
+        svr_ = false;
         fsk_svm_info s;
         check(fsk_svm_get_model(h_, nullptr, nullptr, &s));
-        py::dict d;
-        d["iterations"] = s.iterations; d["gap"] = s.gap; d["objective"] = s.objective; d["n_sv"] = s.n_sv; d["n_bsv"] = s.n_bsv;
-        d["converged"] = (bool)s.converged; d["form"] = s.form == 1 ? "workgroup" : "two-launch"; d["launches"] = s.launches;
-        d["ms"] = s.ms; d["kernel_type"] = kernel_type; d["class_weight"] = py::make_tuple(w.first, w.second);
+        py::dict d = info_dict(s, kernel_type);
+        d["class_weight"] = py::make_tuple(w.first, w.second);
         if (probability) {
             if (fold.ndim() != 1 || fold.shape(0) != labels.shape(0)) throw py::value_error("one fold id per label");
             {
@@ -716,8 +725,96 @@ public:
         if (refit) d["refit"] = fit_svm(labels, scores[(size_t)best].C, eps, max_iter, kernel_type, py::make_tuple(w.first, w.second), false, 5, 0);
         return d;
     }
+    // ---- epsilon-SVR on the resident triangle (fsk_svr_train): real-valued targets; the model takes the one model slot, so
+    // get_dual_coef_np (alpha - alpha*), get_intercept (-rho), decision_function_* and predict_* then speak of it, and
+    // predict_proba_np raises RuntimeError. Class weights do not apply to a regression.
+    py::dict fit_svr(py::array_t<double, py::array::c_style | py::array::forcecast> targets, double C, double epsilon, double eps, int64_t max_iter,
+                     const std::string& kernel_type) {
+        const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (targets.ndim() != 1) throw py::value_error("targets must be 1-D, one real number per training sequence");
+        check(fsk_svm_set_kernel(h_, kind));
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svr_train(h_, targets.data(), (int64_t)targets.shape(0), C, epsilon, eps, max_iter);
+        }
+        check(rc);
+        svr_ = true;
+        fsk_svm_info s;
+        check(fsk_svr_get_model(h_, nullptr, nullptr, nullptr, &s));
+        py::dict d = info_dict(s, kernel_type);
+        d["epsilon"] = epsilon;
+        return d;
+    }
+    // cross-validation of the SVR over folds and the grid Cs x epsilons, every problem side by side (fsk_svr_cv). folds: an int
+    // (fastsk_amd.kfold(n, folds, seed)) or an array of fold ids. best_C, best_epsilon: the grid point of the smallest
+    // out-of-fold mse, the lowest index (c n_eps + q) among equals; refit=True then trains fit_svr there.
+    py::dict cross_validate_svr(py::array_t<double, py::array::c_style | py::array::forcecast> targets,
+                                py::array_t<double, py::array::c_style | py::array::forcecast> Cs,
+                                py::array_t<double, py::array::c_style | py::array::forcecast> epsilons, py::object folds, uint64_t seed, double eps,
+                                int64_t max_iter, const std::string& kernel_type, bool refit) {
+        const int32_t kind = parse_kernel_type(kernel_type);
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (targets.ndim() != 1) throw py::value_error("targets must be 1-D, one real number per training sequence");
+        if (Cs.ndim() != 1 || epsilons.ndim() != 1) throw py::value_error("Cs and epsilons must be 1-D");
+        const int64_t n = (int64_t)targets.shape(0);
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
+        int32_t n_folds = 0;
+        if (py::isinstance<py::int_>(folds) && !py::isinstance<py::bool_>(folds)) {
+            n_folds = folds.cast<int32_t>();
+            fold = py::module_::import("fastsk_amd._native").attr("kfold")(n, folds, seed);
+        } else {
+            fold = folds.cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+            if (fold.ndim() != 1 || fold.shape(0) != targets.shape(0)) throw py::value_error("folds must be an int or one fold id per target");
+            for (py::ssize_t t = 0; t < fold.shape(0); ++t) n_folds = std::max(n_folds, fold.data()[t] + 1);
+        }
+        const int32_t n_C = (int32_t)Cs.shape(0), n_E = (int32_t)epsilons.shape(0);
+        check(fsk_svm_set_kernel(h_, kind));
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svr_cv(h_, targets.data(), n, fold.data(), n_folds, Cs.data(), n_C, epsilons.data(), n_E, eps, max_iter);
+        }
+        check(rc);
+        const int64_t nG = (int64_t)n_C * n_E;
+        py::array_t<double> oof({(py::ssize_t)n_C, (py::ssize_t)n_E, (py::ssize_t)n});
+        py::array_t<double> mse({(py::ssize_t)n_C, (py::ssize_t)n_E}), mae({(py::ssize_t)n_C, (py::ssize_t)n_E}), r2({(py::ssize_t)n_C, (py::ssize_t)n_E}),
+            r({(py::ssize_t)n_C, (py::ssize_t)n_E});
+        std::vector<fsk_svr_cv_score> scores((size_t)nG);
+        std::vector<fsk_svm_cv_problem> probs((size_t)(nG * n_folds));
+        fsk_svm_cv_info info;
+        check(fsk_svr_cv_get(h_, oof.mutable_data(), scores.data(), probs.data(), &info));
+        int64_t best = 0;
+        for (int64_t g = 0; g < nG; ++g) {
+            const fsk_svr_cv_score& x = scores[(size_t)g];
+            mse.mutable_data()[g] = x.mse; mae.mutable_data()[g] = x.mae; r2.mutable_data()[g] = x.r2; r.mutable_data()[g] = x.r;
+            if (x.mse < scores[(size_t)best].mse) best = g;  // (the lowest index among equals)
+        }
+        py::list problems;
+        for (const fsk_svm_cv_problem& q : probs) {
+            py::dict d;
+            d["n_rows"] = q.n_rows; d["iterations"] = q.iterations; d["converged"] = (bool)q.converged; d["gap"] = q.gap;
+            d["objective"] = q.objective; d["rho"] = q.rho; d["n_sv"] = q.n_sv; d["n_bsv"] = q.n_bsv; d["C"] = q.C;
+            d["epsilon"] = q.reserved[0]; d["fold"] = q.fold;
+            problems.append(d);
+        }
+        py::dict inf;
+        inf["form"] = info.form == 1 ? "workgroup" : "two-launch"; inf["launches"] = info.launches; inf["ms"] = info.ms;
+        inf["n"] = info.n; inf["n_folds"] = info.n_folds; inf["n_C"] = info.n_C; inf["n_eps"] = info.reserved0; inf["kernel_type"] = kernel_type;
+        py::dict d;
+        d["mse"] = mse; d["mae"] = mae; d["r2"] = r2; d["r"] = r; d["oof"] = oof; d["problems"] = problems; d["info"] = inf; d["fold"] = fold;
+        d["best_C"] = scores[(size_t)best].C; d["best_epsilon"] = scores[(size_t)best].epsilon;
+        if (refit) d["refit"] = fit_svr(targets, scores[(size_t)best].C, scores[(size_t)best].epsilon, eps, max_iter, kernel_type);
+        else d["refit"] = py::none();
+        return d;
+    }
     py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
         py::array_t<double> out((py::ssize_t)n_train_);
+        if (svr_) {  // (alpha - alpha*)
+            check(fsk_svr_get_model(h_, nullptr, out.mutable_data(), nullptr, nullptr));
+            return out;
+        }
         check(fsk_svm_get_model(h_, out.mutable_data(), nullptr, nullptr));
         if ((int64_t)labels_.size() != n_train_) throw std::runtime_error("no model: call fit_svm first");
         double* a = out.mutable_data();
@@ -726,7 +823,7 @@ public:
     }
     double get_intercept() const {  // -rho, as scikit-learn's intercept_
         double rho = 0;
-        check(fsk_svm_get_model(h_, nullptr, &rho, nullptr));
+        check(svr_ ? fsk_svr_get_model(h_, nullptr, nullptr, &rho, nullptr) : fsk_svm_get_model(h_, nullptr, &rho, nullptr));
         return -rho;
     }
     void decision_rows(const std::string& which, int64_t* r0, int64_t* r1) const {
@@ -756,7 +853,7 @@ public:
         decision_rows(which, &r0, &r1);
         if (r1 == r0) throw py::value_error("no rows");
         double rho = 0;
-        check(fsk_svm_get_model(h_, nullptr, &rho, nullptr));  // (RuntimeError before anything is allocated)
+        check(svr_ ? fsk_svr_get_model(h_, nullptr, nullptr, &rho, nullptr) : fsk_svm_get_model(h_, nullptr, &rho, nullptr));  // (RuntimeError before anything is allocated)
         double* dev = nullptr;
         check(fsk_alloc_block_device(h_, r0, r1, 0, 1, &dev));  // the engine's allocator: a column of r1 - r0 doubles
         const int rc = fsk_svm_decision_device(h_, r0, r1, dev);
@@ -843,6 +940,13 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("decision_function_np", &FastSK::decision_function_np, py::arg("which") = "test")
         .def("decision_function_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
         .def("predict_proba_np", &FastSK::predict_proba_np, py::arg("which") = "test")
+        .def("fit_svr", &FastSK::fit_svr, py::arg("targets"), py::arg("C") = 1.0, py::arg("epsilon") = 0.1, py::arg("eps") = 1e-3,
+             py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk")
+        .def("cross_validate_svr", &FastSK::cross_validate_svr, py::arg("targets"), py::arg("Cs") = std::vector<double>{1.0},
+             py::arg("epsilons") = std::vector<double>{0.1}, py::arg("folds") = 5, py::arg("seed") = 0, py::arg("eps") = 1e-3,
+             py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk", py::arg("refit") = false)
+        .def("predict_np", &FastSK::decision_function_np, py::arg("which") = "test")
+        .def("predict_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
         .def("stats", &FastSK::stats);
     // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
     m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {

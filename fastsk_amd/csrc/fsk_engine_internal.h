@@ -256,7 +256,11 @@ struct SvmCvState {
 struct SvmState {
     bool valid = false;
     SvmCvState cv;
-    std::vector<double> alpha;       // [n_train]
+    int model_kind = 0;              // of the one model slot: 0 a C-SVC (fsk_svm_train), 1 an epsilon-SVR (fsk_svr_train)
+    std::vector<double> alpha;       // [n_train]; of an SVR model [2 n_train]: alpha, then alpha*
+    std::vector<double> coef;        // SVR model: [n_train], alpha - alpha*
+    SvmCvState svr_cv;               // the result of the last fsk_svr_cv (problems (c n_eps + q) n_folds + f), valid as cv is
+    std::vector<fsk_svr_cv_score> svr_scores;   // [n_C n_eps]
     std::vector<signed char> y;      // [n_train], -1 / +1
     double rho = 0;
     int kernel = 0;                  // FSK_SVM_KERNEL_*: what fsk_svm_train / fsk_svm_cv solve on (fsk_svm_set_kernel)

@@ -1,6 +1,7 @@
 // fsk_engine_svm.hip — the SVM stage on the resident result triangle: fsk_svm_train, fsk_svm_get_model, fsk_svm_decision(_device),
 // fsk_svm_cv, fsk_svm_cv_get(_alpha), the class weights (fsk_svm_set_class_weights) and the Platt calibration
-// (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
+// (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba) and the epsilon-SVR (fsk_svr_train,
+// fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
 // (fastsk.cpp:239-530), for the sequences of one compute call and without the kernel matrix ever leaving the device: the
 // engine's consumer is an SVM, and the triangle it needs is 40 GB at 100,000 sequences.
 //
@@ -15,6 +16,11 @@
 // alpha, G (8 n each), y (n) and row i (8 n), and writes the kept row (8 n): 33 n. Launch A reads alpha, G, y, the kept row and
 // row j, and writes G: 41 n. 74 n at the least. A row is 8 i contiguous bytes and one cell of each of the n - i later triangle
 // rows, a 64-byte line each: a middle row (i = n / 2) moves 4 n + 32 n = 36 n instead of 8 n, so 74 n + 2 x 28 n = 130 n with lines.
+// The epsilon-SVR (fsk_svr_train: 2n elements on n rows, a thread owns both twins of a row): the bytes of KERNEL ROWS an iteration
+// are those of an n-row C-SVC solve, not of a 2n-row one — row i and row j once each, 16 n (72 n with lines), for the two twins
+// together. What doubles is the state: launch B reads alpha and G of 2n elements (32 n) and row i (8 n) and writes the kept row
+// (8 n): 48 n; launch A reads alpha, G (32 n), the kept row and row j (16 n) and writes G (16 n): 64 n. 112 n at the least (no y is
+// read: the sign is the half), 168 n with lines — against 148 n / 260 n for a C-SVC of 2n rows.
 #include "fsk_engine_internal.h"
 #include "fsk_kernels_svm.h"
 
@@ -165,6 +171,15 @@ int svm_check_problem(fsk_engine* e, const int32_t* labels, const char* null_tex
 
 int model_ready(fsk_engine* e) {
     if (!e->finalized || !e->svm.valid) return e->fail(FSK_ESTATE, "no model: call fsk_svm_train on a finalized result first");
+    return FSK_OK;
+}
+// The one model slot holds a C-SVC (fsk_svm_train) or an epsilon-SVR (fsk_svr_train): the calls that are one kind's alone
+constexpr int MODEL_SVC = 0, MODEL_SVR = 1;
+int model_of_kind(fsk_engine* e, int kind, const char* call) {
+    int rc = model_ready(e);
+    if (rc) return rc;
+    if (e->svm.model_kind != kind)
+        return e->fail(FSK_ESTATE, "%s: the model is %s", call, e->svm.model_kind == MODEL_SVR ? "an epsilon-SVR (fsk_svr_train)" : "a C-SVC (fsk_svm_train)");
     return FSK_OK;
 }
 
@@ -500,10 +515,298 @@ void platt_fit(const double* dec, const int32_t* labels, int64_t l, fsk_svm_plat
     out->status = status;
 }
 
-int calibration_ready(fsk_engine* e) {
-    int rc = model_ready(e);
+int calibration_ready(fsk_engine* e, const char* call) {
+    int rc = model_of_kind(e, MODEL_SVC, call);
     if (rc) return rc;
     if (!e->svm.cal.valid || !e->svm.platt_valid) return e->fail(FSK_ESTATE, "no calibration: call fsk_svm_calibrate on the model first");
+    return FSK_OK;
+}
+
+// ---- epsilon-SVR: the iteration over twin elements (fsk_kernels_svm.h) ---------------------------------------------------------
+// One problem of n rows, 2n elements, in the two forms of solve(): the form is chosen by the caller from 2n.
+template <typename SrcT>
+int solve_svr(fsk_engine* e, const SrcT* K, const double* diag, uint32_t n, double C, double eps, int64_t max_iter, int form, uint32_t chunk,
+              const SvmRecords& R, uint32_t n_wg, fsk::SvmRecB* status, int64_t* launches) {
+    double *alpha = e->svm.d_alpha.p, *G = e->svm.d_G.p, *krow = e->svm.d_krow.p;
+    if (form == 1) {
+        const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (n + 63u) & ~63u);
+        const size_t lds = fsk::svr_wg_lds(n, nt);
+        if (n > (uint32_t)fsk::SVR_WG_ROWS * nt || lds > 160 * 1024) return e->fail(FSK_EUNSUPPORTED, "k_svr_wg needs %zu bytes of LDS for %u rows", lds, n);
+        FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svr_wg<SrcT>, lds));
+        return svm_poll(e, R.rb, status, 1, [=] {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_wg<SrcT>), dim3(1), dim3(nt), lds, e->stream, K, diag, n, C, eps, (long long)max_iter, chunk, alpha, G,
+                       R.rb);
+            ++*launches;
+        });
+    }
+    return svm_poll(e, R.rb, status, 1, [=] {
+        for (uint32_t c = 0; c < chunk; ++c) {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_select_i<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, C, alpha, G,
+                       (const double*)krow, (const fsk::SvmRecB*)R.rb, R.ra, R.ci, (const fsk::SvmCandJ*)R.cj, n_wg);
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_select_j<SrcT>), dim3(n_wg), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag, n, C, eps,
+                       (long long)max_iter, (const double*)alpha, (const double*)G, krow, R.rb, (const fsk::SvmRecA*)R.ra,
+                       (const fsk::SvmCandI*)R.ci, R.cj, n_wg);
+            *launches += 2;
+        }
+    });
+}
+
+template <typename SrcT>
+int solve_svr_batch(fsk_engine* e, const SrcT* K, const double* diag, const SvmBatch& B, double eps, int64_t max_iter, int form, uint32_t chunk,
+                    fsk::SvmRecB* status, int64_t* launches) {
+    if (form == 1) {
+        const uint32_t nt = std::min<uint32_t>(fsk::SVM_WG_THREADS, (B.max_n + 63u) & ~63u);
+        const size_t lds = fsk::svr_wg_lds(B.max_n, nt);
+        if (B.max_n > (uint32_t)fsk::SVR_WG_ROWS * nt || lds > 160 * 1024)
+            return e->fail(FSK_EUNSUPPORTED, "k_svr_wg_batch needs %zu bytes of LDS for %u rows", lds, B.max_n);
+        FSK_HIP(fsk_hw::allow_dynamic_lds(fsk::k_svr_wg_batch<SrcT>, lds));
+        return svm_poll(e, B.rb, status, B.P, [=] {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_wg_batch<SrcT>), dim3(B.P), dim3(nt), lds, e->stream, K, diag, B.probs, B.idx, eps,
+                       (long long)max_iter, chunk, B.alpha, B.G, B.rb);
+            ++*launches;
+        });
+    }
+    return svm_poll(e, B.rb, status, B.P, [=] {
+        for (uint32_t c = 0; c < chunk; ++c) {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_select_i_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                       B.probs, B.idx, B.alpha, B.G, (const double*)B.krow, (const fsk::SvmRecB*)B.rb, B.ra, B.ci, (const fsk::SvmCandJ*)B.cj);
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svr_select_j_batch<SrcT>), dim3(B.max_wg, B.P), dim3(fsk::SVM_THREADS), 0, e->stream, K, diag,
+                       B.probs, B.idx, eps, (long long)max_iter, (const double*)B.alpha, (const double*)B.G, B.krow, B.rb,
+                       (const fsk::SvmRecA*)B.ra, (const fsk::SvmCandI*)B.ci, B.cj);
+            *launches += 2;
+        }
+    });
+}
+
+// The start of a solve: G = p, p_e = epsilon - z_e for e < n and p_{e+n} = epsilon + z_e, one rounding each (alpha = 0)
+void svr_start(const double* z, uint32_t n, double epsilon, double* p) {
+    for (uint32_t t = 0; t < n; ++t) { p[t] = epsilon - z[t]; p[n + t] = epsilon + z[t]; }
+}
+
+// The finish of a solve as LIBSVM's: calculate_rho over the 2n elements in element order (y = +1 below n, -1 from n on, one
+// box C), the objective 1/2 sum alpha_e (G_e + p_e) in element order, coef[t] = alpha_t - alpha*_t; n_sv counts coef != 0,
+// n_bsv |coef| >= C
+SvmFinish svr_finish(const double* alpha, const double* G, const double* p, uint32_t n, double C, double* coef) {
+    double ub = HUGE_VAL, lb = -HUGE_VAL, sum_free = 0.0, obj = 0.0;
+    int64_t n_free = 0, n_sv = 0, n_bsv = 0;
+    for (uint32_t e = 0; e < 2 * n; ++e) {
+        const bool up = e < n;
+        const double a = alpha[e], yG = up ? G[e] : -G[e];
+        if (a >= C) {
+            if (!up) ub = std::min(ub, yG); else lb = std::max(lb, yG);
+        } else if (a <= 0.0) {
+            if (up) ub = std::min(ub, yG); else lb = std::max(lb, yG);
+        } else {
+            ++n_free;
+            sum_free += yG;
+        }
+        obj += a * (G[e] + p[e]);
+    }
+    for (uint32_t t = 0; t < n; ++t) {
+        coef[t] = alpha[t] - alpha[n + t];
+        n_sv += coef[t] != 0.0;
+        n_bsv += std::fabs(coef[t]) >= C;
+    }
+    return {n_free > 0 ? sum_free / (double)n_free : (ub + lb) / 2.0, obj / 2.0, n_sv, n_bsv};
+}
+
+// what fsk_svr_train and fsk_svr_cv check alike
+int svr_check_problem(fsk_engine* e, const double* targets, const char* null_text, int64_t n, double eps) {
+    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
+    if (!targets) return e->fail(FSK_EINVAL, "%s", null_text);
+    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld targets for %lld training sequences", (long long)n, (long long)e->n_train);
+    if (n < 2) return e->fail(FSK_EINVAL, "%lld training sequences: a regression needs at least 2", (long long)n);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
+    for (int64_t t = 0; t < n; ++t)
+        if (!std::isfinite(targets[t])) return e->fail(FSK_EINVAL, "target %lld is not a finite number", (long long)t);
+    return FSK_OK;
+}
+
+// mse, mae, r2 and Pearson's r of one grid point: plain sums in row order (the order include/fastsk_amd.h states)
+void svr_metrics(const double* oof, const double* z, int64_t n, fsk_svr_cv_score* s) {
+    double sz = 0.0, so = 0.0;
+    for (int64_t t = 0; t < n; ++t) { sz += z[t]; so += oof[t]; }
+    const double zm = sz / (double)n, om = so / (double)n;
+    double sse = 0.0, sae = 0.0, sst = 0.0, soo = 0.0, szo = 0.0;
+    for (int64_t t = 0; t < n; ++t) {
+        const double d = oof[t] - z[t], dz = z[t] - zm, dq = oof[t] - om;
+        sse += d * d;
+        sae += std::fabs(d);
+        sst += dz * dz;
+        soo += dq * dq;
+        szo += dq * dz;
+    }
+    s->mse = sse / (double)n;
+    s->mae = sae / (double)n;
+    s->r2 = 1.0 - sse / sst;
+    s->r = szo / std::sqrt(soo * sst);
+}
+
+int svr_cv_ready(fsk_engine* e) {
+    if (!e->finalized || !e->svm.svr_cv.valid) return e->fail(FSK_ESTATE, "no cross-validation: call fsk_svr_cv on a finalized result first");
+    return FSK_OK;
+}
+
+// fsk_svr_cv: cv_run's plan with the grid (C, epsilon) — problem p = (c n_eps + q) n_folds + f, the folds' row lists shared,
+// a start of G and a box of its own each — on the twin-element batch kernels. A refused call leaves the earlier result.
+int svr_cv_run(fsk_engine* e, const double* z, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C, const double* epsilons,
+               int32_t n_eps, double eps, int64_t max_iter) {
+    const double t0 = now_ms();
+    SvmCvState& S = e->svm.svr_cv;
+    if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
+    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);
+    if (n_eps < 1) return e->fail(FSK_EINVAL, "n_eps is %d: at least one value of epsilon", n_eps);
+    { int rcc = svr_check_problem(e, fold && Cs && epsilons ? z : nullptr, "null targets, fold, Cs or epsilons", n, eps); if (rcc) return rcc; }
+    if ((int64_t)n_C * n_eps * n_folds > FSK_SVM_CV_MAX_PROBLEMS)
+        return e->fail(FSK_EINVAL, "%d folds x %d values of C x %d of epsilon are more than %d problems", n_folds, n_C, n_eps, FSK_SVM_CV_MAX_PROBLEMS);
+    for (int32_t c = 0; c < n_C; ++c)
+        if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
+    for (int32_t q = 0; q < n_eps; ++q)
+        if (!(epsilons[q] >= 0.0) || !std::isfinite(epsilons[q])) return e->fail(FSK_EINVAL, "epsilon %d must be a finite number >= 0", q);
+    const uint32_t F = (uint32_t)n_folds, nG = (uint32_t)(n_C * n_eps), P = F * nG, nn = (uint32_t)n;
+    std::vector<int64_t> rows(F, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
+        ++rows[fold[t]];
+    }
+    for (uint32_t f = 0; f < F; ++f) {
+        if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
+        if (n - rows[f] < 2) return e->fail(FSK_EINVAL, "fold %u leaves fewer than 2 training rows", f);
+    }
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
+
+    std::vector<uint32_t> idx;
+    std::vector<u64> fold_off(F), st_off(P), idx_off(P);
+    idx.reserve((size_t)(F - 1) * nn);
+    for (uint32_t f = 0; f < F; ++f) {
+        fold_off[f] = idx.size();
+        for (uint32_t t = 0; t < nn; ++t)
+            if ((uint32_t)fold[t] != f) idx.push_back(t);
+    }
+    std::vector<fsk::SvmProb> probs(P);
+    uint32_t max_n = 0, total_wg = 0;
+    u64 total = 0;  // elements: 2 n_p a problem
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t f = p % F, np = (uint32_t)(n - rows[f]);
+        probs[p].Cp = probs[p].Cn = Cs[p / F / (uint32_t)n_eps];
+        probs[p].idx_off = idx_off[p] = fold_off[f];
+        probs[p].st_off = st_off[p] = total;
+        probs[p].n = np;
+        probs[p].wg_off = total_wg;
+        total += 2 * (u64)np;
+        total_wg += (np + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
+        max_n = std::max(max_n, np);
+    }
+    const int form = 2 * (int64_t)max_n <= e->tune.svm_wg_max ? 1 : 2;
+    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
+
+    const size_t rec_bytes = svm_batch_record_bytes(P, total_wg);
+    FSK_HIP(S.d_alpha.reserve(total));
+    FSK_HIP(S.d_G.reserve(total));
+    if (form == 2) FSK_HIP(S.d_krow.reserve(total / 2));
+    FSK_HIP(S.d_idx.reserve(idx.size()));
+    FSK_HIP(S.d_prob.reserve((size_t)P * sizeof(fsk::SvmProb)));
+    FSK_HIP(S.d_rec.reserve(rec_bytes));
+    FSK_HIP(S.d_coef.reserve((size_t)P * nn));
+    FSK_HIP(S.d_rho.reserve(P));
+    FSK_HIP(S.d_fold.reserve(nn));
+    FSK_HIP(S.d_oof.reserve((size_t)nG * nn));
+    S.valid = false;  // (from here on the earlier result's buffers are written)
+
+    SvmBatch B;
+    B.P = P; B.max_n = max_n; B.max_wg = (max_n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS; B.total_wg = total_wg;
+    B.probs = reinterpret_cast<const fsk::SvmProb*>(S.d_prob.p);
+    B.idx = S.d_idx.p; B.y = nullptr; B.alpha = S.d_alpha.p; B.G = S.d_G.p; B.krow = S.d_krow.p;
+    B.rb = reinterpret_cast<fsk::SvmRecB*>(S.d_rec.p);
+    B.ra = reinterpret_cast<fsk::SvmRecA*>(B.rb + P);
+    B.ci = reinterpret_cast<fsk::SvmCandI*>(B.ra + P);
+    B.cj = reinterpret_cast<fsk::SvmCandJ*>(B.ci + total_wg);
+
+    // every problem's start of G: p of its rows' targets at its epsilon
+    std::vector<double> pvec(total), G(total), zp;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t np = probs[p].n;
+        zp.resize(np);
+        for (uint32_t q = 0; q < np; ++q) zp[q] = z[idx[idx_off[p] + q]];
+        svr_start(zp.data(), np, epsilons[(p / F) % (uint32_t)n_eps], pvec.data() + st_off[p]);
+    }
+    FSK_HIP(hipMemcpyAsync(S.d_prob.p, probs.data(), (size_t)P * sizeof(fsk::SvmProb), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_G.p, pvec.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_alpha.p, 0, total * sizeof(double), e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_rec.p, 0, rec_bytes, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+
+    std::vector<fsk::SvmRecB> status(P);
+    int64_t launches = 0;
+    const int rc = svm_on_source(src, [&](auto* K) { return solve_svr_batch(e, K, src.diag, B, eps, max_iter, form, chunk, status.data(), &launches); });
+    if (rc) return rc;
+    S.alpha.resize(total);
+    FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+
+    std::vector<double> coef((size_t)P * nn, 0.0), rho(P), part;
+    S.problems.assign(P, fsk_svm_cv_problem{});
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t np = probs[p].n;
+        part.resize(np);
+        const SvmFinish fin = svr_finish(S.alpha.data() + st_off[p], G.data() + st_off[p], pvec.data() + st_off[p], np, probs[p].Cp, part.data());
+        for (uint32_t q = 0; q < np; ++q) coef[(size_t)p * nn + idx[idx_off[p] + q]] = part[q];
+        rho[p] = fin.rho;
+        fsk_svm_cv_problem& o = S.problems[p];
+        o.n_rows = np;
+        o.iterations = status[p].iter;
+        o.gap = status[p].gmax - status[p].gmin;
+        o.objective = fin.objective;
+        o.rho = fin.rho;
+        o.C = probs[p].Cp;
+        o.reserved[0] = epsilons[(p / F) % (uint32_t)n_eps];
+        o.n_sv = fin.n_sv;
+        o.n_bsv = fin.n_bsv;
+        o.converged = status[p].converged;
+        o.fold = (int32_t)(p % F);
+    }
+    FSK_HIP(hipMemcpyAsync(S.d_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(S.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    {
+        const dim3 grid((nn + 3) / 4, nG);  // (one grid point a blockIdx.y)
+        const double *diag = src.diag, *dc = S.d_coef.p, *dr = S.d_rho.p;
+        const int32_t* df = S.d_fold.p;
+        double* out = S.d_oof.p;
+        svm_on_source(src, [=](auto* K) -> int {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_decision_oof<SrcOf<decltype(K)>>), grid, dim3(256), 0, e->stream, K, diag, dc, dr, df, F, nn, out);
+            return FSK_OK;
+        });
+    }
+    S.oof.resize((size_t)nG * nn);
+    FSK_HIP(hipMemcpyAsync(S.oof.data(), S.d_oof.p, S.oof.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+    e->svm.svr_scores.assign(nG, fsk_svr_cv_score{});
+    for (uint32_t g = 0; g < nG; ++g) {
+        fsk_svr_cv_score& s = e->svm.svr_scores[g];
+        s.C = Cs[g / (uint32_t)n_eps];
+        s.epsilon = epsilons[g % (uint32_t)n_eps];
+        svr_metrics(S.oof.data() + (size_t)g * nn, z, n, &s);
+    }
+    S.idx.swap(idx);
+    S.st_off.swap(st_off);
+    S.idx_off.swap(idx_off);
+    S.info = fsk_svm_cv_info{};
+    S.info.n = n;
+    S.info.n_folds = n_folds;
+    S.info.n_C = n_C;
+    S.info.reserved0 = n_eps;
+    S.info.form = form;
+    S.info.launches = launches;
+    S.info.ms = now_ms() - t0;
+    S.valid = true;
     return FSK_OK;
 }
 
@@ -574,13 +877,14 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
     S.info.form = form;
     S.info.launches = launches;
     S.info.ms = now_ms() - t0;
+    S.model_kind = MODEL_SVC;
     S.valid = true;
     return FSK_OK;
 }
 
 int fsk_svm_get_model(fsk_engine* e, double* alpha, double* rho, fsk_svm_info* info) {
     if (!e) return FSK_EINVAL;
-    int rc = model_ready(e);
+    int rc = model_of_kind(e, MODEL_SVC, "fsk_svm_get_model");
     if (rc) return rc;
     if (alpha) memcpy(alpha, e->svm.alpha.data(), e->svm.alpha.size() * sizeof(double));
     if (rho) *rho = e->svm.rho;
@@ -672,7 +976,7 @@ int fsk_svm_platt_fit(const double* dec, const int32_t* labels, int64_t n, fsk_s
 int fsk_svm_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds) {
     if (!e) return FSK_EINVAL;
     const double t0 = now_ms();
-    int rc = model_ready(e);
+    int rc = model_of_kind(e, MODEL_SVC, "fsk_svm_calibrate");
     if (rc) return rc;
     SvmState& S = e->svm;
     const std::vector<int32_t> labels(S.y.begin(), S.y.end());
@@ -691,7 +995,7 @@ int fsk_svm_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds) {
 
 int fsk_svm_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* out) {
     if (!e) return FSK_EINVAL;
-    int rc = calibration_ready(e);
+    int rc = calibration_ready(e, "fsk_svm_get_calibration");
     if (rc) return rc;
     if (oof) memcpy(oof, e->svm.cal.oof.data(), e->svm.cal.oof.size() * sizeof(double));
     if (out) *out = e->svm.platt;
@@ -700,11 +1004,103 @@ int fsk_svm_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* out)
 
 int fsk_svm_proba(fsk_engine* e, int64_t r0, int64_t r1, double* out) {
     if (!e) return FSK_EINVAL;
-    int rc = calibration_ready(e);
+    int rc = calibration_ready(e, "fsk_svm_proba");
     if (rc) return rc;
     rc = fsk_svm_decision(e, r0, r1, out);
     if (rc) return rc;
     for (int64_t r = 0; r < r1 - r0; ++r) out[r] = platt_predict(out[r], e->svm.platt.A, e->svm.platt.B);
+    return FSK_OK;
+}
+
+int fsk_svr_train(fsk_engine* e, const double* targets, int64_t n, double C, double epsilon, double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    { int rcc = svr_check_problem(e, targets, "null targets", n, eps); if (rcc) return rcc; }
+    if (!(C > 0.0) || !std::isfinite(C)) return e->fail(FSK_EINVAL, "C must be a positive finite number");
+    if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return e->fail(FSK_EINVAL, "epsilon must be a finite number >= 0");
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
+
+    SvmState& S = e->svm;
+    S.valid = false;
+    S.cal.valid = S.platt_valid = false;  // (the calibration belonged to the model this one replaces)
+    const uint32_t nn = (uint32_t)n, m = 2 * nn;
+    const int form = (int64_t)m <= e->tune.svm_wg_max ? 1 : 2;  // (the 2n elements against the workgroup's ceiling)
+    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
+    const uint32_t n_wg = (nn + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
+    FSK_HIP(S.d_alpha.reserve(m));
+    FSK_HIP(S.d_G.reserve(m));
+    FSK_HIP(S.d_krow.reserve(nn));
+    FSK_HIP(S.d_coef.reserve(nn));
+    FSK_HIP(S.d_rec.reserve(svm_record_bytes(n_wg)));
+    const SvmRecords R = svm_records(S.d_rec.p, n_wg);
+
+    std::vector<double> p(m), G(m);
+    svr_start(targets, nn, epsilon, p.data());
+    S.alpha.assign(m, 0.0);
+    FSK_HIP(hipMemcpyAsync(S.d_G.p, p.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_alpha.p, 0, (size_t)m * sizeof(double), e->stream));
+    FSK_HIP(hipMemsetAsync(S.d_rec.p, 0, svm_record_bytes(n_wg), e->stream));  // iter = 0, nothing pending, not done
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+
+    fsk::SvmRecB status{};
+    int64_t launches = 0;
+    const int rc = svm_on_source(src, [&](auto* K) { return solve_svr(e, K, src.diag, nn, C, eps, max_iter, form, chunk, R, n_wg, &status, &launches); });
+    if (rc) return rc;
+    FSK_HIP(hipMemcpyAsync(S.alpha.data(), S.d_alpha.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipMemcpyAsync(G.data(), S.d_G.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+
+    S.coef.resize(nn);
+    const SvmFinish fin = svr_finish(S.alpha.data(), G.data(), p.data(), nn, C, S.coef.data());
+    S.rho = fin.rho;
+    S.C = C; S.eps = eps; S.max_iter = max_iter;
+    FSK_HIP(hipMemcpyAsync(S.d_coef.p, S.coef.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    S.info = fsk_svm_info{};
+    S.info.iterations = status.iter;
+    S.info.gap = status.gmax - status.gmin;
+    S.info.objective = fin.objective;
+    S.info.n_sv = fin.n_sv;
+    S.info.n_bsv = fin.n_bsv;
+    S.info.converged = status.converged;
+    S.info.form = form;
+    S.info.launches = launches;
+    S.info.ms = now_ms() - t0;
+    S.model_kind = MODEL_SVR;
+    S.valid = true;
+    return FSK_OK;
+}
+
+int fsk_svr_get_model(fsk_engine* e, double* alpha2, double* coef, double* rho, fsk_svm_info* info) {
+    if (!e) return FSK_EINVAL;
+    int rc = model_of_kind(e, MODEL_SVR, "fsk_svr_get_model");
+    if (rc) return rc;
+    if (alpha2) memcpy(alpha2, e->svm.alpha.data(), e->svm.alpha.size() * sizeof(double));
+    if (coef) memcpy(coef, e->svm.coef.data(), e->svm.coef.size() * sizeof(double));
+    if (rho) *rho = e->svm.rho;
+    if (info) *info = e->svm.info;
+    return FSK_OK;
+}
+
+int fsk_svr_cv(fsk_engine* e, const double* targets, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+               const double* epsilons, int32_t n_eps, double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    return svr_cv_run(e, targets, n, fold, n_folds, Cs, n_C, epsilons, n_eps, eps, max_iter);
+}
+
+int fsk_svr_cv_get(fsk_engine* e, double* oof, fsk_svr_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info) {
+    if (!e) return FSK_EINVAL;
+    int rc = svr_cv_ready(e);
+    if (rc) return rc;
+    const SvmCvState& S = e->svm.svr_cv;
+    if (oof) memcpy(oof, S.oof.data(), S.oof.size() * sizeof(double));
+    if (scores) memcpy(scores, e->svm.svr_scores.data(), e->svm.svr_scores.size() * sizeof(fsk_svr_cv_score));
+    if (problems) memcpy(problems, S.problems.data(), S.problems.size() * sizeof(fsk_svm_cv_problem));
+    if (info) *info = S.info;
     return FSK_OK;
 }
 

@@ -1,5 +1,6 @@
 // fsk_kernels_svm.h — a C-SVC dual solver and its decision values on the RESIDENT result triangle (fsk_svm_train,
-// fsk_svm_decision). Included by fsk_engine_svm.hip only.
+// fsk_svm_decision), and the same solver over the twin elements of an epsilon-SVR (fsk_svr_train, fsk_svr_cv: the last
+// section). Included by fsk_engine_svm.hip only.
 //
 // The kernel is cosine-normalised: every K(t,t) is 1, the whole matrix is on the device, so the solver is SMO with LIBSVM's
 // second-order working-set selection and nothing else — no row cache, no shrinking. A row of Q is read where it lies: cells
@@ -543,6 +544,303 @@ __global__ __launch_bounds__(256) void k_svm_decision_oof(const SrcT* K, const d
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
     if (live && lane == 0) out[(size_t)blockIdx.y * n_train + t] = __dsub_rn(acc, rho[p]);
+}
+
+// =============================================================================================
+// EPSILON-SVR: THE ITERATION OVER TWIN ELEMENTS (fsk_svr_train, fsk_svr_cv). LIBSVM solves the regression with the same
+// Solver over 2n variables: element e < n is alpha_e with y = +1, element e + n is alpha*_e with y = -1, both stand for
+// kernel row e (rows(e) in a batch), Q(e, f) = y_e y_f K(e mod n, f mod n), one box C for all, alpha = 0 and G = p at the
+// start (the host forms p). Steps 1-4 and their functions are the ones above with Cp = Cn = C; ties go to the lowest element
+// in [0, 2n). What is written here is the mapping: a thread owns BOTH twins of a row, so a cell svm_cell(K, diag, ri, r)
+// read in step 2 serves the element and its twin and is kept for step 4 of both, and so is row j's — the kernel rows an
+// iteration reads are those of an n-row C-SVC solve, not of a 2n-row one. The sign follows from the half: no y is loaded.
+// The kernels are instantiations of their own; the C-SVC kernels above carry no "regression or not".
+constexpr int SVR_WG_ROWS = 4;           // k_svr_wg: rows a thread at most (4096 rows = 8192 elements = svm_wg_max's ceiling)
+
+// LDS of k_svr_wg for n rows and nt threads: alpha and G of the 2n elements (16 bytes an element: 147,968 bytes at 4096 rows
+// and 1024 threads, below svm_wg_lds(8192, 1024))
+__host__ __device__ inline size_t svr_wg_lds(uint32_t n, uint32_t nt) {
+    const size_t m8 = (2 * (size_t)n + 7) & ~(size_t)7;
+    return m8 * 16 + (size_t)nt * 16 + (size_t)SVM_PART * 16;
+}
+
+// steps 1 and 2 for the two elements of one row: the better candidate of the pair into the thread's running one
+__device__ __forceinline__ void svr_pair_i(uint32_t r, uint32_t n, double C, double a_up, double g_up, double a_dn, double g_dn, double* vmax,
+                                           int* imax, double* vmin) {
+    const double vu = svm_v(1, g_up), vd = svm_v(-1, g_dn);
+    if (svm_in_up(1, a_up, C) && svm_better_max(vu, (int)r, *vmax, *imax)) { *vmax = vu; *imax = (int)r; }
+    if (svm_in_up(-1, a_dn, C) && svm_better_max(vd, (int)(r + n), *vmax, *imax)) { *vmax = vd; *imax = (int)(r + n); }
+    if (svm_in_low(1, a_up, C) && vu < *vmin) *vmin = vu;
+    if (svm_in_low(-1, a_dn, C) && vd < *vmin) *vmin = vd;
+}
+__device__ __forceinline__ void svr_pair_j(uint32_t r, uint32_t n, double C, double gmax, double kit, double a_up, double g_up, double a_dn,
+                                           double g_dn, double* obj, int* j) {
+    double o;
+    if (svm_in_low(1, a_up, C) && svm_j_objective(gmax, svm_v(1, g_up), kit, &o) && svm_better_min(o, (int)r, *obj, *j)) { *obj = o; *j = (int)r; }
+    if (svm_in_low(-1, a_dn, C) && svm_j_objective(gmax, svm_v(-1, g_dn), kit, &o) && svm_better_min(o, (int)(r + n), *obj, *j)) { *obj = o; *j = (int)(r + n); }
+}
+
+// ONE WORKGROUP (2n <= svm_wg_max): alpha and G of the 2n elements in LDS, element e at [e]. Thread tid owns rows
+// tid + q blockDim.x, q < 4, and both elements of each; it alone writes their alpha and G. Barriers as in svm_wg_iterations.
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svr_wg_iterations(unsigned char* smem, const SrcT* K, const double* diag, const Rows rows, uint32_t n, double C,
+                                                  double eps, long long max_iter, uint32_t chunk, double* alpha, double* G, SvmRecB* rec) {
+    const uint32_t tid = threadIdx.x, nt = blockDim.x, m = 2 * n;
+    const size_t m8 = ((size_t)m + 7) & ~(size_t)7;
+    double* sA = reinterpret_cast<double*>(smem);
+    double* sG = sA + m8;
+    SvmRed red;
+    red.v = sG + m8;
+    red.pv = red.v + nt;
+    red.i = reinterpret_cast<int*>(red.pv + SVM_PART);
+    red.w = red.i + nt;
+    red.pi = red.w + nt;
+    red.pw = red.pi + SVM_PART;
+
+    for (uint32_t e = tid; e < m; e += nt) { sA[e] = alpha[e]; sG[e] = G[e]; }
+    long long iter = rec->iter;
+    double gmax = rec->gmax, gmin = rec->gmin;
+    int done = 0, converged = 0;
+    __syncthreads();
+
+    for (uint32_t c = 0; c < chunk; ++c) {
+        // ---- 1. i, Gmax, Gmin
+        double vmax = -svm_inf(), vmin = svm_inf();
+        int imax = SVM_NONE, none = 0;
+        for (uint32_t r = tid; r < n; r += nt) svr_pair_i(r, n, C, sA[r], sG[r], sA[r + n], sG[r + n], &vmax, &imax, &vmin);
+        svm_reduce<true>(red, &vmax, &imax, &none);
+        int at = 0;
+        svm_reduce<false>(red, &vmin, &at, &none);
+        gmax = vmax; gmin = vmin;
+        if (__dsub_rn(gmax, gmin) <= eps) { done = 1; converged = 1; break; }
+        if (iter >= max_iter) { done = 1; break; }
+        const uint32_t i = (uint32_t)imax, ri = rows(i < n ? i : i - n);
+        // ---- 2. j (one cell a row for both twins, kept with the row's number for step 4)
+        double kit[SVR_WG_ROWS];
+        uint32_t row[SVR_WG_ROWS];
+        double obj = svm_inf();
+        int j = SVM_NONE;
+#pragma unroll
+        for (int q = 0; q < SVR_WG_ROWS; ++q) {
+            const uint32_t r = tid + (uint32_t)q * nt;
+            kit[q] = 0.0;
+            if constexpr (Rows::KEPT) row[q] = 0;
+            if (r < n) {
+                const uint32_t rr = rows(r);
+                if constexpr (Rows::KEPT) row[q] = rr;
+                kit[q] = svm_cell(K, diag, ri, rr);
+                svr_pair_j(r, n, C, gmax, kit[q], sA[r], sG[r], sA[r + n], sG[r + n], &obj, &j);
+            }
+        }
+        svm_reduce<false>(red, &obj, &j, &none);
+        if (j == SVM_NONE) { done = 1; break; }  // (as in svm_wg_iterations: cells that are not numbers)
+        // ---- 3. the step, by every thread alike
+        const uint32_t rj = rows((uint32_t)j < n ? (uint32_t)j : (uint32_t)j - n);
+        const int yi = i < n ? 1 : -1, yj = (uint32_t)j < n ? 1 : -1;
+        const double ai0 = sA[i], aj0 = sA[j], Gi = sG[i], Gj = sG[j];
+        double ai = ai0, aj = aj0;
+        svm_step(yi, yj, svm_cell(K, diag, ri, rj), Gi, Gj, C, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, ai0), daj = __dsub_rn(aj, aj0);
+        __syncthreads();  // (everybody has read alpha and G of i and j)
+        // ---- 4. G of both twins from the two cells of the row, alpha
+#pragma unroll
+        for (int q = 0; q < SVR_WG_ROWS; ++q) {
+            const uint32_t r = tid + (uint32_t)q * nt;
+            if (r < n) {
+                uint32_t rr = r;
+                if constexpr (Rows::KEPT) rr = row[q];
+                const double kjt = svm_cell(K, diag, rj, rr);
+                sG[r] = svm_new_G(sG[r], 1, yi, yj, kit[q], kjt, dai, daj);
+                sG[r + n] = svm_new_G(sG[r + n], -1, yi, yj, kit[q], kjt, dai, daj);
+                if (r == i) sA[r] = ai;
+                if (r + n == i) sA[r + n] = ai;
+                if (r == (uint32_t)j) sA[r] = aj;
+                if (r + n == (uint32_t)j) sA[r + n] = aj;
+            }
+        }
+        ++iter;
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < m; e += nt) { alpha[e] = sA[e]; G[e] = sG[e]; }
+    if (tid == 0) {
+        rec->iter = iter; rec->gmax = gmax; rec->gmin = gmin;
+        rec->done = done; rec->converged = converged; rec->pending = 0;
+    }
+}
+
+// TWO LAUNCHES AN ITERATION: one ROW a thread, both twins; alpha and G have 2n entries, the kept row n; the candidate slots
+// stay one a workgroup (n_wg = ceil(n / 256)): a thread hands in the better of its two elements. Records as above, i and j
+// element numbers in [0, 2n).
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svr_select_i(const SrcT* K, const double* diag, const Rows rows, uint32_t n, double C, double* alpha, double* G,
+                                             const double* krow, const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i, const SvmCandJ* cand_j,
+                                             uint32_t n_wg) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (rb->done) {
+        if (blockIdx.x == 0 && tid == 0) { ra->iter = rb->iter; ra->done = 1; }
+        return;
+    }
+    long long iter = rb->iter;
+    const bool mine = t < n;
+    double a_up = mine ? alpha[t] : 0.0, g_up = mine ? G[t] : 0.0, a_dn = mine ? alpha[t + n] : 0.0, g_dn = mine ? G[t + n] : 0.0;
+    if (rb->pending) {
+        double obj = svm_inf();
+        int j = SVM_NONE, w = 0;
+        for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+            const double o = cand_j[q].obj;
+            const int oj = cand_j[q].j;
+            if (svm_better_min(o, oj, obj, j)) { obj = o; j = oj; w = (int)q; }
+        }
+        svm_reduce<false>(red, &obj, &j, &w);
+        if (j == SVM_NONE) {
+            if (blockIdx.x == 0 && tid == 0) { ra->iter = iter; ra->done = 2; }
+            return;
+        }
+        const SvmCandJ cj = cand_j[w];
+        const int i = rb->i, yi = rb->yi;
+        double ai = rb->ai, aj = cj.aj;
+        svm_step(yi, cj.yj, cj.Kij, rb->Gi, cj.Gj, C, C, &ai, &aj);
+        const double dai = __dsub_rn(ai, rb->ai), daj = __dsub_rn(aj, cj.aj);
+        if (mine) {
+            const uint32_t rj = rows((uint32_t)j < n ? (uint32_t)j : (uint32_t)j - n);
+            const double kit = krow[t], kjt = svm_cell(K, diag, rj, rows(t));
+            g_up = svm_new_G(g_up, 1, yi, cj.yj, kit, kjt, dai, daj);
+            g_dn = svm_new_G(g_dn, -1, yi, cj.yj, kit, kjt, dai, daj);
+            G[t] = g_up;
+            G[t + n] = g_dn;
+            if (t == (uint32_t)i) { a_up = ai; alpha[t] = ai; }
+            if (t + n == (uint32_t)i) { a_dn = ai; alpha[t + n] = ai; }
+            if (t == (uint32_t)j) { a_up = aj; alpha[t] = aj; }
+            if (t + n == (uint32_t)j) { a_dn = aj; alpha[t + n] = aj; }
+        }
+        ++iter;
+    }
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    if (mine) svr_pair_i(t, n, C, a_up, g_up, a_dn, g_dn, &vmax, &imax, &vmin);
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    if (tid == 0) {
+        cand_i[blockIdx.x].vmax = vmax; cand_i[blockIdx.x].vmin = vmin; cand_i[blockIdx.x].imax = imax;
+        if (blockIdx.x == 0) { ra->iter = iter; ra->done = 0; }
+    }
+}
+
+template <typename SrcT, typename Rows>
+__device__ __forceinline__ void svr_select_j(const SrcT* K, const double* diag, const Rows rows, uint32_t n, double C, double eps, long long max_iter,
+                                             const double* alpha, const double* G, double* krow, SvmRecB* rb, const SvmRecA* ra,
+                                             const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
+    __shared__ double s_v[SVM_THREADS], s_pv[SVM_PART];
+    __shared__ int s_i[SVM_THREADS], s_w[SVM_THREADS], s_pi[SVM_PART], s_pw[SVM_PART];
+    const SvmRed red{s_v, s_i, s_w, s_pv, s_pi, s_pw};
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * SVM_THREADS + tid;
+    if (ra->done) {
+        if (ra->done == 2 && blockIdx.x == 0 && tid == 0) { rb->iter = ra->iter; rb->done = 1; rb->converged = 0; rb->pending = 0; }
+        return;
+    }
+    const long long iter = ra->iter;
+    double vmax = -svm_inf(), vmin = svm_inf();
+    int imax = SVM_NONE, none = 0, at = 0;
+    for (uint32_t q = tid; q < n_wg; q += SVM_THREADS) {
+        const double x = cand_i[q].vmax, m = cand_i[q].vmin;
+        const int xi = cand_i[q].imax;
+        if (svm_better_max(x, xi, vmax, imax)) { vmax = x; imax = xi; }
+        if (m < vmin) vmin = m;
+    }
+    svm_reduce<true>(red, &vmax, &imax, &none);
+    svm_reduce<false>(red, &vmin, &at, &none);
+    const bool converged = __dsub_rn(vmax, vmin) <= eps;
+    if (converged || iter >= max_iter) {
+        if (blockIdx.x == 0 && tid == 0) {
+            rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+            rb->done = 1; rb->converged = converged ? 1 : 0; rb->pending = 0;
+        }
+        return;
+    }
+    const uint32_t i = (uint32_t)imax;
+    double obj = svm_inf(), kit = 0.0, a_up = 0.0, g_up = 0.0, a_dn = 0.0, g_dn = 0.0;
+    int j = SVM_NONE;
+    if (t < n) {
+        kit = svm_cell(K, diag, rows(i < n ? i : i - n), rows(t));
+        krow[t] = kit;
+        a_up = alpha[t]; g_up = G[t]; a_dn = alpha[t + n]; g_dn = G[t + n];
+        svr_pair_j(t, n, C, vmax, kit, a_up, g_up, a_dn, g_dn, &obj, &j);
+    }
+    const int mine_j = j;  // (this thread's better element, before the reduction)
+    svm_reduce<false>(red, &obj, &j, &none);
+    if (j == SVM_NONE) {
+        if (tid == 0) { cand_j[blockIdx.x].obj = svm_inf(); cand_j[blockIdx.x].j = SVM_NONE; }
+    } else if (mine_j == j) {
+        const bool up = (uint32_t)j < n;
+        SvmCandJ c;
+        c.obj = obj; c.aj = up ? a_up : a_dn; c.Gj = up ? g_up : g_dn; c.Kij = kit; c.j = j; c.yj = up ? 1 : -1;
+        cand_j[blockIdx.x] = c;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        rb->iter = iter; rb->gmax = vmax; rb->gmin = vmin;
+        rb->ai = alpha[i]; rb->Gi = G[i]; rb->i = (int)i; rb->yi = i < n ? 1 : -1;
+        rb->done = 0; rb->converged = 0; rb->pending = 1;
+    }
+}
+
+// the single solve: the whole training set
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svr_wg(const SrcT* K, const double* diag, uint32_t n, double C, double eps, long long max_iter,
+                                                           uint32_t chunk, double* alpha, double* G, SvmRecB* rec) {
+    FSK_DYN_SHARED(unsigned char, smem);
+    svr_wg_iterations(smem, K, diag, SvmRowsAll{}, n, C, eps, max_iter, chunk, alpha, G, rec);
+}
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svr_select_i(const SrcT* K, const double* diag, uint32_t n, double C, double* alpha, double* G,
+                                                              const double* krow, const SvmRecB* rb, SvmRecA* ra, SvmCandI* cand_i,
+                                                              const SvmCandJ* cand_j, uint32_t n_wg) {
+    svr_select_i(K, diag, SvmRowsAll{}, n, C, alpha, G, krow, rb, ra, cand_i, cand_j, n_wg);
+}
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svr_select_j(const SrcT* K, const double* diag, uint32_t n, double C, double eps, long long max_iter,
+                                                              const double* alpha, const double* G, double* krow, SvmRecB* rb,
+                                                              const SvmRecA* ra, const SvmCandI* cand_i, SvmCandJ* cand_j, uint32_t n_wg) {
+    svr_select_j(K, diag, SvmRowsAll{}, n, C, eps, max_iter, alpha, G, krow, rb, ra, cand_i, cand_j, n_wg);
+}
+
+// the batch (fsk_svr_cv): SvmProb with n ROWS, Cp the box, st_off the start of the problem's 2n alpha and G (its kept row
+// starts at st_off / 2), wg_off the first of its ceil(n / 256) candidate slots. Grids and early returns as in the C-SVC batch.
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_WG_THREADS) void k_svr_wg_batch(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                                                 double eps, long long max_iter, uint32_t chunk, double* alpha_all,
+                                                                 double* G_all, SvmRecB* recs) {
+    FSK_DYN_SHARED(unsigned char, smem);
+    SvmRecB* rec = recs + blockIdx.x;
+    if (rec->done) return;
+    const SvmProb pr = probs[blockIdx.x];
+    svr_wg_iterations(smem, K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, eps, max_iter, chunk, alpha_all + pr.st_off, G_all + pr.st_off,
+                      rec);
+}
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svr_select_i_batch(const SrcT* K, const double* diag, const SvmProb* probs,
+                                                                    const uint32_t* idx_all, double* alpha_all, double* G_all,
+                                                                    const double* krow_all, const SvmRecB* rbs, SvmRecA* ras,
+                                                                    SvmCandI* cand_i_all, const SvmCandJ* cand_j_all) {
+    const SvmProb pr = probs[blockIdx.y];
+    const uint32_t n_wg = (pr.n + SVM_THREADS - 1) / SVM_THREADS;
+    if (blockIdx.x >= n_wg) return;
+    svr_select_i(K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, alpha_all + pr.st_off, G_all + pr.st_off, krow_all + pr.st_off / 2,
+                 rbs + blockIdx.y, ras + blockIdx.y, cand_i_all + pr.wg_off, cand_j_all + pr.wg_off, n_wg);
+}
+template <typename SrcT>
+__global__ __launch_bounds__(SVM_THREADS) void k_svr_select_j_batch(const SrcT* K, const double* diag, const SvmProb* probs,
+                                                                    const uint32_t* idx_all, double eps, long long max_iter,
+                                                                    const double* alpha_all, const double* G_all, double* krow_all,
+                                                                    SvmRecB* rbs, const SvmRecA* ras, const SvmCandI* cand_i_all,
+                                                                    SvmCandJ* cand_j_all) {
+    const SvmProb pr = probs[blockIdx.y];
+    const uint32_t n_wg = (pr.n + SVM_THREADS - 1) / SVM_THREADS;
+    if (blockIdx.x >= n_wg) return;
+    svr_select_j(K, diag, SvmRowsList{idx_all + pr.idx_off}, pr.n, pr.Cp, eps, max_iter, alpha_all + pr.st_off, G_all + pr.st_off,
+                 krow_all + pr.st_off / 2, rbs + blockIdx.y, ras + blockIdx.y, cand_i_all + pr.wg_off, cand_j_all + pr.wg_off, n_wg);
 }
 
 }  // namespace fsk

@@ -40,7 +40,8 @@ extern "C" {
                                   fsk_rows_build, fsk_rows_get_block(_device), fsk_rows_get_info and fsk_rows_info,
                                   fsk_svm_set_kernel / fsk_svm_get_kernel;
                                   fsk_svm_set_class_weights / fsk_svm_get_class_weights, fsk_svm_platt_fit, fsk_svm_calibrate,
-                                  fsk_svm_get_calibration, fsk_svm_proba and fsk_svm_platt_info) */
+                                  fsk_svm_get_calibration, fsk_svm_proba and fsk_svm_platt_info;
+                                  fsk_svr_train, fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get and fsk_svr_cv_score) */
 
 enum {
     FSK_OK = 0,
@@ -575,6 +576,51 @@ int fsk_svm_platt_fit(const double* dec, const int32_t* labels, int64_t n, fsk_s
 int fsk_svm_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds);
 int fsk_svm_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* out);
 int fsk_svm_proba(fsk_engine* e, int64_t r0, int64_t r1, double* out);
+
+/* ---- epsilon-SVR on the resident triangle: real-valued targets (what read_data(..., regression=True) loads), LIBSVM's
+ * EPSILON_SVR without the kernel matrix leaving the device.
+ *
+ * fsk_svr_train: targets[t] finite, t < n = n_train >= 2. LIBSVM's formulation: 2n variables, element e < n is alpha_e with
+ * y = +1, element e + n is alpha*_e with y = -1, both stand for kernel row e: Q(e, f) = y_e y_f K(e mod n, f mod n); the
+ * linear term is p_e = epsilon - targets[e] and p_{e+n} = epsilon + targets[e] (one rounding each, on the host); alpha = 0 and
+ * G = p at the start; one box C for all. The iteration is fsk_svm_train's, operation for operation, over the 2n elements, ties
+ * to the lowest element in [0, 2n): the results do not depend on the form that ran (one workgroup while 2n <= svm_wg_max, two
+ * launches an iteration beyond — each thread owns both twins of a row, so a kernel cell is read once for the two), on
+ * svm_chunk or on the grid. Finished on the host in element order as LIBSVM does: rho by calculate_rho over the 2n elements,
+ * objective = 1/2 sum alpha_e (G_e + p_e), coef[t] = alpha_t - alpha*_t; fsk_svm_info.n_sv counts coef != 0, n_bsv
+ * |coef| >= C. max_iter, the kernel kind of fsk_svm_set_kernel and a group handle as for fsk_svm_train. Class weights do not
+ * apply to a regression (LIBSVM ignores them there): fsk_svm_set_class_weights changes nothing in a solve of these calls.
+ * FSK_ESTATE before a finalized result; FSK_EINVAL, with a message: n != n_train, n < 2, a target that is not finite, C not
+ * positive and finite, epsilon < 0 or not finite, eps not positive and finite. A refused call leaves the earlier model.
+ * THE MODEL SLOT is one: an SVR model replaces a C-SVC model and the reverse, and whatever drops the one drops the other.
+ * fsk_svm_decision(_device) serve either: sum_i coef_i K(r, i) - rho. fsk_svm_get_model, fsk_svm_calibrate,
+ * fsk_svm_get_calibration and fsk_svm_proba on an SVR model, and fsk_svr_get_model on a C-SVC model, return FSK_ESTATE with a
+ * message that names the kind of the model.
+ * fsk_svr_get_model: alpha2[2 n_train] (alpha, then alpha*), coef[n_train], *rho, *info; every one may be NULL.
+ *
+ * fsk_svr_cv: problem p = (c n_eps + q) n_folds + f trains at (Cs[c], epsilons[q]) on the rows with fold[t] != f, all side by
+ * side in the batch launches, each to the bit fsk_svr_train on its sub-matrix (form 1 while twice the largest training set is
+ * at most svm_wg_max). Then oof[(c n_eps + q) n + t] = sum_i coef_i K(t, i) - rho of problem (c n_eps + q) n_folds + fold[t],
+ * summed as fsk_svm_decision sums, and per grid point on the host, every sum a plain loop over the rows in row order, one
+ * accumulator each, z = targets:
+ *   zm = (sum z_t) / n, om = (sum oof_t) / n; then in ONE pass d = oof_t - z_t, dz = z_t - zm, dq = oof_t - om:
+ *   sse += d d, sae += |d|, sst += dz dz, soo += dq dq, szo += dq dz;
+ *   mse = sse / n, mae = sae / n, r2 = 1 - sse / sst, r = szo / sqrt(soo sst)   (constant targets: sst = 0, r2 and r are not numbers).
+ * fsk_svm_cv_problem.reserved[0] holds the problem's epsilon, fsk_svm_cv_info.reserved0 n_eps. Limits and refusals are
+ * fsk_svm_cv's (FSK_SVM_CV_MAX_PROBLEMS, a fold without rows, a fold id out of range, n_folds < 2, n_C or n_eps < 1, a C,
+ * epsilon or eps out of range, a fold that leaves fewer than 2 training rows) and fsk_svr_train's for the targets; a refused
+ * call leaves the earlier result. The result lives beside fsk_svm_cv's and under the same rules; neither touches the model. */
+typedef struct fsk_svr_cv_score {
+    double C, epsilon;
+    double mse, mae, r2, r;
+    double reserved[2];
+} fsk_svr_cv_score;
+int fsk_svr_train(fsk_engine* e, const double* targets, int64_t n, double C, double epsilon, double eps, int64_t max_iter);
+int fsk_svr_get_model(fsk_engine* e, double* alpha2, double* coef, double* rho, fsk_svm_info* info);
+int fsk_svr_cv(fsk_engine* e, const double* targets, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+               const double* epsilons, int32_t n_eps, double eps, int64_t max_iter);
+/* oof[n_C n_eps n], scores[n_C n_eps], problems[n_C n_eps n_folds], *info of the last fsk_svr_cv: every one may be NULL */
+int fsk_svr_cv_get(fsk_engine* e, double* oof, fsk_svr_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
