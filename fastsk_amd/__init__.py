@@ -2,7 +2,8 @@
 ``FastSK(g, m, ...).compute_kernel(Xtrain, Xtest)`` path)."""
 from .utils import FastaUtility, Vocabulary  # noqa: F401
 
-__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile", "stratified_folds", "kfold", "class_weights"]
+__all__ = ["FastSK", "FastaUtility", "Vocabulary", "mismatch_levels", "center_profile", "stratified_folds", "kfold", "class_weights",
+           "multiclass_weights"]
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name == "class_weights":  # (host only, pure Python)
         from ._native import class_weights
         return class_weights
+    if name == "multiclass_weights":  # (host only, pure Python)
+        from ._native import multiclass_weights
+        return multiclass_weights
     raise AttributeError(name)

@@ -105,6 +105,27 @@ class SvrCvScore(C.Structure):
                 ("r", C.c_double), ("reserved", C.c_double * 2)]
 
 
+class SvmMulticlassPair(C.Structure):
+    _fields_ = [("class_a", C.c_int32), ("class_b", C.c_int32), ("n_rows", C.c_int64), ("iterations", C.c_int64),
+                ("gap", C.c_double), ("objective", C.c_double), ("rho", C.c_double), ("n_sv", C.c_int64), ("n_bsv", C.c_int64),
+                ("converged", C.c_int32), ("reserved0", C.c_int32), ("reserved", C.c_double * 2)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+        d["converged"] = bool(d["converged"])
+        return d
+
+
+class SvmMulticlassInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("n_pairs", C.c_int32), ("form", C.c_int32), ("reserved0", C.c_int32), ("launches", C.c_int64),
+                ("n_sv", C.c_int64), ("n_alpha", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+        d["form"] = _FORMS.get(d["form"], "none")
+        return d
+
+
 class SvmPlattInfo(C.Structure):
     _fields_ = [("A", C.c_double), ("B", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32), ("n_folds", C.c_int32),
                 ("form", C.c_int32), ("launches", C.c_int64), ("ms", C.c_double), ("reserved", C.c_double * 4)]
@@ -143,7 +164,9 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_svm_decision_device", "fsk_svm_cv", "fsk_svm_cv_get", "fsk_svm_cv_get_alpha", "fsk_rows_build", "fsk_rows_get_block",
            "fsk_rows_get_block_device", "fsk_rows_get_info", "fsk_svm_set_kernel", "fsk_svm_get_kernel",
            "fsk_svm_set_class_weights", "fsk_svm_get_class_weights", "fsk_svm_platt_fit", "fsk_svm_calibrate",
-           "fsk_svm_get_calibration", "fsk_svm_proba", "fsk_svr_train", "fsk_svr_get_model", "fsk_svr_cv", "fsk_svr_cv_get"]
+           "fsk_svm_get_calibration", "fsk_svm_proba", "fsk_svr_train", "fsk_svr_get_model", "fsk_svr_cv", "fsk_svr_cv_get",
+           "fsk_svm_train_multiclass", "fsk_svm_multiclass_get_model", "fsk_svm_multiclass_decision",
+           "fsk_svm_multiclass_decision_device", "fsk_svm_multiclass_cv", "fsk_svm_multiclass_cv_get"]
 
 
 _hip_shared = False
@@ -307,6 +330,12 @@ class Library:
             "fsk_svr_get_model": ([vp, vp, vp, C.POINTER(C.c_double), C.POINTER(SvmInfo)], C.c_int),
             "fsk_svr_cv": ([vp, vp, i64, vp, i32, vp, i32, vp, i32, C.c_double, i64], C.c_int),
             "fsk_svr_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
+            "fsk_svm_train_multiclass": ([vp, vp, i64, C.c_double, vp, C.c_double, i64], C.c_int),
+            "fsk_svm_multiclass_get_model": ([vp, vp, vp, vp, C.POINTER(SvmMulticlassInfo)], C.c_int),
+            "fsk_svm_multiclass_decision": ([vp, i64, i64, vp, vp], C.c_int),
+            "fsk_svm_multiclass_decision_device": ([vp, i64, i64, vp, vp], C.c_int),
+            "fsk_svm_multiclass_cv": ([vp, vp, i64, vp, i32, vp, i32, vp, C.c_double, i64], C.c_int),
+            "fsk_svm_multiclass_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
         }
         for name, (argtypes, restype) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -516,6 +545,31 @@ def class_weights(labels, spec):
     if not all(np.isfinite(x) and x > 0.0 for x in w):
         raise ValueError("class_weight: the weights must be positive finite numbers, got %r" % (w,))
     return w
+
+
+def multiclass_weights(labels, spec):
+    """The ``class_weight=`` keyword of ``fit_svm_multiclass`` -> one weight a class, in ascending class order (host only), or
+    None. ``None``: None (every weight 1). ``"balanced"``: ``n / (k count_c)`` as scikit-learn's, computed ONCE from all
+    training labels. A dict keyed by label (a missing class is 1; a key that is no class is a ``ValueError``). ``ValueError``
+    unless every weight is a positive finite number."""
+    if spec is None:
+        return None
+    classes, counts = np.unique(np.asarray(labels), return_counts=True)
+    if isinstance(spec, str):
+        if spec != "balanced":
+            raise ValueError("class_weight %r: None, \"balanced\" or a dict keyed by label" % (spec,))
+        w = [len(labels) / (float(len(classes)) * float(c)) for c in counts.tolist()]
+    elif hasattr(spec, "items"):
+        known = set(classes.tolist())
+        for key in spec:
+            if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or int(key) not in known:
+                raise ValueError("class_weight: %r is not a class of the labels" % (key,))
+        w = [float({int(a): b for a, b in spec.items()}.get(c, 1.0)) for c in classes.tolist()]
+    else:
+        raise ValueError("class_weight: None, \"balanced\" or a dict keyed by label")
+    if not all(np.isfinite(x) and x > 0.0 for x in w):
+        raise ValueError("class_weight: the weights must be positive finite numbers, got %r" % (w,))
+    return np.array(w, dtype=np.float64)
 
 
 def center_profile(plateau, halflife, levels=8, floor=0):
@@ -1100,6 +1154,86 @@ class Engine:
         out = np.empty(max(r1 - r0, 0), dtype=np.float64)
         self._ck(self.lib.L.fsk_svm_proba(self.h, r0, r1, out.ctypes.data))
         return out
+
+    # ---- multi-class C-SVC, one-vs-one: the pairs of classes as one batch on the resident triangle
+    def _class_weight_array(self, labels, class_weight):
+        """``class_weight`` for the C calls: None, or one weight a class in ascending class order (an array, or "balanced" / a
+        dict keyed by label through ``multiclass_weights``)."""
+        if class_weight is None:
+            return None
+        if hasattr(class_weight, "items") or isinstance(class_weight, str):
+            return multiclass_weights(labels, class_weight)
+        w = np.ascontiguousarray(class_weight, dtype=np.float64)
+        if w.ndim != 1 or len(w) != len(np.unique(labels)):
+            raise ValueError("class_weight: one weight a class, in ascending class order")
+        return w
+
+    def svm_train_multiclass(self, labels, C=1.0, eps=1e-3, max_iter=-1, class_weight=None):
+        """``fsk_svm_train_multiclass``: a one-vs-one C-SVC on the train x train part of the finalized result, ``labels`` any
+        int32 values (2 to 64 classes). ``class_weight``: None, one weight a class in ascending class order, or what
+        ``multiclass_weights`` takes ("balanced", a dict keyed by label). Returns the info of ``svm_multiclass_model()``."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim != 1:
+            raise ValueError("labels must be 1-D")
+        w = self._class_weight_array(labels, class_weight)
+        self._ck(self.lib.L.fsk_svm_train_multiclass(self.h, labels.ctypes.data if len(labels) else None, len(labels), float(C),
+                                                     None if w is None else w.ctypes.data, float(eps), int(max_iter)))
+        return self.svm_multiclass_model()["info"]
+
+    def svm_multiclass_model(self):
+        """The model of the last ``svm_train_multiclass``: ``classes`` [k] ascending, ``pairs`` (pair p over classes (a, b),
+        a < b, lexicographic: ``class_a``, ``class_b``, ``n_rows``, ``iterations``, ``gap``, ``objective``, ``rho``, ``n_sv``,
+        ``n_bsv``, ``converged``), ``alpha`` (a list: pair p's alpha at its own length, over its rows ascending) and ``info``
+        (``k``, ``n_pairs``, ``form``, ``launches``, ``ms``, ``n_sv``: rows that are a support vector of any pair)."""
+        info = SvmMulticlassInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, None, None, None, C.byref(info)))
+        classes = np.empty(info.k, dtype=np.int32)
+        pairs = (SvmMulticlassPair * info.n_pairs)()
+        alpha = np.empty(info.n_alpha, dtype=np.float64)
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, classes.ctypes.data, C.addressof(pairs), alpha.ctypes.data, C.byref(info)))
+        cuts = np.cumsum([q.n_rows for q in pairs])[:-1]
+        return {"classes": classes, "pairs": [q.as_dict() for q in pairs], "alpha": np.split(alpha, cuts), "info": info.as_dict()}
+
+    def svm_multiclass_decision(self, r0, r1, decision=True, predict=True):
+        """``fsk_svm_multiclass_decision``: (the pairs' decision values [r1 - r0, P], the winning labels [r1 - r0]) of rows
+        [r0, r1) of the sequences (train rows first); None for the one not asked for."""
+        info = SvmMulticlassInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, None, None, None, C.byref(info)))
+        rows = max(r1 - r0, 0)
+        dec = np.empty((rows, info.n_pairs), dtype=np.float64) if decision else None
+        pred = np.empty(rows, dtype=np.int32) if predict else None
+        self._ck(self.lib.L.fsk_svm_multiclass_decision(self.h, r0, r1, None if dec is None else dec.ctypes.data,
+                                                        None if pred is None else pred.ctypes.data))
+        return dec, pred
+
+    def svm_multiclass_cv(self, labels, fold, Cs, eps=1e-3, max_iter=-1, n_folds=None, class_weight=None):
+        """``fsk_svm_multiclass_cv``: the one-vs-one C-SVC cross-validated over the folds ``fold[t]`` and the values ``Cs``, every
+        (C, fold, pair) problem solved side by side. Returns ``pred`` [n_C, n_train] (out-of-fold labels), ``accuracy`` [n_C]
+        (there is no AUC for more than two classes), ``problems`` (problem ``(c * F + f) * P + p`` with ``class_a``,
+        ``class_b``), ``k``, ``form``, ``launches``, ``ms``."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        Cs = np.ascontiguousarray(Cs, dtype=np.float64)
+        if labels.ndim != 1 or fold.ndim != 1 or Cs.ndim != 1:
+            raise ValueError("labels, fold and Cs must be 1-D")
+        if len(fold) != len(labels):
+            raise ValueError("%d fold ids for %d labels" % (len(fold), len(labels)))
+        if n_folds is None:
+            n_folds = int(fold.max()) + 1 if len(fold) else 0
+        w = self._class_weight_array(labels, class_weight)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        self._ck(self.lib.L.fsk_svm_multiclass_cv(self.h, ptr(labels), len(labels), ptr(fold), n_folds, ptr(Cs), len(Cs),
+                                                  None if w is None else w.ctypes.data, float(eps), int(max_iter)))
+        info = SvmCvInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_cv_get(self.h, None, None, None, C.byref(info)))
+        k = info.reserved0
+        n, total = len(labels), len(Cs) * n_folds * (k * (k - 1) // 2)
+        pred = np.empty((len(Cs), n), dtype=np.int32)
+        scores, problems = (SvmCvScore * len(Cs))(), (SvmCvProblem * total)()
+        self._ck(self.lib.L.fsk_svm_multiclass_cv_get(self.h, pred.ctypes.data, C.addressof(scores), C.addressof(problems), C.byref(info)))
+        return {"pred": pred, "accuracy": np.array([s.accuracy for s in scores]),
+                "problems": [dict(q.as_dict(), class_a=int(q.reserved[0]), class_b=int(q.reserved[1])) for q in problems], "k": k,
+                "form": _FORMS.get(info.form, "none"), "launches": info.launches, "ms": info.ms}
 
     def svm_cv_alpha(self, p):
         """alpha[n_train] of problem ``p`` of the last ``svm_cv``, zero at its held-out rows."""

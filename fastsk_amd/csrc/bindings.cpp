@@ -14,7 +14,9 @@
 //     predict_proba_np(which) Platt's probabilities (fsk_svm_calibrate / fsk_svm_proba);
 //     fit_svr(targets, C, epsilon, ...), predict_np / predict_dlpack(which) and cross_validate_svr(targets, Cs, epsilons, folds, ...)
 //     the epsilon-SVR on real-valued targets (fsk_svr_train / fsk_svr_cv), in the one model slot;
-//     both take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
+//     fit_svm_multiclass(labels, C, ...), predict_class_np(which) and cross_validate_svm_multiclass(labels, Cs, folds, ...) the
+//     one-vs-one multi-class C-SVC on integer labels (fsk_svm_train_multiclass / fsk_svm_multiclass_cv), in the same slot;
+//     all of them take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
 //     the kernel, through the rows kernel (fsk_rows_build; get_rows_kernel_block_np, rows_kernel_info);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
 //     DLPack getters. devices=[0,1,...]: one engine per listed GPU behind the same object (fsk_create_multi) —
@@ -809,6 +811,136 @@ public:
         else d["refit"] = py::none();
         return d;
     }
+    // ---- multi-class C-SVC, one-vs-one (fsk_svm_train_multiclass): labels are any integers, the k (k - 1) / 2 pairs of classes
+    // are solved side by side in one batch; the model takes the one model slot. decision_function_np then returns [rows, P],
+    // predict_class_np the voted labels; get_dual_coef_np, get_intercept and predict_proba_np raise RuntimeError naming the
+    // model (pairwise coupling of probabilities is not built). class_weight: None, "balanced" (n / (k count_c)) or a dict keyed
+    // by label (fastsk_amd._native.multiclass_weights).
+    using WeightArray = py::array_t<double, py::array::c_style | py::array::forcecast>;
+    static bool parse_multiclass_weight(const py::object& labels, const py::object& spec, WeightArray* w) {
+        py::object r = py::module_::import("fastsk_amd._native").attr("multiclass_weights")(labels, spec);
+        if (r.is_none()) return false;
+        *w = r.cast<WeightArray>();
+        return true;
+    }
+    static py::dict pair_dict(int32_t a, int32_t b, int64_t n_rows, int64_t iterations, bool converged, double gap, double objective, double rho,
+                              int64_t n_sv, int64_t n_bsv) {
+        py::dict d;
+        d["class_a"] = a; d["class_b"] = b; d["n_rows"] = n_rows; d["iterations"] = iterations; d["converged"] = converged; d["gap"] = gap;
+        d["objective"] = objective; d["rho"] = rho; d["n_sv"] = n_sv; d["n_bsv"] = n_bsv;
+        return d;
+    }
+    py::dict fit_svm_multiclass(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter,
+                                const std::string& kernel_type, py::object class_weight) {
+        const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one integer per training sequence");
+        WeightArray w;
+        const bool weighted = parse_multiclass_weight(labels, class_weight, &w);
+        check(fsk_svm_set_kernel(h_, kind));
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svm_train_multiclass(h_, labels.data(), (int64_t)labels.shape(0), C, weighted ? w.data() : nullptr, eps, max_iter);
+        }
+        check(rc);
+        svr_ = false;
+        labels_.clear();
+        fsk_svm_multiclass_info mi;
+        check(fsk_svm_multiclass_get_model(h_, nullptr, nullptr, nullptr, &mi));
+        py::array_t<int32_t> classes((py::ssize_t)mi.k);
+        std::vector<fsk_svm_multiclass_pair> pairs((size_t)mi.n_pairs);
+        check(fsk_svm_multiclass_get_model(h_, classes.mutable_data(), pairs.data(), nullptr, &mi));
+        py::list pl;
+        bool converged = true;
+        for (const fsk_svm_multiclass_pair& q : pairs) {
+            pl.append(pair_dict(q.class_a, q.class_b, q.n_rows, q.iterations, (bool)q.converged, q.gap, q.objective, q.rho, q.n_sv, q.n_bsv));
+            converged = converged && q.converged;
+        }
+        py::dict d;
+        d["classes"] = classes; d["pairs"] = pl; d["k"] = mi.k; d["n_pairs"] = mi.n_pairs; d["n_sv"] = mi.n_sv; d["converged"] = converged;
+        d["form"] = mi.form == 1 ? "workgroup" : "two-launch"; d["launches"] = mi.launches; d["ms"] = mi.ms; d["kernel_type"] = kernel_type;
+        if (weighted) d["class_weight"] = w; else d["class_weight"] = py::none();
+        return d;
+    }
+    // the voted label of the test (or train) rows under the model of fit_svm_multiclass: LIBSVM's rule, the lowest class among
+    // equal vote counts
+    py::array_t<int32_t> predict_class_np(const std::string& which) const {
+        int64_t r0, r1;
+        decision_rows(which, &r0, &r1);
+        py::array_t<int32_t> out((py::ssize_t)(r1 - r0));
+        check(fsk_svm_multiclass_decision(h_, r0, r1, nullptr, out.mutable_data()));
+        return out;
+    }
+    // cross-validation of the multi-class C-SVC over folds and values of C, every (C, fold, pair) problem in one batch
+    // (fsk_svm_multiclass_cv). folds as for cross_validate_svm. best_C: the C of the highest out-of-fold accuracy, the smallest
+    // of equals (there is no AUC for more than two classes); refit=True then trains fit_svm_multiclass(labels, C=best_C).
+    py::dict cross_validate_svm_multiclass(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
+                                           py::array_t<double, py::array::c_style | py::array::forcecast> Cs, py::object folds, double eps,
+                                           int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type, py::object class_weight) {
+        const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
+        if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
+        if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one integer per training sequence");
+        if (Cs.ndim() != 1) throw py::value_error("Cs must be 1-D");
+        WeightArray w;
+        const bool weighted = parse_multiclass_weight(labels, class_weight, &w);
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
+        int32_t n_folds = 0;
+        if (py::isinstance<py::int_>(folds) && !py::isinstance<py::bool_>(folds)) {
+            n_folds = folds.cast<int32_t>();
+            fold = py::module_::import("fastsk_amd._native").attr("stratified_folds")(labels, folds, seed);
+        } else {
+            fold = folds.cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+            if (fold.ndim() != 1 || fold.shape(0) != labels.shape(0)) throw py::value_error("folds must be an int or one fold id per label");
+            for (py::ssize_t t = 0; t < fold.shape(0); ++t) n_folds = std::max(n_folds, fold.data()[t] + 1);
+        }
+        const int64_t n = (int64_t)labels.shape(0);
+        const int32_t n_C = (int32_t)Cs.shape(0);
+        check(fsk_svm_set_kernel(h_, kind));
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = fsk_svm_multiclass_cv(h_, labels.data(), n, fold.data(), n_folds, Cs.data(), n_C, weighted ? w.data() : nullptr, eps, max_iter);
+        }
+        check(rc);
+        fsk_svm_cv_info info;
+        check(fsk_svm_multiclass_cv_get(h_, nullptr, nullptr, nullptr, &info));
+        const int64_t k = info.reserved0, total = (int64_t)n_C * n_folds * (k * (k - 1) / 2);
+        py::array_t<int32_t> pred({(py::ssize_t)n_C, (py::ssize_t)n});
+        py::array_t<double> acc((py::ssize_t)n_C);
+        std::vector<fsk_svm_cv_score> scores((size_t)n_C);
+        std::vector<fsk_svm_cv_problem> probs((size_t)total);
+        check(fsk_svm_multiclass_cv_get(h_, pred.mutable_data(), scores.data(), probs.data(), &info));
+        int32_t best = 0;
+        for (int32_t c = 0; c < n_C; ++c) {
+            acc.mutable_data()[c] = scores[(size_t)c].accuracy;
+            const fsk_svm_cv_score &x = scores[(size_t)c], &b = scores[(size_t)best];
+            if (x.accuracy > b.accuracy || (x.accuracy == b.accuracy && x.C < b.C)) best = c;
+        }
+        py::list problems;
+        for (const fsk_svm_cv_problem& q : probs) {
+            py::dict d = pair_dict((int32_t)q.reserved[0], (int32_t)q.reserved[1], q.n_rows, q.iterations, (bool)q.converged, q.gap, q.objective, q.rho,
+                                   q.n_sv, q.n_bsv);
+            d["C"] = q.C; d["fold"] = q.fold;
+            problems.append(d);
+        }
+        py::dict d;
+        d["pred"] = pred; d["accuracy"] = acc; d["problems"] = problems; d["k"] = k;
+        d["form"] = info.form == 1 ? "workgroup" : "two-launch"; d["launches"] = info.launches; d["ms"] = info.ms;
+        d["fold"] = fold; d["best_C"] = scores[(size_t)best].C; d["kernel_type"] = kernel_type;
+        if (weighted) d["class_weight"] = w; else d["class_weight"] = py::none();
+        if (refit) {
+            py::object cw = py::none();
+            if (weighted) {  // (the very weights, keyed by class)
+                py::dict by_label;
+                py::array_t<int32_t> classes = py::module_::import("numpy").attr("unique")(labels).cast<py::array_t<int32_t>>();
+                for (py::ssize_t c = 0; c < classes.shape(0); ++c) by_label[py::int_(classes.data()[c])] = w.data()[c];
+                cw = by_label;
+            }
+            d["refit"] = fit_svm_multiclass(labels, scores[(size_t)best].C, eps, max_iter, kernel_type, cw);
+        }
+        return d;
+    }
     py::array_t<double> get_dual_coef_np() const {  // alpha_i y_i, as scikit-learn's dual_coef_ (dense, every training row)
         py::array_t<double> out((py::ssize_t)n_train_);
         if (svr_) {  // (alpha - alpha*)
@@ -833,9 +965,17 @@ public:
     }
     // sum_i alpha_i y_i K(r, i) - rho of the test (or train) rows: only cells with a train column are read, so the
     // test x test block is neither needed nor computed (skip_test_block=True / "lazy")
+    // With the model of fit_svm_multiclass: [rows, P], the pairs (a, b), a < b, in lexicographic order of the classes — the
+    // columns of scikit-learn's decision_function_shape="ovo".
     py::array_t<double> decision_function_np(const std::string& which) const {
         int64_t r0, r1;
         decision_rows(which, &r0, &r1);
+        fsk_svm_multiclass_info mi;
+        if (fsk_svm_multiclass_get_model(h_, nullptr, nullptr, nullptr, &mi) == FSK_OK) {
+            py::array_t<double> dec({(py::ssize_t)(r1 - r0), (py::ssize_t)mi.n_pairs});
+            check(fsk_svm_multiclass_decision(h_, r0, r1, dec.mutable_data(), nullptr));
+            return dec;
+        }
         py::array_t<double> out((py::ssize_t)(r1 - r0));
         check(fsk_svm_decision(h_, r0, r1, out.mutable_data()));
         return out;
@@ -947,6 +1087,12 @@ PYBIND11_MODULE(_fastsk, m) {
              py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk", py::arg("refit") = false)
         .def("predict_np", &FastSK::decision_function_np, py::arg("which") = "test")
         .def("predict_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
+        .def("fit_svm_multiclass", &FastSK::fit_svm_multiclass, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3,
+             py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none())
+        .def("predict_class_np", &FastSK::predict_class_np, py::arg("which") = "test")
+        .def("cross_validate_svm_multiclass", &FastSK::cross_validate_svm_multiclass, py::arg("labels"),
+             py::arg("Cs") = std::vector<double>{1.0}, py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1,
+             py::arg("seed") = 0, py::arg("refit") = false, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none())
         .def("stats", &FastSK::stats);
     // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
     m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {

@@ -230,7 +230,7 @@ int make_diag(fsk_engine* e) {
         FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_diag<u64>), dim3(blocks), dim3(256), 0, e->stream, e->d_K, e->d_diag.p, (uint32_t)e->N);
     FSK_HIP(hipStreamSynchronize(e->stream));
     e->finalized = true;
-    e->svm.valid = e->svm.cv.valid = e->svm.svr_cv.valid = false;  // (a model and a cross-validation belong to the result they were computed on)
+    e->svm.valid = e->svm.cv.valid = e->svm.svr_cv.valid = e->svm.mc_cv.valid = false;  // (a model and a cross-validation belong to the result they were computed on)
     e->rows.drop();                          // (and so does the rows kernel)
     return FSK_OK;
 }

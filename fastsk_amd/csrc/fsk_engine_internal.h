@@ -253,10 +253,32 @@ struct SvmCvState {
     DevBuf<unsigned char> d_prob, d_rec;         // fsk::SvmProb [problems]; the records and candidate slots
 };
 
+// A batch of one-vs-one pair problems (fsk_svm_train_multiclass: the model's P pairs; fsk_svm_multiclass_cv: n_C n_folds P of
+// them) with what the vote kernel reads: the problems' records, row lists and coefficients stay on the device after the solve.
+// Two instances: the model's (valid with SvmState::valid under model_kind 2) and the cross-validation's (valid of its own).
+struct SvmMcState {
+    bool valid = false;                          // the cross-validation's
+    uint32_t k = 0, P = 0;                       // classes, pairs
+    std::vector<int32_t> classes;                // [k], ascending
+    std::vector<fsk_svm_multiclass_pair> pairs;  // model: [P]
+    std::vector<double> alpha;                   // model: the pairs' slices, one after another
+    fsk_svm_multiclass_info info{};
+    std::vector<int32_t> oof;                    // cross-validation: [n_C][n] labels
+    std::vector<fsk_svm_cv_score> scores;        //                   [n_C]
+    std::vector<fsk_svm_cv_problem> problems;    //                   [n_C n_folds P]
+    fsk_svm_cv_info cv_info{};
+    DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_rho, d_dec;
+    DevBuf<uint32_t> d_idx, d_ab;                // the row lists; a | b << 16 of every pair
+    DevBuf<int32_t> d_classes, d_pred, d_fold;
+    DevBuf<signed char> d_y;
+    DevBuf<unsigned char> d_prob, d_rec;         // fsk::SvmProb [problems]; the records and candidate slots
+};
+
 struct SvmState {
     bool valid = false;
     SvmCvState cv;
-    int model_kind = 0;              // of the one model slot: 0 a C-SVC (fsk_svm_train), 1 an epsilon-SVR (fsk_svr_train)
+    SvmMcState mc, mc_cv;            // the multi-class model (model_kind 2) and the result of the last fsk_svm_multiclass_cv
+    int model_kind = 0;              // of the one model slot: 0 a C-SVC (fsk_svm_train), 1 an epsilon-SVR (fsk_svr_train), 2 a one-vs-one multi-class C-SVC
     std::vector<double> alpha;       // [n_train]; of an SVR model [2 n_train]: alpha, then alpha*
     std::vector<double> coef;        // SVR model: [n_train], alpha - alpha*
     SvmCvState svr_cv;               // the result of the last fsk_svr_cv (problems (c n_eps + q) n_folds + f), valid as cv is

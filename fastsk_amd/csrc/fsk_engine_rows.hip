@@ -173,7 +173,7 @@ int fsk_rows_get_info(fsk_engine* e, fsk_rows_info* out) {
 int fsk_svm_set_kernel(fsk_engine* e, int32_t kind) {
     if (!e) return FSK_EINVAL;
     if (kind != FSK_SVM_KERNEL_RESULT && kind != FSK_SVM_KERNEL_ROWS) return e->fail(FSK_EINVAL, "kernel kind %d: FSK_SVM_KERNEL_RESULT (0) or FSK_SVM_KERNEL_ROWS (1)", kind);
-    if (kind != e->svm.kernel) e->svm.valid = e->svm.cv.valid = e->svm.svr_cv.valid = false;  // (a model belongs to the kernel it was trained on)
+    if (kind != e->svm.kernel) e->svm.valid = e->svm.cv.valid = e->svm.svr_cv.valid = e->svm.mc_cv.valid = false;  // (a model belongs to the kernel it was trained on)
     e->svm.kernel = kind;
     return FSK_OK;
 }

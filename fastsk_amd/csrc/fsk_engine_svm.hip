@@ -1,7 +1,9 @@
 // fsk_engine_svm.hip — the SVM stage on the resident result triangle: fsk_svm_train, fsk_svm_get_model, fsk_svm_decision(_device),
 // fsk_svm_cv, fsk_svm_cv_get(_alpha), the class weights (fsk_svm_set_class_weights) and the Platt calibration
-// (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba) and the epsilon-SVR (fsk_svr_train,
-// fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
+// (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba), the epsilon-SVR (fsk_svr_train,
+// fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get) and the one-vs-one multi-class C-SVC (fsk_svm_train_multiclass,
+// fsk_svm_multiclass_get_model, fsk_svm_multiclass_decision(_device), fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get) of
+// include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
 // (fastsk.cpp:239-530), for the sequences of one compute call and without the kernel matrix ever leaving the device: the
 // engine's consumer is an SVM, and the triangle it needs is 40 GB at 100,000 sequences.
 //
@@ -173,13 +175,16 @@ int model_ready(fsk_engine* e) {
     if (!e->finalized || !e->svm.valid) return e->fail(FSK_ESTATE, "no model: call fsk_svm_train on a finalized result first");
     return FSK_OK;
 }
-// The one model slot holds a C-SVC (fsk_svm_train) or an epsilon-SVR (fsk_svr_train): the calls that are one kind's alone
-constexpr int MODEL_SVC = 0, MODEL_SVR = 1;
+// The one model slot holds a C-SVC (fsk_svm_train), an epsilon-SVR (fsk_svr_train) or a one-vs-one multi-class C-SVC
+// (fsk_svm_train_multiclass): the calls that are one kind's alone
+constexpr int MODEL_SVC = 0, MODEL_SVR = 1, MODEL_MC = 2;
+const char* model_text(int kind) {
+    return kind == MODEL_SVR ? "an epsilon-SVR (fsk_svr_train)" : kind == MODEL_MC ? "a multi-class C-SVC (fsk_svm_train_multiclass)" : "a C-SVC (fsk_svm_train)";
+}
 int model_of_kind(fsk_engine* e, int kind, const char* call) {
     int rc = model_ready(e);
     if (rc) return rc;
-    if (e->svm.model_kind != kind)
-        return e->fail(FSK_ESTATE, "%s: the model is %s", call, e->svm.model_kind == MODEL_SVR ? "an epsilon-SVR (fsk_svr_train)" : "a C-SVC (fsk_svm_train)");
+    if (e->svm.model_kind != kind) return e->fail(FSK_ESTATE, "%s: the model is %s", call, model_text(e->svm.model_kind));
     return FSK_OK;
 }
 
@@ -199,6 +204,7 @@ int launch_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dst) {
 int decision_args(fsk_engine* e, int64_t r0, int64_t r1, const double* out) {
     int rc = model_ready(e);
     if (rc) return rc;
+    if (e->svm.model_kind == MODEL_MC) return e->fail(FSK_ESTATE, "fsk_svm_decision: the model is %s", model_text(MODEL_MC));  // (one value a row: a C-SVC's or an SVR's)
     if (r0 < 0 || r1 > e->N || r0 > r1) return e->fail(FSK_EINVAL, "rows out of range");
     if (r1 > r0 && !out) return e->fail(FSK_EINVAL, "null output");
     return FSK_OK;
@@ -810,9 +816,422 @@ int svr_cv_run(fsk_engine* e, const double* z, int64_t n, const int32_t* fold, i
     return FSK_OK;
 }
 
+// ---- one-vs-one multi-class C-SVC: the pairs of classes as one batch (fsk_svm_train_multiclass, fsk_svm_multiclass_cv) ---------
+// The classes of a label vector: the distinct values ascending, every row's class index, the rows of each class (ascending),
+// the weights by class index (1 where class_weight is null). What the train and the cross-validation check alike.
+struct McClasses {
+    std::vector<int32_t> classes;
+    std::vector<uint32_t> cls;     // [n]
+    std::vector<double> w;         // [k]
+};
+int mc_check(fsk_engine* e, const int32_t* labels, const char* null_text, int64_t n, double eps, const double* class_weight, McClasses* out) {
+    if (!e->finalized) return e->fail(FSK_ESTATE, "no finalized kernel: call fsk_compute or fsk_finalize first");
+    if (!labels) return e->fail(FSK_EINVAL, "%s", null_text);
+    if (n != e->n_train) return e->fail(FSK_EINVAL, "%lld labels for %lld training sequences", (long long)n, (long long)e->n_train);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return e->fail(FSK_EINVAL, "eps must be a positive finite number");
+    out->classes.assign(labels, labels + n);
+    std::sort(out->classes.begin(), out->classes.end());
+    out->classes.erase(std::unique(out->classes.begin(), out->classes.end()), out->classes.end());
+    const size_t k = out->classes.size();
+    if (k < 2) return e->fail(FSK_EINVAL, "only one class is present");
+    if (k > FSK_SVM_MAX_CLASSES) return e->fail(FSK_EUNSUPPORTED, "%zu classes: at most %d", k, FSK_SVM_MAX_CLASSES);
+    out->w.assign(k, 1.0);
+    for (size_t c = 0; class_weight && c < k; ++c) {
+        if (!(class_weight[c] > 0.0) || !std::isfinite(class_weight[c]))
+            return e->fail(FSK_EINVAL, "the weight of class %d must be a positive finite number", out->classes[c]);
+        out->w[c] = class_weight[c];
+    }
+    out->cls.resize((size_t)n);
+    for (int64_t t = 0; t < n; ++t)
+        out->cls[(size_t)t] = (uint32_t)(std::lower_bound(out->classes.begin(), out->classes.end(), labels[t]) - out->classes.begin());
+    return FSK_OK;
+}
+
+// The batch of pair problems, solved and finished. In: probs with Cp, Cn, idx_off and n set (st_off and wg_off are set here), the
+// row lists and their labels. The batch goes through solve_batch in the form cv_run would choose, every problem is finished by
+// svm_finish; its coefficients (alpha y at the problem's own length, at st_off), rho, the problems and the lists stay on the
+// device in M for the vote kernels. Out: alpha and the status records of every problem, what svm_finish returned.
+struct McSolved {
+    std::vector<double> alpha;
+    std::vector<fsk::SvmRecB> status;
+    std::vector<SvmFinish> fin;
+    int form = 0;
+    int64_t launches = 0;
+};
+int mc_solve(fsk_engine* e, SvmMcState& M, const SvmSource& src, std::vector<fsk::SvmProb>& probs, const std::vector<uint32_t>& idx,
+             const std::vector<signed char>& y, double eps, int64_t max_iter, McSolved* out) {
+    const uint32_t P = (uint32_t)probs.size();
+    uint32_t max_n = 0, total_wg = 0;
+    u64 total = 0;
+    for (fsk::SvmProb& pr : probs) {
+        pr.st_off = total;
+        pr.wg_off = total_wg;
+        total += pr.n;
+        total_wg += (pr.n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS;
+        max_n = std::max(max_n, pr.n);
+    }
+    const int form = (int64_t)max_n <= e->tune.svm_wg_max ? 1 : 2;
+    const uint32_t chunk = (uint32_t)e->tune.svm_chunk;
+    const size_t rec_bytes = svm_batch_record_bytes(P, total_wg);
+    FSK_HIP(M.d_alpha.reserve(total));
+    FSK_HIP(M.d_G.reserve(total));
+    if (form == 2) FSK_HIP(M.d_krow.reserve(total));
+    FSK_HIP(M.d_coef.reserve(total));
+    FSK_HIP(M.d_idx.reserve(idx.size()));
+    FSK_HIP(M.d_y.reserve(y.size()));
+    FSK_HIP(M.d_prob.reserve((size_t)P * sizeof(fsk::SvmProb)));
+    FSK_HIP(M.d_rec.reserve(rec_bytes));
+    FSK_HIP(M.d_rho.reserve(P));
+
+    SvmBatch B;
+    B.P = P; B.max_n = max_n; B.max_wg = (max_n + fsk::SVM_THREADS - 1) / fsk::SVM_THREADS; B.total_wg = total_wg;
+    B.probs = reinterpret_cast<const fsk::SvmProb*>(M.d_prob.p);
+    B.idx = M.d_idx.p; B.y = M.d_y.p; B.alpha = M.d_alpha.p; B.G = M.d_G.p; B.krow = M.d_krow.p;
+    B.rb = reinterpret_cast<fsk::SvmRecB*>(M.d_rec.p);
+    B.ra = reinterpret_cast<fsk::SvmRecA*>(B.rb + P);
+    B.ci = reinterpret_cast<fsk::SvmCandI*>(B.ra + P);
+    B.cj = reinterpret_cast<fsk::SvmCandJ*>(B.ci + total_wg);
+
+    std::vector<double> G(total, -1.0);
+    FSK_HIP(hipMemcpyAsync(M.d_prob.p, probs.data(), (size_t)P * sizeof(fsk::SvmProb), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_y.p, y.data(), y.size(), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_G.p, G.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemsetAsync(M.d_alpha.p, 0, total * sizeof(double), e->stream));
+    FSK_HIP(hipMemsetAsync(M.d_rec.p, 0, rec_bytes, e->stream));  // iter = 0, nothing pending, nobody done
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+
+    out->status.assign(P, fsk::SvmRecB{});
+    out->launches = 0;
+    out->form = form;
+    const int rc = svm_on_source(src, [&](auto* K) { return solve_batch(e, K, src.diag, B, eps, max_iter, form, chunk, out->status.data(), &out->launches); });
+    if (rc) return rc;
+    out->alpha.resize(total);
+    FSK_HIP(hipMemcpyAsync(out->alpha.data(), M.d_alpha.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipMemcpyAsync(G.data(), M.d_G.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+
+    std::vector<double> coef(total), rho(P);
+    out->fin.resize(P);
+    for (uint32_t p = 0; p < P; ++p) {
+        const fsk::SvmProb& pr = probs[p];
+        out->fin[p] = svm_finish(out->alpha.data() + pr.st_off, G.data() + pr.st_off, y.data() + pr.idx_off, pr.n, pr.Cp, pr.Cn, coef.data() + pr.st_off);
+        rho[p] = out->fin[p].rho;
+    }
+    FSK_HIP(hipMemcpyAsync(M.d_coef.p, coef.data(), total * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_rho.p, rho.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    return FSK_OK;
+}
+
+// the classes and the pairs' (a | b << 16) for the vote, into M
+int mc_upload_classes(fsk_engine* e, SvmMcState& M, const std::vector<int32_t>& classes) {
+    const uint32_t k = (uint32_t)classes.size(), P = k * (k - 1) / 2;
+    std::vector<uint32_t> ab;
+    ab.reserve(P);
+    for (uint32_t a = 0; a < k; ++a)
+        for (uint32_t b = a + 1; b < k; ++b) ab.push_back(a | b << 16);
+    FSK_HIP(M.d_ab.reserve(P));
+    FSK_HIP(M.d_classes.reserve(k));
+    FSK_HIP(hipMemcpyAsync(M.d_ab.p, ab.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_classes.p, classes.data(), (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    M.k = k;
+    M.P = P;
+    M.classes = classes;
+    return FSK_OK;
+}
+
+// rows [r0, r1) under the model's pairs into device memory: dec [r1 - r0][P] and / or pred [r1 - r0]
+int mc_launch_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dec, int32_t* pred) {
+    const SvmMcState& M = e->svm.mc;
+    const uint32_t blocks = (uint32_t)((r1 - r0 + 3) / 4), a = (uint32_t)r0, b = (uint32_t)r1, P = M.P;
+    SvmSource src;
+    { int rc = svm_source(e, false, &src); if (rc) return rc; }
+    const double *diag = src.diag, *coef = M.d_coef.p, *rho = M.d_rho.p;
+    const fsk::SvmProb* probs = reinterpret_cast<const fsk::SvmProb*>(M.d_prob.p);
+    const uint32_t *idx = M.d_idx.p, *ab = M.d_ab.p;
+    const int32_t* classes = M.d_classes.p;
+    return svm_on_source(src, [=](auto* K) -> int {
+        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_ovo_decision<SrcOf<decltype(K)>>), dim3(blocks), dim3(256), 0, e->stream, K, diag, probs, idx, coef, rho, ab,
+                   classes, P, a, b, dec, pred);
+        return FSK_OK;
+    });
+}
+
+int mc_decision_args(fsk_engine* e, const char* call, int64_t r0, int64_t r1) {
+    int rc = model_of_kind(e, MODEL_MC, call);
+    if (rc) return rc;
+    if (r0 < 0 || r1 > e->N || r0 > r1) return e->fail(FSK_EINVAL, "rows out of range");
+    return FSK_OK;
+}
+
+int mc_cv_ready(fsk_engine* e) {
+    if (!e->finalized || !e->svm.mc_cv.valid)
+        return e->fail(FSK_ESTATE, "no cross-validation: call fsk_svm_multiclass_cv on a finalized result first");
+    return FSK_OK;
+}
+
+// the rows of class a or b among `rows` of them (ascending), with y = +1 for a and -1 for b, appended to idx and y
+template <typename Keep>
+uint32_t mc_pair_list(const std::vector<uint32_t>& cls, uint32_t a, uint32_t b, Keep keep, std::vector<uint32_t>* idx, std::vector<signed char>* y) {
+    uint32_t count = 0;
+    for (uint32_t t = 0; t < (uint32_t)cls.size(); ++t)
+        if ((cls[t] == a || cls[t] == b) && keep(t)) {
+            idx->push_back(t);
+            y->push_back(cls[t] == a ? (signed char)1 : (signed char)-1);
+            ++count;
+        }
+    return count;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fsk_svm_train_multiclass(fsk_engine* e, const int32_t* labels, int64_t n, double C, const double* class_weight, double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    McClasses mcl;
+    { int rcc = mc_check(e, labels, "null labels", n, eps, class_weight, &mcl); if (rcc) return rcc; }
+    if (!(C > 0.0) || !std::isfinite(C)) return e->fail(FSK_EINVAL, "C must be a positive finite number");
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
+
+    const uint32_t k = (uint32_t)mcl.classes.size(), P = k * (k - 1) / 2;
+    std::vector<uint32_t> idx;
+    std::vector<signed char> y;
+    idx.reserve((size_t)(k - 1) * (size_t)n);
+    y.reserve((size_t)(k - 1) * (size_t)n);
+    std::vector<fsk::SvmProb> probs;
+    probs.reserve(P);
+    for (uint32_t a = 0; a < k; ++a)
+        for (uint32_t b = a + 1; b < k; ++b) {
+            fsk::SvmProb pr{};
+            pr.Cp = C * mcl.w[a];  // (each product once, one rounding)
+            pr.Cn = C * mcl.w[b];
+            pr.idx_off = idx.size();
+            pr.n = mc_pair_list(mcl.cls, a, b, [](uint32_t) { return true; }, &idx, &y);
+            probs.push_back(pr);
+        }
+
+    SvmState& S = e->svm;
+    SvmMcState& M = S.mc;
+    S.valid = false;  // (from here on the model slot's device state is written)
+    S.cal.valid = S.platt_valid = false;  // (the calibration belonged to the model this one replaces)
+    McSolved solved;
+    { int rc = mc_solve(e, M, src, probs, idx, y, eps, max_iter, &solved); if (rc) return rc; }
+    { int rc = mc_upload_classes(e, M, mcl.classes); if (rc) return rc; }
+
+    std::vector<char> sv((size_t)n, 0);
+    M.pairs.assign(P, fsk_svm_multiclass_pair{});
+    for (uint32_t p = 0, a = 0; a < k; ++a)
+        for (uint32_t b = a + 1; b < k; ++b, ++p) {
+            const fsk::SvmProb& pr = probs[p];
+            fsk_svm_multiclass_pair& o = M.pairs[p];
+            o.class_a = mcl.classes[a];
+            o.class_b = mcl.classes[b];
+            o.n_rows = pr.n;
+            o.iterations = solved.status[p].iter;
+            o.gap = solved.status[p].gmax - solved.status[p].gmin;
+            o.objective = solved.fin[p].objective;
+            o.rho = solved.fin[p].rho;
+            o.n_sv = solved.fin[p].n_sv;
+            o.n_bsv = solved.fin[p].n_bsv;
+            o.converged = solved.status[p].converged;
+            for (uint32_t q = 0; q < pr.n; ++q)
+                if (solved.alpha[pr.st_off + q] > 0.0) sv[idx[pr.idx_off + q]] = 1;
+        }
+    M.alpha.swap(solved.alpha);
+    M.info = fsk_svm_multiclass_info{};
+    M.info.k = (int32_t)k;
+    M.info.n_pairs = (int32_t)P;
+    M.info.form = solved.form;
+    M.info.launches = solved.launches;
+    M.info.n_sv = (int64_t)std::count(sv.begin(), sv.end(), (char)1);
+    M.info.n_alpha = (int64_t)M.alpha.size();
+    M.info.ms = now_ms() - t0;
+    S.model_kind = MODEL_MC;
+    S.valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_get_model(fsk_engine* e, int32_t* classes, fsk_svm_multiclass_pair* pairs, double* alpha, fsk_svm_multiclass_info* info) {
+    if (!e) return FSK_EINVAL;
+    int rc = model_of_kind(e, MODEL_MC, "fsk_svm_multiclass_get_model");
+    if (rc) return rc;
+    const SvmMcState& M = e->svm.mc;
+    if (classes) memcpy(classes, M.classes.data(), M.classes.size() * sizeof(int32_t));
+    if (pairs) memcpy(pairs, M.pairs.data(), M.pairs.size() * sizeof(fsk_svm_multiclass_pair));
+    if (alpha) memcpy(alpha, M.alpha.data(), M.alpha.size() * sizeof(double));
+    if (info) *info = M.info;
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dec, int32_t* pred) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_decision_args(e, "fsk_svm_multiclass_decision", r0, r1);
+    if (rc || r0 == r1 || (!dec && !pred)) return rc;
+    FSK_ON_DEVICE(e);
+    SvmMcState& M = e->svm.mc;
+    const size_t rows = (size_t)(r1 - r0);
+    if (dec) FSK_HIP(M.d_dec.reserve(rows * M.P));
+    if (pred) FSK_HIP(M.d_pred.reserve(rows));
+    rc = mc_launch_decision(e, r0, r1, dec ? M.d_dec.p : nullptr, pred ? M.d_pred.p : nullptr);
+    if (rc) return rc;
+    if (dec) FSK_HIP(hipMemcpyAsync(dec, M.d_dec.p, rows * M.P * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (pred) FSK_HIP(hipMemcpyAsync(pred, M.d_pred.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_dec, int32_t* device_pred) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_decision_args(e, "fsk_svm_multiclass_decision_device", r0, r1);
+    if (rc || r0 == r1 || (!device_dec && !device_pred)) return rc;
+    FSK_ON_DEVICE(e);
+    rc = mc_launch_decision(e, r0, r1, device_dec, device_pred);
+    if (rc) return rc;
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+                          const double* class_weight, double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
+    if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);  // (before the arrays: an empty Cs may be null)
+    McClasses mcl;
+    { int rcc = mc_check(e, fold && Cs ? labels : nullptr, "null labels, fold or Cs", n, eps, class_weight, &mcl); if (rcc) return rcc; }
+    const uint32_t k = (uint32_t)mcl.classes.size(), P = k * (k - 1) / 2;
+    if ((int64_t)n_C * n_folds * P > FSK_SVM_CV_MAX_PROBLEMS)
+        return e->fail(FSK_EINVAL, "%d folds x %d values of C x %u pairs are more than %d problems", n_folds, n_C, P, FSK_SVM_CV_MAX_PROBLEMS);
+    for (int32_t c = 0; c < n_C; ++c)
+        if (!(Cs[c] > 0.0) || !std::isfinite(Cs[c])) return e->fail(FSK_EINVAL, "C %d must be a positive finite number", c);
+    const uint32_t F = (uint32_t)n_folds, nC = (uint32_t)n_C, G = F * nC, nn = (uint32_t)n;
+    std::vector<int64_t> rows(F, 0), of_class(k, 0), held((size_t)F * k, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        if (fold[t] < 0 || fold[t] >= n_folds) return e->fail(FSK_EINVAL, "fold of row %lld is %d: folds are 0..%d", (long long)t, fold[t], n_folds - 1);
+        ++rows[fold[t]];
+        ++of_class[mcl.cls[(size_t)t]];
+        ++held[(size_t)fold[t] * k + mcl.cls[(size_t)t]];
+    }
+    for (uint32_t f = 0; f < F; ++f) {
+        if (rows[f] == 0) return e->fail(FSK_EINVAL, "fold %u has no rows", f);
+        for (uint32_t c = 0; c < k; ++c)
+            if (held[(size_t)f * k + c] == of_class[c])
+                return e->fail(FSK_EINVAL, "class %d has no row among the training rows of fold %u", mcl.classes[c], f);
+    }
+    if (max_iter < 0) max_iter = SVM_DEFAULT_MAX_ITER;
+    FSK_ON_DEVICE(e);
+    { int rcz = materialise_zero(e); if (rcz) return rcz; }
+    SvmSource src;
+    { int rcs = svm_source(e, true, &src); if (rcs) return rcs; }
+
+    // the lists of (f, pair) once, a problem for every (c, f, pair): p = (c F + f) P + pair
+    std::vector<uint32_t> idx;
+    std::vector<signed char> y;
+    std::vector<u64> list_off((size_t)F * P);
+    std::vector<uint32_t> list_n((size_t)F * P);
+    for (uint32_t f = 0; f < F; ++f)
+        for (uint32_t p = 0, a = 0; a < k; ++a)
+            for (uint32_t b = a + 1; b < k; ++b, ++p) {
+                list_off[(size_t)f * P + p] = idx.size();
+                list_n[(size_t)f * P + p] = mc_pair_list(mcl.cls, a, b, [&](uint32_t t) { return (uint32_t)fold[t] != f; }, &idx, &y);
+            }
+    std::vector<fsk::SvmProb> probs((size_t)G * P);
+    for (uint32_t g = 0; g < G; ++g)
+        for (uint32_t p = 0, a = 0; a < k; ++a)
+            for (uint32_t b = a + 1; b < k; ++b, ++p) {
+                fsk::SvmProb& pr = probs[(size_t)g * P + p];
+                pr = fsk::SvmProb{};
+                pr.Cp = Cs[g / F] * mcl.w[a];  // (each product once, one rounding)
+                pr.Cn = Cs[g / F] * mcl.w[b];
+                pr.idx_off = list_off[(size_t)(g % F) * P + p];
+                pr.n = list_n[(size_t)(g % F) * P + p];
+            }
+
+    SvmMcState& M = e->svm.mc_cv;
+    FSK_HIP(M.d_fold.reserve(nn));
+    FSK_HIP(M.d_pred.reserve((size_t)nC * nn));
+    M.valid = false;  // (from here on the earlier result's buffers are written)
+    McSolved solved;
+    { int rc = mc_solve(e, M, src, probs, idx, y, eps, max_iter, &solved); if (rc) return rc; }
+    { int rc = mc_upload_classes(e, M, mcl.classes); if (rc) return rc; }
+    FSK_HIP(hipMemcpyAsync(M.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    {
+        const dim3 grid((nn + 3) / 4, nC);
+        const double *diag = src.diag, *coef = M.d_coef.p, *rho = M.d_rho.p;
+        const fsk::SvmProb* dp = reinterpret_cast<const fsk::SvmProb*>(M.d_prob.p);
+        const uint32_t *di = M.d_idx.p, *ab = M.d_ab.p;
+        const int32_t *classes = M.d_classes.p, *df = M.d_fold.p;
+        int32_t* out = M.d_pred.p;
+        svm_on_source(src, [=](auto* K) -> int {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_ovo_decision_oof<SrcOf<decltype(K)>>), grid, dim3(256), 0, e->stream, K, diag, dp, di, coef, rho, ab,
+                       classes, P, df, F, nn, out);
+            return FSK_OK;
+        });
+    }
+    M.oof.resize((size_t)nC * nn);
+    FSK_HIP(hipMemcpyAsync(M.oof.data(), M.d_pred.p, M.oof.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+
+    M.scores.assign(nC, fsk_svm_cv_score{});
+    for (uint32_t c = 0; c < nC; ++c) {
+        int64_t right = 0;
+        for (uint32_t t = 0; t < nn; ++t) right += M.oof[(size_t)c * nn + t] == labels[t];
+        M.scores[c].C = Cs[c];
+        M.scores[c].auc = NAN;  // (no AUC for more than two classes)
+        M.scores[c].accuracy = (double)right / (double)n;
+    }
+    M.problems.assign((size_t)G * P, fsk_svm_cv_problem{});
+    for (uint32_t g = 0; g < G; ++g)
+        for (uint32_t p = 0, a = 0; a < k; ++a)
+            for (uint32_t b = a + 1; b < k; ++b, ++p) {
+                const size_t at = (size_t)g * P + p;
+                fsk_svm_cv_problem& o = M.problems[at];
+                o.n_rows = probs[at].n;
+                o.iterations = solved.status[at].iter;
+                o.gap = solved.status[at].gmax - solved.status[at].gmin;
+                o.objective = solved.fin[at].objective;
+                o.rho = solved.fin[at].rho;
+                o.C = Cs[g / F];
+                o.n_sv = solved.fin[at].n_sv;
+                o.n_bsv = solved.fin[at].n_bsv;
+                o.converged = solved.status[at].converged;
+                o.fold = (int32_t)(g % F);
+                o.reserved[0] = (double)mcl.classes[a];
+                o.reserved[1] = (double)mcl.classes[b];
+            }
+    M.cv_info = fsk_svm_cv_info{};
+    M.cv_info.n = n;
+    M.cv_info.n_folds = n_folds;
+    M.cv_info.n_C = n_C;
+    M.cv_info.form = solved.form;
+    M.cv_info.reserved0 = (int32_t)k;
+    M.cv_info.launches = solved.launches;
+    M.cv_info.ms = now_ms() - t0;
+    M.valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_cv_get(fsk_engine* e, int32_t* pred, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_cv_ready(e);
+    if (rc) return rc;
+    const SvmMcState& M = e->svm.mc_cv;
+    if (pred) memcpy(pred, M.oof.data(), M.oof.size() * sizeof(int32_t));
+    if (scores) memcpy(scores, M.scores.data(), M.scores.size() * sizeof(fsk_svm_cv_score));
+    if (problems) memcpy(problems, M.problems.data(), M.problems.size() * sizeof(fsk_svm_cv_problem));
+    if (info) *info = M.cv_info;
+    return FSK_OK;
+}
 
 int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, double eps, int64_t max_iter) {
     if (!e) return FSK_EINVAL;

@@ -1,6 +1,6 @@
 // fsk_kernels_svm.h — a C-SVC dual solver and its decision values on the RESIDENT result triangle (fsk_svm_train,
-// fsk_svm_decision), and the same solver over the twin elements of an epsilon-SVR (fsk_svr_train, fsk_svr_cv: the last
-// section). Included by fsk_engine_svm.hip only.
+// fsk_svm_decision), the pairs' decision values and the vote of a one-vs-one multi-class model (k_svm_ovo_decision), and the same
+// solver over the twin elements of an epsilon-SVR (fsk_svr_train, fsk_svr_cv: the last section). Included by fsk_engine_svm.hip only.
 //
 // The kernel is cosine-normalised: every K(t,t) is 1, the whole matrix is on the device, so the solver is SMO with LIBSVM's
 // second-order working-set selection and nothing else — no row cache, no shrinking. A row of Q is read where it lies: cells
@@ -544,6 +544,84 @@ __global__ __launch_bounds__(256) void k_svm_decision_oof(const SrcT* K, const d
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
     if (live && lane == 0) out[(size_t)blockIdx.y * n_train + t] = __dsub_rn(acc, rho[p]);
+}
+
+// =============================================================================================
+// ONE-VS-ONE: THE PAIRS' DECISION VALUES AND THE VOTE OF ONE ROW (fsk_svm_multiclass_decision, fsk_svm_multiclass_cv). One wave
+// a row r of the N-set, as k_svm_decision. For every pair p of the P = k (k - 1) / 2 in turn the wave computes
+//   dec_p(r) = sum_q coef_p[q] K(r, idx_p[q]) - rho_p
+// over the pair's OWN row list (the SvmProb of its solve: idx at idx_off, coef = alpha y at st_off, both at the pair's
+// length n_p): a lane takes the positions lane, lane + 64, ... of the list in order, one __dmul_rn and one __dadd_rn a term,
+// zero coefficients skipped with their cell; then the six xor-shuffle stages (every lane ends with the same sum: a + b is
+// b + a to the bit) and __dsub_rn of rho_p — the summation of k_svm_decision over a list. Cells through svm_cell: r may be a
+// train or a test row, a list holds train rows only, so no test x test cell is read.
+// WHAT A ROW READS: sum_p n_p = (k - 1) n_train coefficients (every training row is in k - 1 lists) and as many row numbers
+// where the coefficient is not zero, and the cells of the non-zero ones — a cell once for every pair it is a support vector
+// of, not once a row.
+// THE VOTE (LIBSVM's): dec_p > 0 gives class a a vote, anything else (a NaN too) class b. Lane c counts class c (k <= 64), in a
+// register: no scratch, no LDS. The winner goes over the lanes by xor shuffles of (votes, lane), the lower lane among equals.
+// THE LAUNCH: 256 threads, a wave a SIMD, no LDS and no barrier (the waves share nothing), so occupancy is the registers' alone.
+// The P values of a row are held one a lane — pair p by lane p mod 64 — and written 64 at a time: consecutive lanes, consecutive
+// doubles of the row-major [rows][P] array.
+template <typename SrcT>
+__device__ __forceinline__ void svm_ovo_row(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                            const double* coef_all, const double* rho, const uint32_t* ab, const int32_t* classes,
+                                            uint32_t P, uint32_t r, bool live, double* dec_row, int32_t* pred_out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    int votes = 0;
+    double keep = 0.0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const SvmProb pr = probs[p];
+        const uint32_t* idx = idx_all + pr.idx_off;
+        const double* coef = coef_all + pr.st_off;
+        double acc = 0.0;
+        if (live)
+            for (uint32_t q = lane; q < pr.n; q += 64u) {
+                const double c = coef[q];
+                if (c != 0.0) acc = __dadd_rn(acc, __dmul_rn(c, svm_cell(K, diag, r, idx[q])));
+            }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
+        const double v = __dsub_rn(acc, rho[p]);
+        const uint32_t w = ab[p], winner = v > 0.0 ? (w & 0xffffu) : (w >> 16);
+        votes += lane == winner;
+        if ((p & 63u) == lane) keep = v;
+        if (((p & 63u) == 63u || p + 1 == P) && live && dec_row && lane <= (p & 63u)) dec_row[(p & ~63u) + lane] = keep;
+    }
+    int best = (int)lane;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int ov = __shfl_xor(votes, d), ob = __shfl_xor(best, d);
+        if (ov > votes || (ov == votes && ob < best)) { votes = ov; best = ob; }
+    }
+    if (live && pred_out && lane == 0) *pred_out = classes[best];
+}
+
+// rows [r0, r1) of the N-set under the model's P pairs: dec [r1 - r0][P] and / or pred [r1 - r0], either may be null
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_ovo_decision(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                                          const double* coef_all, const double* rho, const uint32_t* ab,
+                                                          const int32_t* classes, uint32_t P, uint32_t r0, uint32_t r1, double* dec,
+                                                          int32_t* pred) {
+    const uint32_t r = r0 + blockIdx.x * 4u + (threadIdx.x >> 6);
+    const bool live = r < r1;  // (a dead wave reads and writes nothing: shuffles are per wave)
+    const size_t at = live ? (size_t)(r - r0) : 0;
+    svm_ovo_row(K, diag, probs, idx_all, coef_all, rho, ab, classes, P, r, live, dec ? dec + at * P : nullptr, pred ? pred + at : nullptr);
+}
+
+// OUT OF FOLD: for the value of C blockIdx.y and training row t the pairs' models are those of the problem group
+// (c n_folds + fold[t]) — problems (c n_folds + fold[t]) P + p, none of which trained on t — as k_svm_decision_oof picks the
+// one problem of the binary case. pred [n_C][n_train]; train x train cells only.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_ovo_decision_oof(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                                              const double* coef_all, const double* rho, const uint32_t* ab,
+                                                              const int32_t* classes, uint32_t P, const int32_t* fold, uint32_t n_folds,
+                                                              uint32_t n_train, int32_t* pred) {
+    const uint32_t t = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const bool live = t < n_train;
+    const size_t g = (size_t)blockIdx.y * n_folds + (live ? (uint32_t)fold[t] : 0u);
+    svm_ovo_row(K, diag, probs + g * P, idx_all, coef_all, rho + g * P, ab, classes, P, t, live, (double*)nullptr,
+                pred + (size_t)blockIdx.y * n_train + (live ? t : 0u));
 }
 
 // =============================================================================================

@@ -56,6 +56,14 @@ class Vocabulary(object):
             assert got == idx, "vocabulary changed under the reader"
 
 
+def _is_int(text):
+    try:
+        int(text)
+        return True
+    except ValueError:
+        return False
+
+
 class MalformedFasta(AssertionError, ValueError):
     """The file is not alternating ``>label`` / sequence lines with labels in {-1, 0, 1} (where the
     reference's reader fails an ``assert``, ``utils.py:80-94``)."""
@@ -139,15 +147,22 @@ class FastaUtility:
             out.append(v)
         return out if regression else np.asarray(out, dtype=np.int64)
 
-    def read_data(self, data_file, vocab="inferred", regression=False):
+    def read_data(self, data_file, vocab="inferred", regression=False, multiclass=False):
         """``(X, Y)``: token-id lists and labels of ``data_file`` — the reference's return value
-        (``utils.py:50-96``). Labels are ints in {-1, 0, 1}; with ``regression`` the label text."""
+        (``utils.py:50-96``). Labels are ints in {-1, 0, 1}; with ``regression`` the label text; with
+        ``multiclass`` any integers (what ``fit_svm_multiclass`` takes), ``MalformedFasta`` on a label
+        that is no integer."""
         assert vocab.lower() in ["dna", "protein", "inferred"]
-        if regression:  # free-text labels: tokens as usual, labels re-read as text
+        if regression or multiclass:  # free-text labels: tokens as usual, labels re-read as text
             with open(data_file, "r") as f:
                 label_lines = [ln.strip().lower() for ln in f.read().split("\n")[0::2]]
             tokens, offsets, _ = self._read_text(data_file, want_labels=False)
             Y = self._labels(label_lines[:len(offsets) - 1], regression=True)
+            if multiclass and not regression:
+                try:
+                    Y = [int(v) for v in Y]
+                except ValueError:
+                    raise MalformedFasta("expected integer labels, got %r" % next(v for v in Y if not _is_int(v))) from None
         else:
             tokens, offsets, labels = self.read_packed(data_file)
             Y = labels.tolist()

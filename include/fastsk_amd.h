@@ -41,7 +41,9 @@ extern "C" {
                                   fsk_svm_set_kernel / fsk_svm_get_kernel;
                                   fsk_svm_set_class_weights / fsk_svm_get_class_weights, fsk_svm_platt_fit, fsk_svm_calibrate,
                                   fsk_svm_get_calibration, fsk_svm_proba and fsk_svm_platt_info;
-                                  fsk_svr_train, fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get and fsk_svr_cv_score) */
+                                  fsk_svr_train, fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get and fsk_svr_cv_score;
+                                  fsk_svm_train_multiclass, fsk_svm_multiclass_get_model, fsk_svm_multiclass_decision(_device),
+                                  fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get and their two structs) */
 
 enum {
     FSK_OK = 0,
@@ -621,6 +623,73 @@ int fsk_svr_cv(fsk_engine* e, const double* targets, int64_t n, const int32_t* f
                const double* epsilons, int32_t n_eps, double eps, int64_t max_iter);
 /* oof[n_C n_eps n], scores[n_C n_eps], problems[n_C n_eps n_folds], *info of the last fsk_svr_cv: every one may be NULL */
 int fsk_svr_cv_get(fsk_engine* e, double* oof, fsk_svr_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info);
+
+/* ---- multi-class C-SVC, one-vs-one, on the resident triangle: what LIBSVM's C-SVC does with more than two classes, every
+ * pair of classes solved side by side in the batch launches of fsk_svm_cv.
+ *
+ * fsk_svm_train_multiclass: labels[t], t < n = n_train, are any int32 values; the classes are the distinct values in ascending
+ * order, classes[0] < ... < classes[k-1], 2 <= k <= FSK_SVM_MAX_CLASSES (more: FSK_EUNSUPPORTED). Pair p runs over (a, b),
+ * a < b, in lexicographic order of the class indices (P = k (k - 1) / 2; scikit-learn's decision_function_shape="ovo" order).
+ * Its problem is the training rows of class a or b IN ASCENDING ROW ORDER, class a as y = +1 and class b as y = -1, with the
+ * boxes Cp = C w[a], Cn = C w[b] (class_weight[k] by class index, each product formed once; NULL: every w = 1). The class
+ * weights of fsk_svm_set_class_weights are neither consulted nor changed; fsk_svm_set_kernel applies as to fsk_svm_train. A
+ * pair is fsk_svm_train's algorithm on its sub-matrix, to the bit, whichever form ran (form 1 while the LARGEST pair has at
+ * most svm_wg_max rows), finished on the host as a problem of fsk_svm_cv is.
+ * NOT LIBSVM'S ORDER: LIBSVM groups the rows by class before it solves a pair (all of class a, then all of class b). The
+ * sub-problems here are in ascending row order, so that every tie falls as in fsk_svm_train on the same rows: a pair's alpha
+ * equals this project's restatement bit for bit, and LIBSVM's only within the stopping tolerance.
+ * The model takes the one model slot: fsk_svm_get_model, fsk_svm_decision(_device), fsk_svm_calibrate,
+ * fsk_svm_get_calibration, fsk_svm_proba and fsk_svr_get_model then return FSK_ESTATE with a message that names the model, and
+ * the calls below return it on a C-SVC or an SVR model. A later fsk_svm_train or fsk_svr_train replaces it; what drops a model
+ * drops it. FSK_EINVAL: n != n_train, one class only, a weight, C or eps that is not a positive finite number. A refused call
+ * leaves the earlier model as it was.
+ * fsk_svm_multiclass_get_model: classes[k], pairs[P], alpha (the pairs' alpha one after another in pair order, pair p at its
+ * own length n_rows and in its own row order: (k - 1) n_train values in all), *info; every one may be NULL (call with info
+ * alone to learn k).
+ * fsk_svm_multiclass_decision: for rows r0 <= r < r1 <= N of the sequences, dec[(r - r0) P + p] = sum_q coef_p[q] K(r, row_p[q])
+ * - rho_p over pair p's own row list — a lane of a wave takes the list positions lane, lane + 64, ... in order, zero
+ * coefficients skipped, then the xor shuffles, as fsk_svm_decision sums — and pred[r - r0] the label that wins LIBSVM's vote:
+ * dec_p > 0 votes for class a, anything else for class b; most votes win, the lowest class among equals. Either output may be
+ * NULL. Only cells with a train column are read. The _device form writes DEVICE memory of the caller.
+ *
+ * fsk_svm_multiclass_cv: problem (c n_folds + f) P + p trains pair p at Cs[c] on its rows with fold[t] != f; all n_C n_folds P
+ * <= FSK_SVM_CV_MAX_PROBLEMS problems in one batch. The out-of-fold label of row t at Cs[c] is the vote of the P problems of
+ * (c, fold[t]); accuracy[c] = #{t: label == labels[t]} / n, an integer count divided once. There is no AUC for more than two
+ * classes: fsk_svm_cv_score.auc is NaN. fsk_svm_cv_problem.reserved[0], [1] hold the pair's class_a, class_b (label values,
+ * exact in a double); fsk_svm_cv_info.reserved0 holds k. FSK_EINVAL, beyond fsk_svm_cv's refusals (which stay, but for the
+ * label values): a fold whose training rows hold no row of some class, the message naming the class and the fold. The result
+ * lives beside fsk_svm_cv's: neither call disturbs the other's, nor any model. */
+#define FSK_SVM_MAX_CLASSES 64  /* one vote counter a lane of a wave */
+typedef struct fsk_svm_multiclass_pair {
+    int32_t class_a, class_b;   /* label values: y = +1 / y = -1 of the pair's problem                   */
+    int64_t n_rows, iterations;
+    double gap, objective, rho;
+    int64_t n_sv, n_bsv;
+    int32_t converged, reserved0;
+    double reserved[2];
+} fsk_svm_multiclass_pair;
+typedef struct fsk_svm_multiclass_info {
+    int32_t k, n_pairs;
+    int32_t form;            /* 1: one workgroup a pair (k_svm_wg_batch); 2: two launches an iteration      */
+    int32_t reserved0;
+    int64_t launches;        /* kernel launches of the solves                                               */
+    int64_t n_sv;            /* training rows that are a support vector of any pair                         */
+    int64_t n_alpha;         /* length of the concatenated alpha: (k - 1) n_train                           */
+    double ms;               /* host time of fsk_svm_train_multiclass                                       */
+    double reserved[4];
+} fsk_svm_multiclass_info;
+int fsk_svm_train_multiclass(fsk_engine* e, const int32_t* labels, int64_t n, double C, const double* class_weight, double eps,
+                             int64_t max_iter);
+int fsk_svm_multiclass_get_model(fsk_engine* e, int32_t* classes, fsk_svm_multiclass_pair* pairs, double* alpha,
+                                 fsk_svm_multiclass_info* info);
+int fsk_svm_multiclass_decision(fsk_engine* e, int64_t r0, int64_t r1, double* dec, int32_t* pred);
+int fsk_svm_multiclass_decision_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_dec, int32_t* device_pred);
+int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs,
+                          int32_t n_C, const double* class_weight, double eps, int64_t max_iter);
+/* pred[n_C n] (out-of-fold labels), scores[n_C], problems[n_C n_folds P], *info of the last fsk_svm_multiclass_cv: every one
+ * may be NULL */
+int fsk_svm_multiclass_cv_get(fsk_engine* e, int32_t* pred, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems,
+                              fsk_svm_cv_info* info);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
