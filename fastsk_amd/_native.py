@@ -166,7 +166,9 @@ SYMBOLS = ["fsk_create", "fsk_destroy", "fsk_last_error", "fsk_abi_version", "fs
            "fsk_svm_set_class_weights", "fsk_svm_get_class_weights", "fsk_svm_platt_fit", "fsk_svm_calibrate",
            "fsk_svm_get_calibration", "fsk_svm_proba", "fsk_svr_train", "fsk_svr_get_model", "fsk_svr_cv", "fsk_svr_cv_get",
            "fsk_svm_train_multiclass", "fsk_svm_multiclass_get_model", "fsk_svm_multiclass_decision",
-           "fsk_svm_multiclass_decision_device", "fsk_svm_multiclass_cv", "fsk_svm_multiclass_cv_get"]
+           "fsk_svm_multiclass_decision_device", "fsk_svm_multiclass_cv", "fsk_svm_multiclass_cv_get",
+           "fsk_svm_multiclass_calibrate", "fsk_svm_multiclass_get_calibration", "fsk_svm_multiclass_set_calibration",
+           "fsk_svm_multiclass_proba", "fsk_svm_multiclass_proba_device", "fsk_exp_neg"]
 
 
 _hip_shared = False
@@ -336,6 +338,12 @@ class Library:
             "fsk_svm_multiclass_decision_device": ([vp, i64, i64, vp, vp], C.c_int),
             "fsk_svm_multiclass_cv": ([vp, vp, i64, vp, i32, vp, i32, vp, C.c_double, i64], C.c_int),
             "fsk_svm_multiclass_cv_get": ([vp, vp, vp, vp, C.POINTER(SvmCvInfo)], C.c_int),
+            "fsk_svm_multiclass_calibrate": ([vp, vp, i32], C.c_int),
+            "fsk_svm_multiclass_get_calibration": ([vp, vp, vp], C.c_int),
+            "fsk_svm_multiclass_set_calibration": ([vp, vp, vp], C.c_int),
+            "fsk_svm_multiclass_proba": ([vp, i64, i64, vp, vp, vp], C.c_int),
+            "fsk_svm_multiclass_proba_device": ([vp, i64, i64, vp, vp, vp], C.c_int),
+            "fsk_exp_neg": ([C.c_double], C.c_double),
         }
         for name, (argtypes, restype) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -395,6 +403,10 @@ class Library:
         if rc:
             raise FskError(rc, "fsk_svm_platt_fit refused its arguments")
         return {"A": info.A, "B": info.B, "iterations": info.iterations, "status": info.status}
+
+    def exp_neg(self, x):
+        """``fsk_exp_neg``: exp(x) for x <= 0 as the fixed sequence of IEEE operations the probability kernel uses (host only)."""
+        return float(self.L.fsk_exp_neg(float(x)))
 
     def tuning_keys(self):
         """{key: (default, lowest, highest, what it does)} — every knob fsk_set_tuning / FSK_TUNING takes."""
@@ -1234,6 +1246,57 @@ class Engine:
         return {"pred": pred, "accuracy": np.array([s.accuracy for s in scores]),
                 "problems": [dict(q.as_dict(), class_a=int(q.reserved[0]), class_b=int(q.reserved[1])) for q in problems], "k": k,
                 "form": _FORMS.get(info.form, "none"), "launches": info.launches, "ms": info.ms}
+
+    def svm_multiclass_calibrate(self, fold, n_folds=None):
+        """``fsk_svm_multiclass_calibrate``: a Platt sigmoid for every pair of the model of ``svm_train_multiclass``, fitted on
+        the out-of-fold pair decisions of the folds ``fold[t]`` (0..F-1; F = ``n_folds``, the largest id + 1 when None), all
+        F * P problems solved side by side with the model's C, class weights, eps, max_iter and kernel kind. Returns
+        ``svm_multiclass_calibration()[1]``."""
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if fold.ndim != 1:
+            raise ValueError("fold must be 1-D")
+        if n_folds is None:
+            n_folds = int(fold.max()) + 1 if len(fold) else 0
+        if len(fold) != self.n_train:
+            raise ValueError("%d fold ids for %d training sequences" % (len(fold), self.n_train))
+        self._ck(self.lib.L.fsk_svm_multiclass_calibrate(self.h, fold.ctypes.data if len(fold) else None, int(n_folds)))
+        return self.svm_multiclass_calibration()[1]
+
+    def svm_multiclass_calibration(self):
+        """(the out-of-fold pair decisions [n_train, P] — None where ``svm_multiclass_set_calibration`` installed the sigmoids —
+        and the P fits: ``A``, ``B``, ``iterations``, ``status``, ``n_folds``, ``form``, ``launches``, ``ms``)."""
+        info = SvmMulticlassInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, None, None, None, C.byref(info)))
+        fits = (SvmPlattInfo * info.n_pairs)()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_calibration(self.h, None, C.addressof(fits)))
+        oof = None
+        if fits[0].n_folds:
+            oof = np.empty((self.n_train, info.n_pairs), dtype=np.float64)
+            self._ck(self.lib.L.fsk_svm_multiclass_get_calibration(self.h, oof.ctypes.data, None))
+        return oof, [f.as_dict() for f in fits]
+
+    def svm_multiclass_set_calibration(self, A, B):
+        """``fsk_svm_multiclass_set_calibration``: install the sigmoids ``A[p]``, ``B[p]`` of the P pairs without a solve."""
+        info = SvmMulticlassInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, None, None, None, C.byref(info)))
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if A.shape != (info.n_pairs,) or B.shape != (info.n_pairs,):
+            raise ValueError("A and B: one value a pair, %d pairs" % info.n_pairs)
+        self._ck(self.lib.L.fsk_svm_multiclass_set_calibration(self.h, A.ctypes.data, B.ctypes.data))
+
+    def svm_multiclass_proba(self, r0, r1, proba=True, predict=True, iterations=True):
+        """``fsk_svm_multiclass_proba``: (the class probabilities [r1 - r0, k] in the order of ``classes``, the label of the
+        largest [r1 - r0], the coupling's iterations [r1 - r0]) of rows [r0, r1); None for what is not asked for."""
+        info = SvmMulticlassInfo()
+        self._ck(self.lib.L.fsk_svm_multiclass_get_model(self.h, None, None, None, C.byref(info)))
+        rows = max(r1 - r0, 0)
+        prob = np.empty((rows, info.k), dtype=np.float64) if proba else None
+        pred = np.empty(rows, dtype=np.int32) if predict else None
+        iters = np.empty(rows, dtype=np.int32) if iterations else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._ck(self.lib.L.fsk_svm_multiclass_proba(self.h, r0, r1, ptr(prob), ptr(pred), ptr(iters)))
+        return prob, pred, iters
 
     def svm_cv_alpha(self, p):
         """alpha[n_train] of problem ``p`` of the last ``svm_cv``, zero at its held-out rows."""

@@ -16,6 +16,8 @@
 //     the epsilon-SVR on real-valued targets (fsk_svr_train / fsk_svr_cv), in the one model slot;
 //     fit_svm_multiclass(labels, C, ...), predict_class_np(which) and cross_validate_svm_multiclass(labels, Cs, folds, ...) the
 //     one-vs-one multi-class C-SVC on integer labels (fsk_svm_train_multiclass / fsk_svm_multiclass_cv), in the same slot;
+//     fit_svm_multiclass(probability=True), predict_proba_np / predict_proba_dlpack(which) and predict_class_np(rule="proba") its
+//     class probabilities by pairwise coupling (fsk_svm_multiclass_calibrate / fsk_svm_multiclass_proba);
 //     all of them take a trailing kernel_type = "fastsk" | "linear": "linear" is the reference's default, the SVM on the ROWS of
 //     the kernel, through the rows kernel (fsk_rows_build; get_rows_kernel_block_np, rows_kernel_info);
 //   - additive keyword arguments (device, devices, collective, deadline_ms, path, seed, skip_test_block, revcomp, weights, max_mismatches, wildcards, center_weights), numpy and
@@ -813,8 +815,8 @@ public:
     }
     // ---- multi-class C-SVC, one-vs-one (fsk_svm_train_multiclass): labels are any integers, the k (k - 1) / 2 pairs of classes
     // are solved side by side in one batch; the model takes the one model slot. decision_function_np then returns [rows, P],
-    // predict_class_np the voted labels; get_dual_coef_np, get_intercept and predict_proba_np raise RuntimeError naming the
-    // model (pairwise coupling of probabilities is not built). class_weight: None, "balanced" (n / (k count_c)) or a dict keyed
+    // predict_class_np the voted labels; get_dual_coef_np and get_intercept raise RuntimeError naming the model, and so does
+    // predict_proba_np until the model is calibrated (probability=True). class_weight: None, "balanced" (n / (k count_c)) or a dict keyed
     // by label (fastsk_amd._native.multiclass_weights).
     using WeightArray = py::array_t<double, py::array::c_style | py::array::forcecast>;
     static bool parse_multiclass_weight(const py::object& labels, const py::object& spec, WeightArray* w) {
@@ -830,13 +832,18 @@ public:
         d["objective"] = objective; d["rho"] = rho; d["n_sv"] = n_sv; d["n_bsv"] = n_bsv;
         return d;
     }
+    // probability=True: a Platt sigmoid a pair on the out-of-fold pair decisions of stratified_folds(labels, calibration_folds,
+    // seed) (fsk_svm_multiclass_calibrate); predict_proba_np then gives [rows, k], predict_class_np(rule="proba") its argmax.
     py::dict fit_svm_multiclass(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels, double C, double eps, int64_t max_iter,
-                                const std::string& kernel_type, py::object class_weight) {
+                                const std::string& kernel_type, py::object class_weight, bool probability, int32_t calibration_folds,
+                                uint64_t seed) {
         const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one integer per training sequence");
         WeightArray w;
         const bool weighted = parse_multiclass_weight(labels, class_weight, &w);
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> fold;
+        if (probability) fold = py::module_::import("fastsk_amd._native").attr("stratified_folds")(labels, calibration_folds, seed);
         check(fsk_svm_set_kernel(h_, kind));
         int rc;
         {
@@ -861,15 +868,39 @@ public:
         d["classes"] = classes; d["pairs"] = pl; d["k"] = mi.k; d["n_pairs"] = mi.n_pairs; d["n_sv"] = mi.n_sv; d["converged"] = converged;
         d["form"] = mi.form == 1 ? "workgroup" : "two-launch"; d["launches"] = mi.launches; d["ms"] = mi.ms; d["kernel_type"] = kernel_type;
         if (weighted) d["class_weight"] = w; else d["class_weight"] = py::none();
+        if (probability) {
+            if (fold.ndim() != 1 || fold.shape(0) != labels.shape(0)) throw py::value_error("one fold id per label");
+            {
+                py::gil_scoped_release nogil;
+                rc = fsk_svm_multiclass_calibrate(h_, fold.data(), calibration_folds);
+            }
+            check(rc);
+            std::vector<fsk_svm_platt_info> fits((size_t)mi.n_pairs);
+            check(fsk_svm_multiclass_get_calibration(h_, nullptr, fits.data()));
+            py::list per_pair;
+            for (const fsk_svm_platt_info& q : fits) {
+                py::dict one;
+                one["A"] = q.A; one["B"] = q.B; one["iterations"] = q.iterations; one["status"] = q.status;
+                per_pair.append(one);
+            }
+            const fsk_svm_platt_info& q = fits[0];  // (what belongs to the whole call is in every fit)
+            py::dict platt;
+            platt["pairs"] = per_pair; platt["n_folds"] = q.n_folds; platt["form"] = q.form == 1 ? "workgroup" : "two-launch";
+            platt["launches"] = q.launches; platt["ms"] = q.ms;
+            d["platt"] = platt;
+        }
         return d;
     }
-    // the voted label of the test (or train) rows under the model of fit_svm_multiclass: LIBSVM's rule, the lowest class among
-    // equal vote counts
-    py::array_t<int32_t> predict_class_np(const std::string& which) const {
+    // the label of the test (or train) rows under the model of fit_svm_multiclass. rule="vote": LIBSVM's vote, the lowest class
+    // among equal vote counts (svm_predict). rule="proba": the class of the largest coupled probability, the lowest among equals
+    // (svm_predict_probability's label; needs probability=True).
+    py::array_t<int32_t> predict_class_np(const std::string& which, const std::string& rule) const {
+        if (rule != "vote" && rule != "proba") throw py::value_error("rule must be 'vote' or 'proba'");
         int64_t r0, r1;
         decision_rows(which, &r0, &r1);
         py::array_t<int32_t> out((py::ssize_t)(r1 - r0));
-        check(fsk_svm_multiclass_decision(h_, r0, r1, nullptr, out.mutable_data()));
+        if (rule == "proba") check(fsk_svm_multiclass_proba(h_, r0, r1, nullptr, out.mutable_data(), nullptr));
+        else check(fsk_svm_multiclass_decision(h_, r0, r1, nullptr, out.mutable_data()));
         return out;
     }
     // cross-validation of the multi-class C-SVC over folds and values of C, every (C, fold, pair) problem in one batch
@@ -877,7 +908,8 @@ public:
     // of equals (there is no AUC for more than two classes); refit=True then trains fit_svm_multiclass(labels, C=best_C).
     py::dict cross_validate_svm_multiclass(py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels,
                                            py::array_t<double, py::array::c_style | py::array::forcecast> Cs, py::object folds, double eps,
-                                           int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type, py::object class_weight) {
+                                           int64_t max_iter, uint64_t seed, bool refit, const std::string& kernel_type, py::object class_weight,
+                                           bool probability, int32_t calibration_folds) {
         const int32_t kind = parse_kernel_type(kernel_type);  // (ValueError before any device call)
         if (!computed_) throw std::runtime_error("call compute_kernel or compute_train first");
         if (labels.ndim() != 1) throw py::value_error("labels must be 1-D, one integer per training sequence");
@@ -937,7 +969,7 @@ public:
                 for (py::ssize_t c = 0; c < classes.shape(0); ++c) by_label[py::int_(classes.data()[c])] = w.data()[c];
                 cw = by_label;
             }
-            d["refit"] = fit_svm_multiclass(labels, scores[(size_t)best].C, eps, max_iter, kernel_type, cw);
+            d["refit"] = fit_svm_multiclass(labels, scores[(size_t)best].C, eps, max_iter, kernel_type, cw, probability, calibration_folds, seed);
         }
         return d;
     }
@@ -980,13 +1012,39 @@ public:
         check(fsk_svm_decision(h_, r0, r1, out.mutable_data()));
         return out;
     }
-    // P(y = +1) of the test (or train) rows: the calibration's sigmoid of the decision values (fsk_svm_proba), a host array
+    // P(y = +1) of the test (or train) rows: the calibration's sigmoid of the decision values (fsk_svm_proba), a host array.
+    // With the calibrated model of fit_svm_multiclass(probability=True): [rows, k], the coupled class probabilities of
+    // fsk_svm_multiclass_proba, columns in the order of `classes`; uncalibrated it raises, naming the model.
     py::array_t<double> predict_proba_np(const std::string& which) const {
         int64_t r0, r1;
         decision_rows(which, &r0, &r1);
+        fsk_svm_multiclass_info mi;
+        if (fsk_svm_multiclass_get_model(h_, nullptr, nullptr, nullptr, &mi) == FSK_OK) {
+            if (fsk_svm_multiclass_get_calibration(h_, nullptr, nullptr) != FSK_OK)
+                throw std::runtime_error("predict_proba_np: the model is a multi-class C-SVC (fsk_svm_train_multiclass) without a calibration: "
+                                         "fit_svm_multiclass(..., probability=True)");
+            py::array_t<double> prob({(py::ssize_t)(r1 - r0), (py::ssize_t)mi.k});
+            check(fsk_svm_multiclass_proba(h_, r0, r1, prob.mutable_data(), nullptr, nullptr));
+            return prob;
+        }
         py::array_t<double> out((py::ssize_t)(r1 - r0));
         check(fsk_svm_proba(h_, r0, r1, out.mutable_data()));
         return out;
+    }
+    // the same [rows, k] left on the device (fsk_svm_multiclass_proba_device), no copy; the multi-class model only
+    py::capsule predict_proba_dlpack(const std::string& which) {
+        int64_t r0, r1;
+        decision_rows(which, &r0, &r1);
+        if (r1 == r0) throw py::value_error("no rows");
+        fsk_svm_multiclass_info mi;
+        check(fsk_svm_multiclass_get_model(h_, nullptr, nullptr, nullptr, &mi));  // (RuntimeError before anything is allocated)
+        check(fsk_svm_multiclass_get_calibration(h_, nullptr, nullptr));
+        double* dev = nullptr;
+        check(fsk_alloc_block_device(h_, r0, r1, 0, mi.k, &dev));  // the engine's allocator: (r1 - r0) x k doubles
+        const int rc = fsk_svm_multiclass_proba_device(h_, r0, r1, dev, nullptr, nullptr);
+        if (rc != FSK_OK) (void)fsk_free_device(h_, dev);
+        check(rc);
+        return dlpack_of(dev, 2, r1 - r0, mi.k);
     }
     py::capsule decision_function_dlpack(const std::string& which) {
         int64_t r0, r1;
@@ -1088,11 +1146,14 @@ PYBIND11_MODULE(_fastsk, m) {
         .def("predict_np", &FastSK::decision_function_np, py::arg("which") = "test")
         .def("predict_dlpack", &FastSK::decision_function_dlpack, py::arg("which") = "test")
         .def("fit_svm_multiclass", &FastSK::fit_svm_multiclass, py::arg("labels"), py::arg("C") = 1.0, py::arg("eps") = 1e-3,
-             py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none())
-        .def("predict_class_np", &FastSK::predict_class_np, py::arg("which") = "test")
+             py::arg("max_iter") = -1, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none(),
+             py::arg("probability") = false, py::arg("calibration_folds") = 5, py::arg("seed") = 0)
+        .def("predict_class_np", &FastSK::predict_class_np, py::arg("which") = "test", py::arg("rule") = "vote")
+        .def("predict_proba_dlpack", &FastSK::predict_proba_dlpack, py::arg("which") = "test")
         .def("cross_validate_svm_multiclass", &FastSK::cross_validate_svm_multiclass, py::arg("labels"),
              py::arg("Cs") = std::vector<double>{1.0}, py::arg("folds") = 5, py::arg("eps") = 1e-3, py::arg("max_iter") = -1,
-             py::arg("seed") = 0, py::arg("refit") = false, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none())
+             py::arg("seed") = 0, py::arg("refit") = false, py::arg("kernel_type") = "fastsk", py::arg("class_weight") = py::none(),
+             py::arg("probability") = false, py::arg("calibration_folds") = 5)
         .def("stats", &FastSK::stats);
     // the level coefficients a_0..a_d of mismatch weights c_0..c_m at window length g (fsk_mismatch_levels; host only)
     m.def("mismatch_levels", [](int g, std::vector<uint64_t> weights) {

@@ -267,6 +267,18 @@ struct SvmMcState {
     std::vector<fsk_svm_cv_score> scores;        //                   [n_C]
     std::vector<fsk_svm_cv_problem> problems;    //                   [n_C n_folds P]
     fsk_svm_cv_info cv_info{};
+    // model: what it was trained with (fsk_svm_multiclass_calibrate solves the folds with the same), and its calibration — the
+    // pairs' sigmoids for k_svm_ovo_proba; cal_oof [n_train][P] is empty where fsk_svm_multiclass_set_calibration installed them
+    std::vector<int32_t> labels;
+    std::vector<double> w;
+    bool weighted = false;
+    double C = 0.0, eps = 0.0;
+    int64_t max_iter = 0;
+    bool cal_valid = false;
+    std::vector<double> cal_oof;
+    std::vector<fsk_svm_platt_info> fits;        // [P]
+    DevBuf<double> d_sigA, d_sigB, d_proba;
+    DevBuf<int32_t> d_iters;
     DevBuf<double> d_alpha, d_G, d_krow, d_coef, d_rho, d_dec;
     DevBuf<uint32_t> d_idx, d_ab;                // the row lists; a | b << 16 of every pair
     DevBuf<int32_t> d_classes, d_pred, d_fold;
@@ -278,6 +290,7 @@ struct SvmState {
     bool valid = false;
     SvmCvState cv;
     SvmMcState mc, mc_cv;            // the multi-class model (model_kind 2) and the result of the last fsk_svm_multiclass_cv
+    SvmMcState mc_cal;               // the fold solves of the last fsk_svm_multiclass_calibrate (its results are the model's)
     int model_kind = 0;              // of the one model slot: 0 a C-SVC (fsk_svm_train), 1 an epsilon-SVR (fsk_svr_train), 2 a one-vs-one multi-class C-SVC
     std::vector<double> alpha;       // [n_train]; of an SVR model [2 n_train]: alpha, then alpha*
     std::vector<double> coef;        // SVR model: [n_train], alpha - alpha*

@@ -2,8 +2,9 @@
 // fsk_svm_cv, fsk_svm_cv_get(_alpha), the class weights (fsk_svm_set_class_weights) and the Platt calibration
 // (fsk_svm_platt_fit, fsk_svm_calibrate, fsk_svm_get_calibration, fsk_svm_proba), the epsilon-SVR (fsk_svr_train,
 // fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get) and the one-vs-one multi-class C-SVC (fsk_svm_train_multiclass,
-// fsk_svm_multiclass_get_model, fsk_svm_multiclass_decision(_device), fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get) of
-// include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
+// fsk_svm_multiclass_get_model, fsk_svm_multiclass_decision(_device), fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get) with its
+// probabilities (fsk_svm_multiclass_calibrate, fsk_svm_multiclass_get_calibration, fsk_svm_multiclass_set_calibration,
+// fsk_svm_multiclass_proba(_device), fsk_exp_neg) of include/fastsk_amd.h. What FastSK::fit / FastSK::score do with LIBSVM on the host
 // (fastsk.cpp:239-530), for the sequences of one compute call and without the kernel matrix ever leaving the device: the
 // engine's consumer is an SVM, and the triangle it needs is 40 GB at 100,000 sequences.
 //
@@ -1021,7 +1022,7 @@ int fsk_svm_train_multiclass(fsk_engine* e, const int32_t* labels, int64_t n, do
     SvmState& S = e->svm;
     SvmMcState& M = S.mc;
     S.valid = false;  // (from here on the model slot's device state is written)
-    S.cal.valid = S.platt_valid = false;  // (the calibration belonged to the model this one replaces)
+    S.cal.valid = S.platt_valid = M.cal_valid = false;  // (the calibration belonged to the model this one replaces)
     McSolved solved;
     { int rc = mc_solve(e, M, src, probs, idx, y, eps, max_iter, &solved); if (rc) return rc; }
     { int rc = mc_upload_classes(e, M, mcl.classes); if (rc) return rc; }
@@ -1054,6 +1055,10 @@ int fsk_svm_train_multiclass(fsk_engine* e, const int32_t* labels, int64_t n, do
     M.info.n_sv = (int64_t)std::count(sv.begin(), sv.end(), (char)1);
     M.info.n_alpha = (int64_t)M.alpha.size();
     M.info.ms = now_ms() - t0;
+    M.labels.assign(labels, labels + n);  // (what fsk_svm_multiclass_calibrate solves the folds with)
+    M.w = mcl.w;
+    M.weighted = class_weight != nullptr;
+    M.C = C; M.eps = eps; M.max_iter = max_iter;
     S.model_kind = MODEL_MC;
     S.valid = true;
     return FSK_OK;
@@ -1100,9 +1105,16 @@ int fsk_svm_multiclass_decision_device(fsk_engine* e, int64_t r0, int64_t r1, do
     return FSK_OK;
 }
 
-int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
-                          const double* class_weight, double eps, int64_t max_iter) {
-    if (!e) return FSK_EINVAL;
+}  // extern "C"
+
+namespace {
+
+// What fsk_svm_multiclass_cv and fsk_svm_multiclass_calibrate share — everything but where the batch is kept and what the
+// out-of-fold launch writes: the checks, the (C, fold, pair) problems, the one batch solve. values = false: the out-of-fold
+// LABELS of every C (k_svm_ovo_decision_oof), the scores and the problems' records into M. values = true (one C): the
+// out-of-fold pair DECISIONS [n][P] (k_svm_ovo_values_oof) into *oof_values, and the form and launches into M.cv_info.
+int mc_cv_run(fsk_engine* e, SvmMcState& M, bool values, std::vector<double>* oof_values, const int32_t* labels, int64_t n, const int32_t* fold,
+              int32_t n_folds, const double* Cs, int32_t n_C, const double* class_weight, double eps, int64_t max_iter) {
     const double t0 = now_ms();
     if (n_folds < 2) return e->fail(FSK_EINVAL, "n_folds is %d: at least 2 folds", n_folds);
     if (n_C < 1) return e->fail(FSK_EINVAL, "n_C is %d: at least one value of C", n_C);  // (before the arrays: an empty Cs may be null)
@@ -1156,14 +1168,41 @@ int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const
                 pr.n = list_n[(size_t)(g % F) * P + p];
             }
 
-    SvmMcState& M = e->svm.mc_cv;
     FSK_HIP(M.d_fold.reserve(nn));
-    FSK_HIP(M.d_pred.reserve((size_t)nC * nn));
+    if (values) FSK_HIP(M.d_dec.reserve((size_t)nn * P));
+    else FSK_HIP(M.d_pred.reserve((size_t)nC * nn));
     M.valid = false;  // (from here on the earlier result's buffers are written)
+    if (values) e->svm.mc.cal_valid = false;  // (and the calibration they belonged to is gone)
     McSolved solved;
     { int rc = mc_solve(e, M, src, probs, idx, y, eps, max_iter, &solved); if (rc) return rc; }
     { int rc = mc_upload_classes(e, M, mcl.classes); if (rc) return rc; }
     FSK_HIP(hipMemcpyAsync(M.d_fold.p, fold, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    if (values) {
+        const double *diag = src.diag, *coef = M.d_coef.p, *rho = M.d_rho.p;
+        const fsk::SvmProb* dp = reinterpret_cast<const fsk::SvmProb*>(M.d_prob.p);
+        const uint32_t* di = M.d_idx.p;
+        const int32_t* df = M.d_fold.p;
+        double* out = M.d_dec.p;
+        svm_on_source(src, [=](auto* K) -> int {
+            FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_ovo_values_oof<SrcOf<decltype(K)>>), dim3((nn + 3) / 4), dim3(256), 0, e->stream, K, diag, dp, di, coef,
+                       rho, P, df, nn, out);
+            return FSK_OK;
+        });
+        oof_values->resize((size_t)nn * P);
+        FSK_HIP(hipMemcpyAsync(oof_values->data(), M.d_dec.p, oof_values->size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        FSK_HIP(hipStreamSynchronize(e->stream));
+        FSK_HIP(hipGetLastError());
+        M.cv_info = fsk_svm_cv_info{};
+        M.cv_info.n = n;
+        M.cv_info.n_folds = n_folds;
+        M.cv_info.n_C = n_C;
+        M.cv_info.form = solved.form;
+        M.cv_info.reserved0 = (int32_t)k;
+        M.cv_info.launches = solved.launches;
+        M.cv_info.ms = now_ms() - t0;
+        M.valid = true;
+        return FSK_OK;
+    }
     {
         const dim3 grid((nn + 3) / 4, nC);
         const double *diag = src.diag, *coef = M.d_coef.p, *rho = M.d_rho.p;
@@ -1221,6 +1260,163 @@ int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const
     return FSK_OK;
 }
 
+// the sigmoids of the model's pairs onto the device, for k_svm_ovo_proba
+int mc_upload_sigmoids(fsk_engine* e, SvmMcState& M) {
+    std::vector<double> A(M.P), B(M.P);
+    for (uint32_t p = 0; p < M.P; ++p) { A[p] = M.fits[p].A; B[p] = M.fits[p].B; }
+    FSK_HIP(M.d_sigA.reserve(M.P));
+    FSK_HIP(M.d_sigB.reserve(M.P));
+    FSK_HIP(hipMemcpyAsync(M.d_sigA.p, A.data(), (size_t)M.P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipMemcpyAsync(M.d_sigB.p, B.data(), (size_t)M.P * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));  // (the host vectors above are pageable)
+    return FSK_OK;
+}
+
+int mc_proba_args(fsk_engine* e, const char* call, int64_t r0, int64_t r1) {
+    int rc = model_of_kind(e, MODEL_MC, call);
+    if (rc) return rc;
+    if (!e->svm.mc.cal_valid)
+        return e->fail(FSK_ESTATE, "no calibration: call fsk_svm_multiclass_calibrate or fsk_svm_multiclass_set_calibration on the model first");
+    if (r0 < 0 || r1 > e->N || r0 > r1) return e->fail(FSK_EINVAL, "rows out of range");
+    return FSK_OK;
+}
+
+// rows [r0, r1) under the model's pairs and sigmoids into device memory: prob [r1 - r0][k], pred and iters [r1 - r0]
+static_assert(4 * (FSK_SVM_MAX_CLASSES * (FSK_SVM_MAX_CLASSES - 1) / 2) * sizeof(double) <= 64 * 1024, "k_svm_ovo_proba's LDS: four waves of P doubles");
+int mc_launch_proba(fsk_engine* e, int64_t r0, int64_t r1, double* prob, int32_t* pred, int32_t* iters) {
+    const SvmMcState& M = e->svm.mc;
+    const uint32_t blocks = (uint32_t)((r1 - r0 + 3) / 4), a = (uint32_t)r0, b = (uint32_t)r1, P = M.P, k = M.k;
+    const size_t lds = (size_t)4 * P * sizeof(double);
+    SvmSource src;
+    { int rc = svm_source(e, false, &src); if (rc) return rc; }
+    const double *diag = src.diag, *coef = M.d_coef.p, *rho = M.d_rho.p, *sA = M.d_sigA.p, *sB = M.d_sigB.p;
+    const fsk::SvmProb* probs = reinterpret_cast<const fsk::SvmProb*>(M.d_prob.p);
+    const uint32_t* idx = M.d_idx.p;
+    const int32_t* classes = M.d_classes.p;
+    return svm_on_source(src, [=](auto* K) -> int {
+        FSK_LAUNCH(HIP_KERNEL_NAME(fsk::k_svm_ovo_proba<SrcOf<decltype(K)>>), dim3(blocks), dim3(256), lds, e->stream, K, diag, probs, idx, coef, rho, sA,
+                   sB, classes, k, P, a, b, prob, pred, iters);
+        return FSK_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+double fsk_exp_neg(double x) { return fsk::exp_neg(x); }
+
+int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const int32_t* fold, int32_t n_folds, const double* Cs, int32_t n_C,
+                          const double* class_weight, double eps, int64_t max_iter) {
+    if (!e) return FSK_EINVAL;
+    return mc_cv_run(e, e->svm.mc_cv, false, nullptr, labels, n, fold, n_folds, Cs, n_C, class_weight, eps, max_iter);
+}
+
+int fsk_svm_multiclass_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds) {
+    if (!e) return FSK_EINVAL;
+    const double t0 = now_ms();
+    int rc = model_of_kind(e, MODEL_MC, "fsk_svm_multiclass_calibrate");
+    if (rc) return rc;
+    SvmMcState& M = e->svm.mc;
+    const std::vector<int32_t> labels = M.labels;  // (the model's own: what it was trained on)
+    const std::vector<double> w = M.w;
+    const double C = M.C;
+    std::vector<double> oof;
+    rc = mc_cv_run(e, e->svm.mc_cal, true, &oof, fold ? labels.data() : nullptr, (int64_t)labels.size(), fold, n_folds, &C, 1,
+                   M.weighted ? w.data() : nullptr, M.eps, M.max_iter);
+    if (rc) return rc;
+    const SvmMcState& B = e->svm.mc_cal;
+    const uint32_t k = M.k, P = M.P, nn = (uint32_t)labels.size();
+    std::vector<fsk_svm_platt_info> fits(P);
+    std::vector<double> dec;
+    std::vector<int32_t> yy;
+    for (uint32_t p = 0, a = 0; a < k; ++a)
+        for (uint32_t b = a + 1; b < k; ++b, ++p) {
+            dec.clear();
+            yy.clear();
+            for (uint32_t t = 0; t < nn; ++t)
+                if (labels[t] == M.classes[a] || labels[t] == M.classes[b]) {
+                    dec.push_back(oof[(size_t)t * P + p]);
+                    yy.push_back(labels[t] == M.classes[a] ? 1 : -1);
+                }
+            platt_fit(dec.data(), yy.data(), (int64_t)dec.size(), &fits[p]);
+            fits[p].n_folds = n_folds;
+            fits[p].form = B.cv_info.form;
+            fits[p].launches = B.cv_info.launches;
+        }
+    M.fits.swap(fits);
+    M.cal_oof.swap(oof);
+    FSK_ON_DEVICE(e);
+    rc = mc_upload_sigmoids(e, M);
+    if (rc) return rc;
+    const double ms = now_ms() - t0;
+    for (fsk_svm_platt_info& f : M.fits) f.ms = ms;
+    M.cal_valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* fits) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_proba_args(e, "fsk_svm_multiclass_get_calibration", 0, 0);
+    if (rc) return rc;
+    const SvmMcState& M = e->svm.mc;
+    if (oof && M.cal_oof.empty())
+        return e->fail(FSK_ESTATE, "no out-of-fold decisions: the sigmoids were installed by fsk_svm_multiclass_set_calibration");
+    if (oof) memcpy(oof, M.cal_oof.data(), M.cal_oof.size() * sizeof(double));
+    if (fits) memcpy(fits, M.fits.data(), M.fits.size() * sizeof(fsk_svm_platt_info));
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_set_calibration(fsk_engine* e, const double* A, const double* B) {
+    if (!e) return FSK_EINVAL;
+    int rc = model_of_kind(e, MODEL_MC, "fsk_svm_multiclass_set_calibration");
+    if (rc) return rc;
+    SvmMcState& M = e->svm.mc;
+    if (!A || !B) return e->fail(FSK_EINVAL, "null A or B");
+    for (uint32_t p = 0; p < M.P; ++p)
+        if (!std::isfinite(A[p])) return e->fail(FSK_EINVAL, "A of pair %u must be a finite number", p);
+    FSK_ON_DEVICE(e);
+    M.cal_valid = false;
+    M.fits.assign(M.P, fsk_svm_platt_info{});
+    for (uint32_t p = 0; p < M.P; ++p) { M.fits[p].A = A[p]; M.fits[p].B = B[p]; }
+    M.cal_oof.clear();
+    rc = mc_upload_sigmoids(e, M);
+    if (rc) return rc;
+    M.cal_valid = true;
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_proba(fsk_engine* e, int64_t r0, int64_t r1, double* prob, int32_t* pred, int32_t* iters) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_proba_args(e, "fsk_svm_multiclass_proba", r0, r1);
+    if (rc || r0 == r1 || (!prob && !pred && !iters)) return rc;
+    FSK_ON_DEVICE(e);
+    SvmMcState& M = e->svm.mc;
+    const size_t rows = (size_t)(r1 - r0);
+    if (prob) FSK_HIP(M.d_proba.reserve(rows * M.k));
+    if (pred) FSK_HIP(M.d_pred.reserve(rows));
+    if (iters) FSK_HIP(M.d_iters.reserve(rows));
+    rc = mc_launch_proba(e, r0, r1, prob ? M.d_proba.p : nullptr, pred ? M.d_pred.p : nullptr, iters ? M.d_iters.p : nullptr);
+    if (rc) return rc;
+    if (prob) FSK_HIP(hipMemcpyAsync(prob, M.d_proba.p, rows * M.k * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (pred) FSK_HIP(hipMemcpyAsync(pred, M.d_pred.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (iters) FSK_HIP(hipMemcpyAsync(iters, M.d_iters.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    FSK_HIP(hipGetLastError());
+    return FSK_OK;
+}
+
+int fsk_svm_multiclass_proba_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_prob, int32_t* device_pred, int32_t* device_iters) {
+    if (!e) return FSK_EINVAL;
+    int rc = mc_proba_args(e, "fsk_svm_multiclass_proba_device", r0, r1);
+    if (rc || r0 == r1 || (!device_prob && !device_pred && !device_iters)) return rc;
+    FSK_ON_DEVICE(e);
+    rc = mc_launch_proba(e, r0, r1, device_prob, device_pred, device_iters);
+    if (rc) return rc;
+    FSK_HIP(hipStreamSynchronize(e->stream));
+    return FSK_OK;
+}
+
 int fsk_svm_multiclass_cv_get(fsk_engine* e, int32_t* pred, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems, fsk_svm_cv_info* info) {
     if (!e) return FSK_EINVAL;
     int rc = mc_cv_ready(e);
@@ -1248,7 +1444,7 @@ int fsk_svm_train(fsk_engine* e, const int32_t* labels, int64_t n, double C, dou
 
     SvmState& S = e->svm;
     S.valid = false;
-    S.cal.valid = S.platt_valid = false;  // (the calibration belongs to the model)
+    S.cal.valid = S.platt_valid = S.mc.cal_valid = false;  // (the calibration belongs to the model)
     const double Cp = C * S.w_pos, Cn = C * S.w_neg;  // (each product once, one rounding)
     const uint32_t nn = (uint32_t)n;
     const int form = (int64_t)nn <= e->tune.svm_wg_max ? 1 : 2;
@@ -1445,7 +1641,7 @@ int fsk_svr_train(fsk_engine* e, const double* targets, int64_t n, double C, dou
 
     SvmState& S = e->svm;
     S.valid = false;
-    S.cal.valid = S.platt_valid = false;  // (the calibration belonged to the model this one replaces)
+    S.cal.valid = S.platt_valid = S.mc.cal_valid = false;  // (the calibration belonged to the model this one replaces)
     const uint32_t nn = (uint32_t)n, m = 2 * nn;
     const int form = (int64_t)m <= e->tune.svm_wg_max ? 1 : 2;  // (the 2n elements against the workgroup's ceiling)
     const uint32_t chunk = (uint32_t)e->tune.svm_chunk;

@@ -1,6 +1,6 @@
 // fsk_kernels_svm.h — a C-SVC dual solver and its decision values on the RESIDENT result triangle (fsk_svm_train,
-// fsk_svm_decision), the pairs' decision values and the vote of a one-vs-one multi-class model (k_svm_ovo_decision), and the same
-// solver over the twin elements of an epsilon-SVR (fsk_svr_train, fsk_svr_cv: the last section). Included by fsk_engine_svm.hip only.
+// fsk_svm_decision), the pairs' decision values and the vote of a one-vs-one multi-class model (k_svm_ovo_decision), its class
+// probabilities by pairwise coupling (k_svm_ovo_proba), and the same solver over the twin elements of an epsilon-SVR (fsk_svr_train, fsk_svr_cv: the last section). Included by fsk_engine_svm.hip only.
 //
 // The kernel is cosine-normalised: every K(t,t) is 1, the whole matrix is on the device, so the solver is SMO with LIBSVM's
 // second-order working-set selection and nothing else — no row cache, no shrinking. A row of Q is read where it lies: cells
@@ -20,6 +20,7 @@
 // reduction tree nor the grid shows in the result. Products and sums are the __d*_rn forms: no contraction.
 #pragma once
 #include "fsk_common.h"
+#include "fsk_exp_neg.h"
 
 namespace fsk {
 
@@ -622,6 +623,185 @@ __global__ __launch_bounds__(256) void k_svm_ovo_decision_oof(const SrcT* K, con
     const size_t g = (size_t)blockIdx.y * n_folds + (live ? (uint32_t)fold[t] : 0u);
     svm_ovo_row(K, diag, probs + g * P, idx_all, coef_all, rho + g * P, ab, classes, P, t, live, (double*)nullptr,
                 pred + (size_t)blockIdx.y * n_train + (live ? t : 0u));
+}
+
+// =============================================================================================
+// ONE-VS-ONE: CLASS PROBABILITIES OF ONE ROW (fsk_svm_multiclass_calibrate, fsk_svm_multiclass_proba). LIBSVM's
+// svm_predict_probability on the device: the pairs' decision values, a sigmoid a pair, and Wu, Lin and Weng's second method
+// (multiclass_probability) over the k classes, one wave a row.
+//
+// svm_ovo_pair is the inner sum of svm_ovo_row restated as a function of its own — the same operations in the same order, so
+// the same bits (the tests hold both to one restatement). svm_ovo_row keeps its own text: calling this function from it changed
+// the register allocation and the schedule of k_svm_ovo_decision (54 instead of 55 VGPRs), and that kernel is to stay what it is.
+// A wave of these kernels is alive as a whole or not at all (a dead wave returns at once), so there is no `live` here.
+template <typename SrcT>
+__device__ __forceinline__ double svm_ovo_pair(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                               const double* coef_all, const double* rho, uint32_t p, uint32_t r) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const SvmProb pr = probs[p];
+    const uint32_t* idx = idx_all + pr.idx_off;
+    const double* coef = coef_all + pr.st_off;
+    double acc = 0.0;
+    for (uint32_t q = lane; q < pr.n; q += 64u) {
+        const double c = coef[q];
+        if (c != 0.0) acc = __dadd_rn(acc, __dmul_rn(c, svm_cell(K, diag, r, idx[q])));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, d));
+    return __dsub_rn(acc, rho[p]);
+}
+
+// OUT OF FOLD, THE VALUES: dec [n_train][P], row t under the P problems of fold[t] (problems fold[t] P + p: one value of C).
+// What k_svm_ovo_decision_oof computes and does not keep; the stores are those of svm_ovo_row, 64 values at a time.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_ovo_values_oof(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                                            const double* coef_all, const double* rho, uint32_t P, const int32_t* fold,
+                                                            uint32_t n_train, double* dec) {
+    const uint32_t t = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (t >= n_train) return;  // (the whole wave)
+    const size_t g = (size_t)(uint32_t)fold[t] * P;
+    double* dec_row = dec + (size_t)t * P;
+    double keep = 0.0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const double v = svm_ovo_pair(K, diag, probs + g, idx_all, coef_all, rho + g, p, t);
+        if ((p & 63u) == lane) keep = v;
+        if (((p & 63u) == 63u || p + 1 == P) && lane <= (p & 63u)) dec_row[(p & ~63u) + lane] = keep;
+    }
+}
+
+// LIBSVM's sigmoid_predict and the clamp of svm_predict_probability: fApB = v A + B in two roundings; the exponential is
+// fsk::exp_neg, whose argument is never positive on either branch; min(max(s, 1e-7), 1 - 1e-7) with LIBSVM's own comparisons,
+// so a NaN becomes 1e-7 as it does there.
+__device__ __forceinline__ double svm_pair_prob(double v, double A, double B) {
+    const double fApB = __dadd_rn(__dmul_rn(v, A), B);
+    double s;
+    if (fApB >= 0.0) {
+        const double e = exp_neg(-fApB);
+        s = __ddiv_rn(e, __dadd_rn(1.0, e));
+    } else {
+        s = __ddiv_rn(1.0, __dadd_rn(1.0, exp_neg(fApB)));
+    }
+    constexpr double lo = 1e-7, hi = 1 - 1e-7;
+    const double x = s > lo ? s : lo;
+    return x < hi ? x : hi;
+}
+
+// the lanes of a wave meet: LDS written by one lane above is read by another below
+__device__ __forceinline__ void svm_wave_sync() {
+#ifdef FSK_EMU
+    (void)__shfl(0, 0);  // (the emulator's lanes are fibers that meet at collectives only)
+#else
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+}
+
+// rows [r0, r1) under the model's P pairs and their sigmoids (sigA, sigB [P]): prob [r1 - r0][k], pred [r1 - r0] (the class of
+// the largest probability, the lowest class among equals), iters [r1 - r0] (the coupling's iterations; 0 for k = 2); each may be
+// null. 256 threads, a wave a row, a wave a SIMD.
+// 1. The pair loop: v = dec_p(r) (svm_ovo_pair), x = svm_pair_prob(v, A_p, B_p) in every lane; r[a][b] = x is kept in the
+//    wave's OWN slice of LDS, rp[p] (8 P bytes a wave, 64,512 bytes a workgroup at 64 classes; written 64 pairs at a time),
+//    r[b][a] = 1 - x is formed where it is read (one rounding, as LIBSVM's stored value). No barrier: no wave reads another's.
+// 2. k = 2: p = (x, 1 - x). Otherwise lane t owns class t and the wave runs multiclass_probability operation for operation:
+//    Q[t][t] = sum_{j != t} r[j][t]^2 in ascending j (a register); Q[t][j] = -(r[j][t] r[t][j]) is formed from LDS where it is
+//    used (the product commutes, so Q[t][j] and Q[j][t] are one value); p = 1 / k, eps = 0.005 / k, at most max(100, k)
+//    iterations of
+//      Qp[t] = sum_j Q[t][j] p[j] in ascending j from 0.0 (p[j] by a shuffle from lane j);
+//      pQp = sum_t p[t] Qp[t] in ascending t, every lane the same scalar (the products by shuffles);
+//      max_t |Qp[t] - pQp| by xor shuffles (a maximum does not depend on the order); stop when it is < eps;
+//      for t = 0 .. k - 1 in turn: diff = (-Qp[t] + pQp) / Q[t][t], p[t] += diff,
+//        pQp = (pQp + diff (diff Q[t][t] + 2 Qp[t])) / (1 + diff) / (1 + diff), and in every lane j
+//        Qp[j] = (Qp[j] + diff Q[t][j]) / (1 + diff), p[j] /= (1 + diff).
+//    One rounding an operation, divisions by __ddiv_rn. Lanes k .. 63 take part in the shuffles and hold nothing.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void k_svm_ovo_proba(const SrcT* K, const double* diag, const SvmProb* probs, const uint32_t* idx_all,
+                                                       const double* coef_all, const double* rho, const double* sigA, const double* sigB,
+                                                       const int32_t* classes, uint32_t k, uint32_t P, uint32_t r0, uint32_t r1,
+                                                       double* prob, int32_t* pred, int32_t* iters) {
+    FSK_DYN_SHARED(double, lds);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t r = r0 + blockIdx.x * 4u + wave;
+    if (r >= r1) return;  // (the whole wave: a dead wave reads and writes nothing)
+    const size_t at = (size_t)(r - r0);
+    double* rp = lds + (size_t)wave * P;
+    double keep = 0.0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const double v = svm_ovo_pair(K, diag, probs, idx_all, coef_all, rho, p, r);
+        const double x = svm_pair_prob(v, sigA[p], sigB[p]);
+        if ((p & 63u) == lane) keep = x;
+        if (((p & 63u) == 63u || p + 1 == P) && lane <= (p & 63u)) rp[(p & ~63u) + lane] = keep;
+    }
+    svm_wave_sync();
+
+    const bool mine = lane < k;  // (this lane owns a class)
+    double pr_t = 0.0;
+    int iter = 0;
+    if (k == 2) {
+        const double x = rp[0];
+        pr_t = lane == 0 ? x : __dsub_rn(1.0, x);
+    } else {
+        // r[i][j], i != j, from the pair (min, max) at a (2k - a - 1) / 2 + (b - a - 1)
+        auto rij = [&](uint32_t i, uint32_t j) -> double {
+            const uint32_t a = i < j ? i : j, b = i < j ? j : i;
+            const double x = rp[a * (2u * k - a - 1u) / 2u + (b - a - 1u)];
+            return i < j ? x : __dsub_rn(1.0, x);
+        };
+        auto q_of = [&](uint32_t t, uint32_t j, double qtt) -> double {  // Q[t][j] seen from lane j (or t): the diagonal is qtt
+            return t == j ? qtt : -__dmul_rn(rij(j, t), rij(t, j));
+        };
+        double Qtt = 0.0;
+        if (mine)
+            for (uint32_t j = 0; j < k; ++j)
+                if (j != lane) {
+                    const double x = rij(j, lane);
+                    Qtt = __dadd_rn(Qtt, __dmul_rn(x, x));
+                }
+        const double kd = (double)k, eps = __ddiv_rn(0.005, kd);
+        const int max_iter = k > 100u ? (int)k : 100;
+        double Qp = 0.0;
+        pr_t = __ddiv_rn(1.0, kd);
+        for (; iter < max_iter; ++iter) {
+            double q = 0.0;
+            for (uint32_t j = 0; j < k; ++j) {
+                const double pj = __shfl(pr_t, (int)j);
+                if (mine) q = __dadd_rn(q, __dmul_rn(q_of(lane, j, Qtt), pj));
+            }
+            Qp = q;
+            const double prod = __dmul_rn(pr_t, Qp);
+            double pQp = 0.0;
+            for (uint32_t t = 0; t < k; ++t) pQp = __dadd_rn(pQp, __shfl(prod, (int)t));
+            double err = mine ? fabs(__dsub_rn(Qp, pQp)) : 0.0;
+            err = err > 0.0 ? err : 0.0;  // (LIBSVM's `error > max_error` from 0 never takes a NaN)
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const double o = __shfl_xor(err, d);
+                err = o > err ? o : err;
+            }
+            if (err < eps) break;
+            for (uint32_t t = 0; t < k; ++t) {
+                const double Qp_t = __shfl(Qp, (int)t), Qtt_t = __shfl(Qtt, (int)t);
+                const double diff = __ddiv_rn(__dadd_rn(-Qp_t, pQp), Qtt_t), d1 = __dadd_rn(1.0, diff);
+                if (lane == t) pr_t = __dadd_rn(pr_t, diff);
+                pQp = __ddiv_rn(__ddiv_rn(__dadd_rn(pQp, __dmul_rn(diff, __dadd_rn(__dmul_rn(diff, Qtt_t), __dmul_rn(2.0, Qp_t)))), d1), d1);
+                if (mine) {
+                    Qp = __ddiv_rn(__dadd_rn(Qp, __dmul_rn(diff, q_of(t, lane, Qtt))), d1);
+                    pr_t = __ddiv_rn(pr_t, d1);
+                }
+            }
+        }
+    }
+    if (prob && mine) prob[at * k + lane] = pr_t;
+    if (iters && lane == 0) iters[at] = iter;
+    double best_p = mine ? pr_t : -svm_inf();
+    int best = (int)lane;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double op = __shfl_xor(best_p, d);
+        const int ob = __shfl_xor(best, d);
+        if (op > best_p || (op == best_p && ob < best)) { best_p = op; best = ob; }
+    }
+    if (pred && lane == 0) pred[at] = classes[best];
 }
 
 // =============================================================================================

@@ -43,7 +43,9 @@ extern "C" {
                                   fsk_svm_get_calibration, fsk_svm_proba and fsk_svm_platt_info;
                                   fsk_svr_train, fsk_svr_get_model, fsk_svr_cv, fsk_svr_cv_get and fsk_svr_cv_score;
                                   fsk_svm_train_multiclass, fsk_svm_multiclass_get_model, fsk_svm_multiclass_decision(_device),
-                                  fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get and their two structs) */
+                                  fsk_svm_multiclass_cv, fsk_svm_multiclass_cv_get and their two structs;
+                                  fsk_svm_multiclass_calibrate, fsk_svm_multiclass_get_calibration,
+                                  fsk_svm_multiclass_set_calibration, fsk_svm_multiclass_proba(_device) and fsk_exp_neg) */
 
 enum {
     FSK_OK = 0,
@@ -690,6 +692,58 @@ int fsk_svm_multiclass_cv(fsk_engine* e, const int32_t* labels, int64_t n, const
  * may be NULL */
 int fsk_svm_multiclass_cv_get(fsk_engine* e, int32_t* pred, fsk_svm_cv_score* scores, fsk_svm_cv_problem* problems,
                               fsk_svm_cv_info* info);
+
+/* ---- class probabilities of the multi-class model: a Platt sigmoid a pair and pairwise coupling on the device — what
+ * LIBSVM's svm_parameter.probability = 1 gives (svm_binary_svc_probability, sigmoid_train, svm_predict_probability with
+ * multiclass_probability, Wu, Lin and Weng's second method).
+ *
+ * fsk_svm_multiclass_calibrate: needs the model of fsk_svm_train_multiclass (FSK_ESTATE naming the model otherwise). fold[t],
+ * t < n_train, in 0..n_folds-1 as for fsk_svm_calibrate. Problem f P + p is pair p on the rows of its two classes with
+ * fold[t] != f, in ascending row order, with the model's boxes C w[a], C w[b], its eps, max_iter and kernel kind; all n_folds P
+ * problems are solved in one batch (fsk_svm_multiclass_cv with the model's one C; its limits and refusals apply, FSK_EINVAL
+ * with its messages: a fold id out of range, a fold without rows, n_folds < 2, a fold whose training rows lack a class — naming
+ * class and fold). Then oof[t P + p] is the decision value of row t under problem fold[t] P + p, summed as
+ * fsk_svm_multiclass_decision sums, and for every pair fsk_svm_platt_fit runs on the oof values of the rows of classes a and
+ * b, ascending, label +1 for class a: A[p], B[p].
+ * NOT LIBSVM'S FOLDS AND ORDER: LIBSVM shuffles each pair's rows on its own (rand()) into 5 folds and solves each fold's
+ * sub-problem grouped by class. Here the folds are ONE assignment over all rows, given by the caller (a stratified draw in the
+ * Python layer), and the sub-problems are in ascending row order, as the fit's are. A and B therefore equal this project's
+ * restatement bit for bit and LIBSVM's only statistically.
+ * The calibration belongs to the model: a later fsk_svm_train_multiclass, fsk_svm_train or fsk_svr_train drops it, and so does
+ * whatever drops the model; a refused call leaves the earlier one. A stored fsk_svm_multiclass_cv result is neither needed nor
+ * touched.
+ * fsk_svm_multiclass_get_calibration: oof[n_train P] and fits[P] (A, B, iterations, status of every pair; n_folds, form,
+ * launches and ms of the whole call in each); either may be NULL. After fsk_svm_multiclass_set_calibration there are no
+ * out-of-fold values: asking for oof is FSK_ESTATE, the fits hold A and B alone.
+ * fsk_svm_multiclass_set_calibration: installs the P sigmoids A[p], B[p] on the model without a solve (a saved calibration put
+ * back). FSK_EINVAL where an A is not finite; B is not checked.
+ *
+ * fsk_svm_multiclass_proba: for rows r0 <= r < r1 <= N, one launch (k_svm_ovo_proba): the pairs' decision values v_p as above;
+ * LIBSVM's sigmoid_predict with fApB = v_p A[p] + B[p] (two roundings): e / (1 + e), e = fsk_exp_neg(-fApB), where fApB >= 0,
+ * else 1 / (1 + fsk_exp_neg(fApB)); clamped as LIBSVM clamps, (x > 1e-7 ? x : 1e-7) then (y < 1 - 1e-7 ? y : 1 - 1e-7), so a NaN
+ * becomes 1e-7; r[a][b] that value, r[b][a] = 1 - r[a][b]. k = 2: prob = (r[0][1], r[1][0]), iters = 0. Otherwise
+ * multiclass_probability operation for operation, one rounding each: Q[t][t] = sum_{j != t} r[j][t]^2 in ascending j,
+ * Q[t][j] = -(r[j][t] r[t][j]), p = 1 / k, eps = 0.005 / k, at most max(100, k) iterations, each: Qp[t] = sum_j Q[t][j] p[j]
+ * and pQp = sum_t p[t] Qp[t] in ascending order from 0.0; stop when max_t |Qp[t] - pQp| < eps; else for t = 0 .. k - 1 in turn
+ * diff = (-Qp[t] + pQp) / Q[t][t], p[t] += diff, pQp = (pQp + diff (diff Q[t][t] + 2 Qp[t])) / (1 + diff) / (1 + diff), and
+ * for all j Qp[j] = (Qp[j] + diff Q[t][j]) / (1 + diff), p[j] /= (1 + diff).
+ * prob[(r - r0) k + c] is the probability of classes[c]; pred[r - r0] the label of the largest (the lowest class among equals:
+ * LIBSVM's svm_predict_probability label, which need not be the vote's); iters[r - r0] the iterations taken. Each output may
+ * be NULL. The _device form writes DEVICE memory of the caller. FSK_ESTATE before a calibration ("no calibration: ...") and,
+ * naming the model, on a C-SVC or an SVR model; FSK_EINVAL for rows out of range.
+ * fsk_svm_calibrate, fsk_svm_get_calibration and fsk_svm_proba stay the binary model's and keep refusing this one.
+ *
+ * fsk_exp_neg: exp(x) for x <= 0 as a fixed sequence of IEEE double operations, the same bits on the host and on the device:
+ * NaN -> NaN; x < -708 -> 0.0 (no subnormal is formed); else n = floor(x (1 / ln 2) + 0.5), r = (x - n ln2_hi) - n ln2_lo
+ * (Cody and Waite), the Taylor polynomial of degree 13 in r by Horner, times 2^n. Within 2 ulp of a correctly rounded exp on
+ * [-708, 0] (measured: 1). x > 0 is not supported. Host only, no device needed. */
+int fsk_svm_multiclass_calibrate(fsk_engine* e, const int32_t* fold, int32_t n_folds);
+int fsk_svm_multiclass_get_calibration(fsk_engine* e, double* oof, fsk_svm_platt_info* fits);
+int fsk_svm_multiclass_set_calibration(fsk_engine* e, const double* A, const double* B);
+int fsk_svm_multiclass_proba(fsk_engine* e, int64_t r0, int64_t r1, double* prob, int32_t* pred, int32_t* iters);
+int fsk_svm_multiclass_proba_device(fsk_engine* e, int64_t r0, int64_t r1, double* device_prob, int32_t* device_pred,
+                                    int32_t* device_iters);
+double fsk_exp_neg(double x);
 
 /* ---- helpers shared with the host side --------------------------------------------------- */
 int64_t fsk_num_combos(int32_t g, int32_t m);                              /* nchoosek */
