@@ -1,5 +1,5 @@
-// fsk_bytesel.h — the byte-select add, the half-select xor and the first-use point of LDS reads of the packed shift corrections
-// (k_dense_shift_packed, fsk_kernels_dense_shift.h).
+// fsk_bytesel.h — the byte-select add, the half-select xor, the first-use point of LDS reads and the LDS-only barrier of the
+// packed shift corrections (k_dense_shift_packed, fsk_kernels_dense_shift.h).
 //
 // acc + byte B of `packed` is ONE v_add_u32_sdwa on gfx950 (src0_sel:BYTE_B); written in C++ hipcc emits v_bfe_u32 + v_add3_u32
 // for two cells, one and a half instructions a cell in a kernel that is bound by the VALU instructions it issues.
@@ -58,6 +58,19 @@ __device__ __forceinline__ uint32_t xor_word(uint32_t packed, uint32_t x) {
 __device__ __forceinline__ void first_use(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e, uint32_t& f, uint32_t& g, uint32_t& h) {
 #ifndef FSK_EMU
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : : "memory");
+#endif
+}
+
+// A workgroup barrier that orders LDS accesses only: s_waitcnt lgkmcnt(0) + s_barrier, and no wait on the vector-memory
+// counter. __syncthreads() is a workgroup fence as well and drains vmcnt, which ends a direct-to-LDS load that is meant to stay
+// in flight across the barrier (the ahead schedule of k_dense_shift_packed). Everything the waves exchange through LDS by
+// ds_read / ds_write / ds_add is ordered by it; what a direct-to-LDS load lands is NOT: that needs fsk_hw::wait_panel_rows()
+// in front of a barrier.
+__device__ __forceinline__ void barrier_lds_only() {
+#ifdef FSK_EMU
+    __syncthreads();
+#else
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
 }
 

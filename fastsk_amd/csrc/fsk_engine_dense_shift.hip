@@ -18,7 +18,8 @@
 //                      one launch does not run (dense_shift_one_launch = -1, the shift path forced below 16384 tiles, a plan
 //                      whose group was cut at by_overflow slots)
 //   k_dense_keymajor   the count panels once more per counted list as key-major planes (a dword = one key of 8 sequences)
-//   k_dense_shift_packed  the derived steps from those planes, eight cells an LDS read (tuning dense_shift_packed)
+//   k_dense_shift_packed  the derived steps from those planes, eight cells an LDS read (tuning dense_shift_packed); by default
+//                      by the ahead schedule (tuning dense_shift_ahead), which reads dense_shift_chain_table's chain table
 //   k_dense_shift_fix  the derived steps from the count panels themselves: dense_shift_packed = -1, and whenever the key-major
 //                      planes do not fit
 //
@@ -147,18 +148,51 @@ static void dense_shift_unpack_flags(std::vector<uint32_t>& steps, uint32_t n_ba
     if (n_steps > 0) steps[2 * n_steps - 1] |= 256u;
 }
 
+// The chain table of the ahead schedule (k_dense_shift_packed<true, true>), from the uploaded copy of the step table: two words
+// a chain that has steps, {the first step's slot word, steps | first weight << 8 | the steps' unpack flags << 16}. The kernel
+// makes every further step's slots and weight from them, which holds for the tables dense_shift_plan writes — a chain's upper
+// slots are consecutive, a step's lower slot is the upper of the step before, the weights fall by one — and is checked here
+// step by step: a table of another make returns empty, and the parent's schedule runs. Like the flags, a schedule and not
+// part of the plan.
+static std::vector<uint32_t> dense_shift_chain_table(const std::vector<uint32_t>& steps, uint32_t n_bases) {
+    std::vector<uint32_t> t;
+    const size_t n_steps = steps.size() / 2;
+    size_t s = 0;
+    while (s < n_steps) {
+        const uint32_t sl0 = steps[2 * s], up0 = sl0 >> 16, wt0 = steps[2 * s + 1] & 255u;
+        if ((sl0 & 0xffffu) >= n_bases) return {};
+        uint32_t len = 0, flags = 0;
+        for (; s + len < n_steps && (len == 0 || (steps[2 * (s + len)] & 0xffffu) >= n_bases); ++len) {
+            const uint32_t sl = steps[2 * (s + len)], wt = steps[2 * (s + len) + 1];
+            if (len > 0 && sl != ((up0 + len) << 16 | (up0 + len - 1u))) return {};
+            if (len >= 8 || wt0 < len || (wt & 255u) != wt0 - len || up0 + len > 0xffffu) return {};
+            flags |= ((wt >> 8) & 1u) << len;
+        }
+        t.push_back(sl0);
+        t.push_back(len | wt0 << 8 | flags << 16);
+        s += len;
+    }
+    return t;
+}
+
 // the plan's tables on the device, and the edge keys of the list just counted (chunk_pos: its kept positions in slot order)
 int dense_shift_edge_keys(fsk_engine* e, const uint8_t* chunk_pos, uint32_t panels_pad) {
     ShiftPlan& p = e->shift;
     const uint32_t n_steps = (uint32_t)(p.steps.size() / 2), np_seq = panels_pad * fsk::PANEL;
     std::vector<uint32_t> steps = p.steps;
     dense_shift_unpack_flags(steps, p.n_bases, e->tune.dense_shift_batch != 0);
-    FSK_HIP(e->d_shift_steps.reserve(p.steps.size() + p.group_steps.size()));  // the step table, the one launch's group table behind it
+    const std::vector<uint32_t> chain_tab = dense_shift_chain_table(steps, p.n_bases);
+    // the step table, the one launch's group table behind it, the ahead schedule's chain table behind that
+    FSK_HIP(e->d_shift_steps.reserve(p.steps.size() + p.group_steps.size() + chain_tab.size()));
     FSK_HIP(e->d_edge_keys.reserve((size_t)n_steps * np_seq));
     FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p, steps.data(), steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     if (!p.group_steps.empty())
         FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p + p.steps.size(), p.group_steps.data(), p.group_steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                e->stream));
+    if (!chain_tab.empty())
+        FSK_HIP(hipMemcpyAsync(e->d_shift_steps.p + p.steps.size() + p.group_steps.size(), chain_tab.data(), chain_tab.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, e->stream));
+    e->ld.shift_chains = (uint32_t)(chain_tab.size() / 2);
     FSK_LAUNCH(fsk::k_dense_edge_keys, dim3(panels_pad, (n_steps + 3u) / 4u), dim3(256), 0, e->stream, e->view(), e->cfg.g, e->k, e->sigma, chunk_pos,
                (const uint32_t*)e->d_shift_steps.p, n_steps, np_seq, e->d_edge_keys.p);
     FSK_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors are pageable memory)
@@ -235,10 +269,15 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
         }
     }
     if (e->ld.shift_packed) {
-        const auto k_packed = e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true> : fsk::k_dense_shift_packed<false>;
+        // the ahead schedule (tuning dense_shift_ahead) is a schedule of the in-place form and needs the chain table
+        const bool ahead = e->tune.dense_shift_inplace != 0 && e->tune.dense_shift_ahead != 0 && e->ld.shift_chains > 0;
+        const auto k_packed = ahead ? fsk::k_dense_shift_packed<true, true>
+                                    : e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true, false> : fsk::k_dense_shift_packed<false, false>;
+        // (ahead: the chain table in the step table's place, its chains in n_bases' — the kernel makes the steps from them)
         FSK_LAUNCH(k_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
-                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),
-                   (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, p.n_bases, (uint32_t)(30u * p.wsum), (uint32_t)e->N, K);
+                   (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p,
+                   (const uint32_t*)e->d_shift_steps.p + (ahead ? p.steps.size() + p.group_steps.size() : 0), (uint32_t)(p.steps.size() / 2),
+                   (const uint32_t*)e->d_edge_offs.p, panels_pad * fsk::PANEL, nb, Vq8, ahead ? e->ld.shift_chains : p.n_bases, (uint32_t)(30u * p.wsum), (uint32_t)e->N, K);
     } else {
         FSK_LAUNCH(fsk::k_dense_shift_fix, dim3((uint32_t)n_tiles), dim3(512), 0, e->stream, (const uint32_t*)e->d_C4.p, (const uint32_t*)e->d_C4H.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p, (const uint32_t*)e->d_shift_steps.p, (uint32_t)(p.steps.size() / 2),

@@ -292,13 +292,49 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 // planes is below 16. A barrier ends the lookups, the next ends the updates. A chain's first step, a flagged step and the step
 // behind a flagged one (whose buffer the hi planes took) are staged as before; the planes in memory are never written. The step
 // table runs three steps ahead and the masks two, so that a step knows at its head whether the next one is flagged.
-template <bool INPLACE>
+//
+// AHEAD (tuning dense_shift_ahead, the default; a schedule of the in-place form): vmcnt retires in order, so a stage stays in
+// flight only as long as NO younger vector load is waited for — and above every step loads its offsets, its table words and its
+// masks, and ends in vmcnt(0). Here a step inside a chain issues no vector memory load at all, and the chain's first step stages
+// the NEXT chain's start under the whole chain. The host hands over a chain table in place of the step table (`steps`; its
+// length in `n_bases`: fsk_engine_dense_shift.hip, dense_shift_chain_table), two words a chain, from which every step's slot
+// word, weight, unpack flag and masks follow; 64 descriptors sit in a VGPR pair, one chain a lane, and are read with v_readlane.
+// LDS: the two 32 KB stage buffers and, behind them, a ring of two 8 KB halves of key offsets (8 steps x 256 positions): 80 KB,
+// two workgroups a CU. At a chain's first step, in this order: the next chain's row masks (one word a lane, lane 4 r + x), then
+// its first planes into the buffer the chain does not use (it is made in place in the other), then the offsets of all its steps
+// into the ring half the chain does not read — wave w lands the 1 KB of steps w and w + 4. Inside the chain the lane's 16 offsets
+// are four ds_read_b128 of the chain's ring half (eight lanes share an address) and the update's offset one ds_read_b32, one
+// step ahead as before; the first offsets of a chain are read behind its predecessor's last barrier.
+//
+// What orders the prefetch (D = any LDS location a direct-to-LDS load of the prefetch writes: the idle buffer, the idle ring half):
+//   - the overwrite of D after its last read: D was last read by the lookups (the buffer), the offset reads and the update's read
+//     (the ring half) of the PREVIOUS chain, all in front of that chain's closing __syncthreads(); the loads are issued behind it.
+//   - every read of D after the load: the chain's LAST step ends in fsk_hw::wait_panel_rows() — vmcnt(0): this wave's loads have
+//     landed, with the mask words, which are older — and __syncthreads(): every wave's have. The next chain's first lookups, its
+//     first ring reads and the ballot over the masks all follow that barrier. A chain of one step has its first step for its last:
+//     the prefetch has one step of cover, as every stage had before.
+//   - the barriers in between — the end of a step that is not the chain's last, and the one behind the in-place update — are
+//     fsk_hw::barrier_lds_only(): lgkmcnt(0) and s_barrier, no fence. They order the lookups, the ds_add updates and the ring reads
+//     of the CURRENT buffer and ring half, which no load in flight writes; __syncthreads() there would drain vmcnt and with it
+//     the prefetch.
+//   - a flagged step: the hi pass stages over the buffer just used and the step behind it is staged into the OTHER buffer, over
+//     the prefetch, as before (`lost`: nothing is prefetched when the chain's second step is staged already). A wave waits for
+//     its own part of the prefetch (vmcnt(0)) before it issues the replacement — the same wave writes the same 1 KB pieces, so
+//     the replacement lands last — and that step, like every staged step, ends in vmcnt(0) + __syncthreads(). While `lost` is set
+//     the chain's last step stages the next chain's start at its head, under its lookups: the schedule above. The ring is not
+//     touched by any of this and is always prefetched.
+// Every compiler-visible load (descriptors at every 64th chain, masks once a chain) is issued in front of the prefetch and first
+// used, through a v_mov the compiler cannot see through, behind the chain's closing wait.
+template <bool INPLACE, bool AHEAD = false>
 __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* KM, const uint32_t* KMH, const uint32_t* rowmask, const uint32_t* tile_tab,
                                                                const uint32_t* steps, uint32_t n_steps, const uint32_t* offs, uint32_t np_seq,
                                                                int n_slots, uint32_t Vq8, uint32_t n_bases, uint32_t bias, uint32_t N, u64* K) {
+    static_assert(INPLACE || !AHEAD, "the ahead schedule is a schedule of the in-place form");
     constexpr uint32_t SIDE = 256u * 16u;  // dwords of one staged plane (256 keys at most on this path)
     constexpr uint32_t PBUF = 2u * SIDE;   // dwords per stage buffer: A B
-    __shared__ __attribute__((aligned(1024))) uint32_t P[2 * PBUF];
+    constexpr uint32_t RING = 8u * 256u;   // (ahead) dwords of one half of the offsets ring: 8 steps x 256 positions
+    // (ahead: the two stage buffers and the two ring halves, 80 KB of static LDS; gfx950 has 160 KB a CU)
+    __shared__ __attribute__((aligned(1024))) uint32_t P[AHEAD ? 2 * PBUF + 2 * RING : 2 * PBUF];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     // (the two masks in registers the compiler cannot see through, one of them scalar: see above)
@@ -352,19 +388,90 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
 
     // (the step table runs two steps ahead and the masks one, both loaded at the END of a step and landed by its barrier)
     // (wt is the whole weight word: bits 0..7 the weight, bit 8 "unpack after this step")
-    uint32_t sl = steps[0], wt = steps[1], fl = flagged(sl);
-    uint32_t sn = n_steps > 1u ? steps[2] : 0u, wn = n_steps > 1u ? steps[3] : 0u;
+    uint32_t sl, wt, fl, sn = 0u, wn = 0u;
     uint32_t s2 = 0u, w2 = 0u, fl_nx = 0u;  // (in place: the table entry of step s + 2 and the masks of step s + 1, at the head of step s)
-    if constexpr (INPLACE) {
-        if (n_steps > 2u) { s2 = steps[4]; w2 = steps[5]; }
-        if (n_steps > 1u) fl_nx = flagged(sn);
-    }
     uint4 oR_n[2], oC_n[2];
-    load_offs(0u, oR_n, oC_n);
     uint32_t buf = 0;
-    load_stage(KM, 0u, sl);
-    fsk_hw::wait_panel_rows();
-    __syncthreads();
+    // ---- the ahead schedule's state and loads (see the head comment). `steps` is the CHAIN table here and n_bases the number of
+    // its chains: chain c has the descriptor (the first step's slot word, steps | first weight << 8 | unpack flags << 16), its
+    // step r the slots (up0 + r) << 16 | (up0 + r - 1) and the weight wt0 - r (the host checks that the step table says so). A
+    // step's words are kept by increments — a shift, an add — because the kernel is bound by what it issues.
+    [[maybe_unused]] uint32_t* const ring = P + 2u * PBUF;
+    [[maybe_unused]] uint32_t cb = 0u, dv0 = 0u, dv1 = 0u;    // the descriptors of chains cb .. cb + 63, one a lane
+    [[maybe_unused]] uint32_t c = 0u, r = 0u, rem = 0u;       // the chain, the step inside it, the steps it still has (this one included)
+    [[maybe_unused]] uint32_t n0 = 0u, n1 = 0u, mk_n = 0u;    // the next chain's descriptor and row masks (lane 4 r + x: step r, A0 A1 B0 B1)
+    [[maybe_unused]] uint32_t flw = 0u, wu = 0u, slq = 0u;    // nibble q: step r + q is flagged; bit q: step r + q unpacks; the slot word of step r + 1
+    [[maybe_unused]] uint32_t half = 0u, rg = 0u;             // the chain's ring half, the dword of this step's offsets in the ring
+    [[maybe_unused]] bool lost = false;                       // the other buffer does not (or will not) hold the next chain's first planes
+    // chain (e0, e1) becomes the current one: its first step's words
+    [[maybe_unused]] auto enter_chain = [&](uint32_t e0, uint32_t e1, uint32_t mk) {
+        flw = (uint32_t)__ballot(fsk_hw::vgpr_copy(mk) != 0u);
+        sl = e0;
+        slq = ((e0 >> 16) + 1u) << 16 | (e0 >> 16);
+        rem = e1 & 15u;
+        wt = (e1 >> 8) & 255u;
+        wu = e1 >> 16;
+        r = 0u;
+        rg = half * RING;
+    };
+    [[maybe_unused]] auto load_desc = [&]() {
+        const uint32_t q = cb + lane < n_bases ? cb + lane : n_bases - 1u;
+        dv0 = steps[2u * q];
+        dv1 = steps[2u * q + 1u];
+    };
+    [[maybe_unused]] auto load_masks = [&](uint32_t e0, uint32_t e1) {
+        const uint32_t mr = lane >> 2, x = lane & 3u, up0 = e0 >> 16;
+        uint32_t m = 0u;
+        if (mr < (e1 & 15u)) {
+            const uint32_t slot = x < 2u ? up0 + mr : (mr == 0u ? (e0 & 0xffffu) : up0 + mr - 1u);
+            m = rowmask[(size_t)((x < 2u ? ti : tj) * 2u + (x & 1u)) * n_slots + slot];
+        }
+        return m;
+    };
+    // a chain's key offsets into a ring half: wave w lands the 1 KB of steps w and w + 4 (the row side's 128 positions, then the
+    // column side's)
+    [[maybe_unused]] auto load_ring = [&](uint32_t hf, uint32_t s_first, uint32_t n) {
+        const uint32_t ring_lane = lane < 32u ? (ti * TILE + 4u * lane) * 4u : (tj * TILE + 4u * (lane - 32u)) * 4u;
+#pragma unroll
+        for (uint32_t q = 0; q < 2u; ++q) {
+            const uint32_t rr = w + 4u * q;
+            if (rr < n)
+                fsk_hw::panel_rows_to_lds(offs + (size_t)(s_first + rr) * np_seq, np_seq * 4u, fsk_hw::lds_address(ring) + (hf * RING + rr * 256u) * 4u,
+                                          ring_lane);
+        }
+    };
+    // a step's offsets of this lane's 8 rows and 8 columns from the ring, `at` = the step's dword there (eight lanes share an address)
+    [[maybe_unused]] auto ring_offs = [&](uint32_t at, uint4 (&oR)[2], uint4 (&oC)[2]) {
+        const uint32_t* q = ring + at;
+#pragma unroll
+        for (uint32_t hh = 0; hh < 2u; ++hh) {
+            oR[hh] = *reinterpret_cast<const uint4*>(q + hh * PANEL + 4u * tr);
+            oC[hh] = *reinterpret_cast<const uint4*>(q + TILE + hh * PANEL + 4u * tc);
+        }
+    };
+    if constexpr (AHEAD) {
+        load_desc();
+        const uint32_t d0 = fsk_hw::readlane(dv0, 0u), d1 = fsk_hw::readlane(dv1, 0u);
+        const uint32_t mk = load_masks(d0, d1);
+        load_stage(KM, 0u, d0);
+        load_ring(0u, 0u, d1 & 15u);
+        fsk_hw::wait_panel_rows();
+        __syncthreads();
+        fl = 0u;
+        enter_chain(d0, d1, mk);
+        ring_offs(0u, oR_n, oC_n);
+    } else {
+        sl = steps[0]; wt = steps[1]; fl = flagged(sl);
+        sn = n_steps > 1u ? steps[2] : 0u; wn = n_steps > 1u ? steps[3] : 0u;
+        if constexpr (INPLACE) {
+            if (n_steps > 2u) { s2 = steps[4]; w2 = steps[5]; }
+            if (n_steps > 1u) fl_nx = flagged(sn);
+        }
+        load_offs(0u, oR_n, oC_n);
+        load_stage(KM, 0u, sl);
+        fsk_hw::wait_panel_rows();
+        __syncthreads();
+    }
     for (uint32_t s = 0; s < n_steps; ++s) {
         uint32_t oR[8], oC[8];
 #pragma unroll
@@ -375,15 +482,55 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
             oC[4 * h + 2] = fsk_hw::vgpr_copy(oC_n[h].z); oC[4 * h + 3] = fsk_hw::vgpr_copy(oC_n[h].w);
         }
         // the next step's planes are made from this step's: it continues the chain, and neither step has a count above 15
-        const bool same = INPLACE && s + 1u < n_steps && (sn & 0xffffu) >= n_bases && fl == 0u && fl_nx == 0u;
+        bool same;
         uint32_t uo_n = 0u;
-        if (s + 1u < n_steps) {
-            load_offs(s + 1u, oR_n, oC_n);
-            // (thread q < 128: row-side position q, the keys of step s + 1; thread 128 + q: column-side position q, the keys of step s)
-            if (same) uo_n = offs[(size_t)(w < 2u ? s + 1u : s) * np_seq + (w < 2u ? ti : tj) * TILE + (tid & 127u)];
-            else load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
+        [[maybe_unused]] bool last = false;
+        if constexpr (AHEAD) {
+            // (wt: the weight in bits 0..7; bit 8, "unpack after this step", joins it here)
+            const bool first = r == 0u, has_next = c + 1u < n_bases;
+            last = rem == 1u;
+            if (first) {
+                lost = false;
+                if (has_next) {  // the next chain's descriptor and masks: issued before its stage, retired with it at this chain's end
+                    if (c + 1u - cb >= 64u) {
+                        cb = c;
+                        load_desc();
+                    }
+                    n0 = fsk_hw::readlane(dv0, c + 1u - cb);
+                    n1 = fsk_hw::readlane(dv1, c + 1u - cb);
+                    mk_n = load_masks(n0, n1);
+                }
+            }
+            fl = flw & 15u;
+            wt = (wt & 255u) | (wu & 1u) << 8;
+            same = !last && (flw & 255u) == 0u;  // (the masks past the chain's end are zero)
+            if (first && has_next) {  // the next chain's first planes into the idle buffer, its offsets into the idle ring half
+                if (last || same) load_stage(KM, buf ^ 1u, n0);
+                else lost = true;  // (step 1 is about to be staged there)
+                load_ring(half ^ 1u, s + rem, n1 & 15u);
+            }
+            if (!last) {
+                ring_offs(rg + 256u, oR_n, oC_n);
+                if (same) {  // (thread q < 128: row-side position q, the keys of step r + 1; thread 128 + q: column-side position q, step r)
+                    uo_n = ring[rg + (w < 2u ? 256u : (uint32_t)TILE) + (tid & 127u)];
+                } else {  // a flagged step, or the step behind one: staged as before, over the prefetch
+                    lost = true;
+                    if (!first) fsk_hw::wait_panel_rows();  // (this wave's part of the prefetch has landed before its replacement is issued)
+                    load_stage(KM, buf ^ 1u, slq);
+                }
+            } else if (lost && has_next) {
+                load_stage(KM, buf ^ 1u, n0);  // the prefetch was lost: the next chain's start the old way, under this step's lookups
+            }
+        } else {
+            same = INPLACE && s + 1u < n_steps && (sn & 0xffffu) >= n_bases && fl == 0u && fl_nx == 0u;
+            if (s + 1u < n_steps) {
+                load_offs(s + 1u, oR_n, oC_n);
+                // (thread q < 128: row-side position q, the keys of step s + 1; thread 128 + q: column-side position q, the keys of step s)
+                if (same) uo_n = offs[(size_t)(w < 2u ? s + 1u : s) * np_seq + (w < 2u ? ti : tj) * TILE + (tid & 127u)];
+                else load_stage(KM, buf ^ 1u, sn);  // in flight under the lookups
+            }
         }
-        if ((sl & 0xffffu) < n_bases) {  // a new chain: the prefix sums restart
+        if (AHEAD ? r == 0u : (sl & 0xffffu) < n_bases) {  // a new chain: the prefix sums restart
 #pragma unroll
             for (int a = 0; a < 8; ++a) Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
         }
@@ -457,43 +604,76 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
                 }
             }
         }
-        uint32_t fl_n = 0u, sl_n2 = 0u, wt_n2 = 0u;
-        if constexpr (INPLACE) {  // the masks of step s + 2, the table entry of step s + 3
-            if (s + 2u < n_steps) {
-                fl_n = flagged(s2);
-                if (s + 3u < n_steps) {
-                    sl_n2 = steps[2u * (s + 3u)];
-                    wt_n2 = steps[2u * (s + 3u) + 1u];
+        if constexpr (AHEAD) {
+            if (last) {
+                fsk_hw::wait_panel_rows();  // the prefetch — planes, offsets, masks, descriptors — has landed
+                __syncthreads();            // ... everyone's has, and everyone is done with this chain's buffer and ring half
+                buf ^= 1u;
+                if (c + 1u < n_bases) {
+                    half ^= 1u;
+                    enter_chain(n0, n1, mk_n);
+                    ring_offs(rg, oR_n, oC_n);
+                }
+                ++c;
+            } else {
+                if (same) {
+                    fsk_hw::barrier_lds_only();  // everyone is done with the lookups; the prefetch stays in flight
+                    const uint32_t uo = fsk_hw::vgpr_copy(uo_n), od = uo & 0xffffu, os = uo >> 16;
+                    if (od != os) {
+                        const uint32_t p = tid & 127u, t4 = p & 0x3cu, e = (p >> 6) * 4u + (p & 3u);
+                        const uint32_t base = buf * PBUF + (w >> 1) * SIDE, inc = 1u << (4u * e);
+                        atomicAdd(&P[base + ((os ^ t4) >> 2)], inc);
+                        atomicAdd(&P[base + ((od ^ t4) >> 2)], 0u - inc);
+                    }
+                    fsk_hw::barrier_lds_only();  // the planes of step r + 1 are whole
+                } else {
+                    fsk_hw::wait_panel_rows();
+                    __syncthreads();
+                    buf ^= 1u;
+                }
+                sl = slq; slq += 0x10001u;
+                --rem; --wt; wu >>= 1; flw >>= 4;
+                ++r; rg += 256u;
+            }
+        } else {
+            uint32_t fl_n = 0u, sl_n2 = 0u, wt_n2 = 0u;
+            if constexpr (INPLACE) {  // the masks of step s + 2, the table entry of step s + 3
+                if (s + 2u < n_steps) {
+                    fl_n = flagged(s2);
+                    if (s + 3u < n_steps) {
+                        sl_n2 = steps[2u * (s + 3u)];
+                        wt_n2 = steps[2u * (s + 3u) + 1u];
+                    }
+                }
+            } else if (s + 1u < n_steps) {
+                fl_n = flagged(sn);
+                if (s + 2u < n_steps) {
+                    sl_n2 = steps[2u * (s + 2u)];
+                    wt_n2 = steps[2u * (s + 2u) + 1u];
                 }
             }
-        } else if (s + 1u < n_steps) {
-            fl_n = flagged(sn);
-            if (s + 2u < n_steps) {
-                sl_n2 = steps[2u * (s + 2u)];
-                wt_n2 = steps[2u * (s + 2u) + 1u];
+            fsk_hw::wait_panel_rows();  // this wave's part of the next stage has landed (and every load of this trip)
+            __syncthreads();            // ... everyone's has, and everyone is done with the current buffer
+            if (same) {  // A: c_up(s) -> c_up(s + 1), B: c_lo(s) -> c_up(s): one nibble up and one down a position, where the keys differ
+                const uint32_t uo = fsk_hw::vgpr_copy(uo_n), od = uo & 0xffffu, os = uo >> 16;
+                if (od != os) {
+                    const uint32_t p = tid & 127u, t4 = p & 0x3cu, e = (p >> 6) * 4u + (p & 3u);
+                    const uint32_t base = buf * PBUF + (w >> 1) * SIDE, inc = 1u << (4u * e);
+                    atomicAdd(&P[base + ((os ^ t4) >> 2)], inc);
+                    atomicAdd(&P[base + ((od ^ t4) >> 2)], 0u - inc);
+                }
+                __syncthreads();  // the planes of step s + 1 are whole
+            } else {
+                buf ^= 1u;
             }
-        }
-        fsk_hw::wait_panel_rows();  // this wave's part of the next stage has landed (and every load of this trip)
-        __syncthreads();            // ... everyone's has, and everyone is done with the current buffer
-        if (same) {  // A: c_up(s) -> c_up(s + 1), B: c_lo(s) -> c_up(s): one nibble up and one down a position, where the keys differ
-            const uint32_t uo = fsk_hw::vgpr_copy(uo_n), od = uo & 0xffffu, os = uo >> 16;
-            if (od != os) {
-                const uint32_t p = tid & 127u, t4 = p & 0x3cu, e = (p >> 6) * 4u + (p & 3u);
-                const uint32_t base = buf * PBUF + (w >> 1) * SIDE, inc = 1u << (4u * e);
-                atomicAdd(&P[base + ((os ^ t4) >> 2)], inc);
-                atomicAdd(&P[base + ((od ^ t4) >> 2)], 0u - inc);
+            if constexpr (INPLACE) {
+                sl = sn; wt = wn; fl = fl_nx;
+                sn = s2; wn = w2; fl_nx = fl_n;
+                s2 = sl_n2; w2 = wt_n2;
+            } else {
+                sl = sn; wt = wn; fl = fl_n;
+                sn = sl_n2; wn = wt_n2;
             }
-            __syncthreads();  // the planes of step s + 1 are whole
-        } else {
-            buf ^= 1u;
-        }
-        if constexpr (INPLACE) {
-            sl = sn; wt = wn; fl = fl_nx;
-            sn = s2; wn = w2; fl_nx = fl_n;
-            s2 = sl_n2; w2 = wt_n2;
-        } else {
-            sl = sn; wt = wn; fl = fl_n;
-            sn = sl_n2; wn = wt_n2;
         }
     }
 #pragma unroll
