@@ -271,8 +271,14 @@ int dense_shift_tiles(fsk_engine* e, u64 n_tiles, int nb, uint32_t Vq8, uint32_t
     if (e->ld.shift_packed) {
         // the ahead schedule (tuning dense_shift_ahead) is a schedule of the in-place form and needs the chain table
         const bool ahead = e->tune.dense_shift_inplace != 0 && e->tune.dense_shift_ahead != 0 && e->ld.shift_chains > 0;
-        const auto k_packed = ahead ? fsk::k_dense_shift_packed<true, true>
-                                    : e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true, false> : fsk::k_dense_shift_packed<false, false>;
+        // the straight chains (tuning dense_shift_straight) are a form of the ahead schedule's step loop
+        const bool straight = ahead && e->tune.dense_shift_straight != 0;
+        const auto k_packed = straight ? fsk::k_dense_shift_packed<true, true, true>
+                              : ahead  ? fsk::k_dense_shift_packed<true, true, false>
+                                       : e->tune.dense_shift_inplace != 0 ? fsk::k_dense_shift_packed<true, false, false> : fsk::k_dense_shift_packed<false, false, false>;
+        if (e->trace())
+            fprintf(stderr, "[fsk] dense shift classes: the corrections by k_dense_shift_packed<%s>\n",
+                    straight ? "true, true, true" : ahead ? "true, true, false" : e->tune.dense_shift_inplace != 0 ? "true, false, false" : "false, false, false");
         // (ahead: the chain table in the step table's place, its chains in n_bases' — the kernel makes the steps from them)
         FSK_LAUNCH(k_packed, dim3((uint32_t)n_tiles), dim3(256), 0, e->stream, (const uint32_t*)e->d_KM.p, (const uint32_t*)e->d_KMH.p,
                    (const uint32_t*)e->d_rowmask.p, (const uint32_t*)e->d_tiletab.p,

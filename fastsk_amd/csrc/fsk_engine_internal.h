@@ -145,6 +145,7 @@ using fsk_detail::Event;
     X(dense_shift_inplace, 1, 0, 1, "dense, shift classes: k_dense_shift_packed stages a chain's first planes and makes every further step's in LDS, one nibble up and one down a sequence (a step that meets a count above 15 in its tile, and the step behind it, are staged) — 0 = every step staged") \
     X(dense_shift_batch, 1, 0, 1, "dense, shift classes: k_dense_shift_packed adds the prefix sums of several steps byte to byte and hands the bytes to its int32 sums once a batch, where the step table says so (a step at chain position r counts 30 (r + 1) against a byte's 255; a batch may span chains) — 0 = after every step") \
     X(dense_shift_ahead, 1, 0, 1, "dense, shift classes: k_dense_shift_packed stages the NEXT chain's first planes and key offsets at a chain's first step, into the idle stage buffer and an offsets ring in LDS (80 KB a workgroup), and issues no vector memory load inside a chain (a chain that meets a count above 15 in its tile stages as before) — 0 = every chain start staged one step ahead; ignored with dense_shift_inplace = 0 and on the k_dense_shift_fix path") \
+    X(dense_shift_straight, 1, 0, 1, "dense, shift classes: the ahead schedule of k_dense_shift_packed runs a chain none of whose steps meets a count above 15 in its tile as a straight loop (lookups; barrier, update, barrier) that carries a step counter, the ring position and the unpack bits, and every other chain by the step loop of dense_shift_ahead — 0 = every chain by that step loop; ignored wherever dense_shift_ahead is ignored") \
     X(dense_shift_one_launch, 0, -1, 1, "dense, shift classes: every chain-length group of the base products in ONE launch that flushes at the group ends without clearing (k_dense_tile_shift_all) — 1 = whenever the shift path runs, -1 = never: one k_dense_tile_shift launch a group (0: where the shift path runs by its own default rule, tile_splits = 0 and 16384 tiles or more)") \
     X(dense_shift_plane_kb, 0, 0, (int64_t)1 << 40, "dense, shift classes: the key-major planes and offsets may take this many KiB at most (0: half of the free memory; tests: the planes do not fit)") \
     X(dense_chunk, 0, 0, 1 << 24, "dense: cap of the count kernel's staging chunk, in windows (0: none)")                             \

@@ -325,11 +325,32 @@ __global__ __launch_bounds__(256) void k_dense_edge_offs(const uint16_t* keys, s
 //     touched by any of this and is always prefetched.
 // Every compiler-visible load (descriptors at every 64th chain, masks once a chain) is issued in front of the prefetch and first
 // used, through a v_mov the compiler cannot see through, behind the chain's closing wait.
-template <bool INPLACE, bool AHEAD = false>
+//
+// STRAIGHT (tuning dense_shift_straight, the default; a form of the ahead schedule's loop): the loop runs over CHAINS, and what a
+// chain needs is decided once, at its head, from the ballot over its masks. A chain none of whose steps meets a count above 15 on
+// either side of the tile — all but about 2 % of the (tile, chain) pairs of random DNA — is: the prefetch; then per step the ring
+// reads of the next step, the lookups, the unpack on bit 0 of the chain's unpack bits; between steps barrier_lds_only, the two
+// ds_add, barrier_lds_only; the closing wait. It carries the steps left, the ring position and the unpack bits, and neither slot
+// words nor a weight nor flags nor the first / middle / last ladder of the step loop. Any other chain runs that loop's body step by
+// step around the SAME lookup block (one in the kernel: a form with the clean chains in a loop of their own beside the step loop
+// held two and spilled 157 VGPRs). In this loop the next step's offsets are read from the ring INTO the registers of this step's,
+// right behind the step's last lookup is issued (behind the hi pass where a step has one, which looks up again): the step loop's
+// second set of 16 offset registers and its 16 v_mov a step are gone, and the read is a barrier pair ahead of its first use.
+// What orders the prefetch across clean -> flagged -> clean:
+//   - both kinds issue it at the chain's head, behind the previous chain's closing __syncthreads(), into the buffer and the ring
+//     half that chain read last; both end in wait_panel_rows() + __syncthreads() and read what it landed behind them. Inside a
+//     clean chain no barrier drains vmcnt and nothing is staged, so the first two points above hold as they stand.
+//   - a flagged chain may stage over the prefetched buffer; `lost` is that chain's own — cleared at every chain's head — and under
+//     it the chain's last step stages the next start before the same closing wait. Whichever way they came, `buf` holds a chain's
+//     first planes at its head, which is all the next chain, clean or not, relies on. The ring half is never staged over.
+//   - a chain whose first step is flagged stages its second step at the head, in the prefetch's place, behind a wait for the
+//     ring loads just issued (the step loop skips that wait at a first step; here the step inside the chain is not kept).
+template <bool INPLACE, bool AHEAD = false, bool STRAIGHT = false>
 __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* KM, const uint32_t* KMH, const uint32_t* rowmask, const uint32_t* tile_tab,
                                                                const uint32_t* steps, uint32_t n_steps, const uint32_t* offs, uint32_t np_seq,
                                                                int n_slots, uint32_t Vq8, uint32_t n_bases, uint32_t bias, uint32_t N, u64* K) {
     static_assert(INPLACE || !AHEAD, "the ahead schedule is a schedule of the in-place form");
+    static_assert(AHEAD || !STRAIGHT, "the straight chains are a form of the ahead schedule's loop");
     constexpr uint32_t SIDE = 256u * 16u;  // dwords of one staged plane (256 keys at most on this path)
     constexpr uint32_t PBUF = 2u * SIDE;   // dwords per stage buffer: A B
     constexpr uint32_t RING = 8u * 256u;   // (ahead) dwords of one half of the offsets ring: 8 steps x 256 positions
@@ -472,7 +493,198 @@ __global__ __launch_bounds__(256, 2) void k_dense_shift_packed(const uint32_t* K
         fsk_hw::wait_panel_rows();
         __syncthreads();
     }
-    for (uint32_t s = 0; s < n_steps; ++s) {
+    if constexpr (STRAIGHT) {
+        // The loop over CHAINS. At a chain's head — enter_chain done, the first offsets read, `buf` holding its first planes
+        // whichever way they came — the chain is clean (flw == 0: no step of it meets a count above 15 on either side of this
+        // tile; 98 % of the (tile, chain) pairs of random DNA) or it is not, and that is decided once:
+        //   head   the next chain's descriptor, masks, first planes and ring half, in the order above (the step loop's
+        //          `first && has_next` block; in a clean chain `last || same` is known);
+        //   body   a clean chain: the lookups with the ring reads of the next step behind the last of them, the unpack on bit 0 of wu, and
+        //          between steps barrier_lds_only - the two ds_add - barrier_lds_only. It carries rem, rg and wu and nothing else: no slot
+        //          words, no weight (the weights are prefix sums), no flags, no first / middle / last ladder;
+        //          any other chain: the step loop's body below, step by step, in what it does (a staged step, the hi pass, `lost`,
+        //          the late stage of the next start), around the same lookup block;
+        //   tail   wait_panel_rows() + __syncthreads(), the buffer and the ring half change, the next chain is entered.
+        // Both kinds issue the prefetch behind the previous chain's closing barrier and first read what it landed behind their
+        // own closing wait and barrier, so the ordering argument above holds across clean -> flagged -> clean as it stands:
+        // a clean chain leaves `buf ^ 1` and `half ^ 1` prefetched, a flagged one leaves `buf ^ 1` staged by its last step where
+        // the prefetch was lost, and neither reads `lost` of the other: it is cleared at every chain's head.
+        uint32_t s = 0u;  // the first step of the NEXT chain, from the chain's head on
+        uint32_t xA = tr * 4u, xB = (tc * 4u) | (SIDE * 4u);  // (buf = 0; a staged plane's base is a multiple of 16 KB and a key offset has 14 bits)
+        uint32_t oR[8], oC[8], dA[8], sA[8], dB[8], sB[8];
+        auto read_A = [&](int e) { dA[e] = lds_at(fsk_hw::xor_word<0>(oC[e], xA)); sA[e] = lds_at(fsk_hw::xor_word<1>(oC[e], xA)); };
+        auto read_B = [&](int e) { dB[e] = lds_at(fsk_hw::xor_word<0>(oR[e], xB)); sB[e] = lds_at(fsk_hw::xor_word<1>(oR[e], xB)); };
+        auto row_term = [&](int e) {
+            Rr[0][e] += (sA[e] & M4) + (~dA[e] & M4);
+            Rr[1][e] += ((sA[e] >> 4) & M4) + (~(dA[e] >> 4) & M4);
+            Qr[0][e] += Rr[0][e];
+            Qr[1][e] += Rr[1][e];
+        };
+        auto col_term = [&](int e) {
+            Rc[0][e] += (sB[e] & M4) + (~dB[e] & M4);
+            Rc[1][e] += ((sB[e] >> 4) & M4) + (~(dB[e] >> 4) & M4);
+            Qc[0][e] += Rc[0][e];
+            Qc[1][e] += Rc[1][e];
+        };
+        // load_masks by arithmetic on lane constants (the slot of lane 4 r + x is up0 + r for A, up0 + r - 1 for B and the chain's
+        // base slot for B at r = 0): written with selects, the lane conditions are hoisted in front of the loop as wave masks, two
+        // SGPRs each, and the loop spills one
+        const uint32_t mk_r = lane >> 2, mk_x = lane & 3u;
+        const size_t mk_row = (size_t)((mk_x < 2u ? ti : tj) * 2u + (mk_x & 1u)) * n_slots;
+        const uint32_t mk_add = mk_r - (mk_x >> 1), mk_base = fsk_hw::vgpr_copy(mk_x >= 2u && mk_r == 0u ? 1u : 0u);
+        auto next_masks = [&](uint32_t e0, uint32_t e1) {
+            const uint32_t up0 = e0 >> 16, slot = up0 + mk_add + mk_base * ((e0 & 0xffffu) + 1u - up0);
+            uint32_t m = 0u;
+            if (mk_r < (e1 & 15u)) m = rowmask[mk_row + slot];
+            return m;
+        };
+        // a step's offsets from the ring into oR / oC (ring_offs without the registers of a step ahead)
+        auto next_offs = [&](uint32_t at) {
+            const uint32_t* q = ring + at;
+#pragma unroll
+            for (uint32_t hh = 0; hh < 2u; ++hh) {
+                const uint4 a = *reinterpret_cast<const uint4*>(q + hh * PANEL + 4u * tr), b = *reinterpret_cast<const uint4*>(q + TILE + hh * PANEL + 4u * tc);
+                oR[4 * hh] = a.x; oR[4 * hh + 1] = a.y; oR[4 * hh + 2] = a.z; oR[4 * hh + 3] = a.w;
+                oC[4 * hh] = b.x; oC[4 * hh + 1] = b.y; oC[4 * hh + 2] = b.z; oC[4 * hh + 3] = b.w;
+            }
+        };
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {  // (the first chain's first offsets were read above)
+            oR[4 * h] = oR_n[h].x; oR[4 * h + 1] = oR_n[h].y; oR[4 * h + 2] = oR_n[h].z; oR[4 * h + 3] = oR_n[h].w;
+            oC[4 * h] = oC_n[h].x; oC[4 * h + 1] = oC_n[h].y; oC[4 * h + 2] = oC_n[h].z; oC[4 * h + 3] = oC_n[h].w;
+        }
+        while (c < n_bases) {
+            const uint32_t gen = flw;  // != 0: some step of the chain meets a count above 15 in this tile
+            lost = false;
+            if (c + 1u < n_bases) {
+                if (c + 1u - cb >= 64u) {
+                    cb = c;
+                    load_desc();
+                }
+                n0 = fsk_hw::readlane(dv0, c + 1u - cb);
+                n1 = fsk_hw::readlane(dv1, c + 1u - cb);
+                mk_n = next_masks(n0, n1);
+                s += rem;  // the next chain's first step
+                if (rem == 1u || (flw & 255u) == 0u) load_stage(KM, buf ^ 1u, n0);
+                else lost = true;  // (step 1 is about to be staged there)
+                load_ring(half ^ 1u, s, n1 & 15u);
+            }
+#pragma unroll
+            for (int a = 0; a < 8; ++a) Rr[0][a] = Rr[1][a] = Rc[0][a] = Rc[1][a] = 0u;
+            for (;;) {
+                const bool last = rem == 1u;
+                bool in_place = true;  // the next step's planes are made from this step's
+                uint32_t uo_n = 0u;
+                bool hi = false;  // the step meets a count above 15: the hi pass
+                if (gen == 0u) {
+                    if (!last) uo_n = ring[rg + (w < 2u ? 256u : (uint32_t)TILE) + (tid & 127u)];
+                } else {
+                    hi = (flw & 15u) != 0u;
+                    in_place = (flw & 255u) == 0u;
+                    if (!last) {
+                        if (in_place) {
+                            uo_n = ring[rg + (w < 2u ? 256u : (uint32_t)TILE) + (tid & 127u)];
+                        } else {  // a flagged step, or the step behind one: staged, over the prefetch
+                            lost = true;
+                            fsk_hw::wait_panel_rows();  // (this wave's part of the prefetch has landed before its replacement is issued)
+                            load_stage(KM, buf ^ 1u, ((sl >> 16) + 1u) << 16 | (sl >> 16));  // (the slot word of step r + 1)
+                        }
+                    } else if (lost && c + 1u < n_bases) {
+                        load_stage(KM, buf ^ 1u, n0);  // the prefetch was lost: the next chain's start the old way, under this step's lookups
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) read_A(e);
+                fsk_hw::first_use(dA[0], sA[0], dA[1], sA[1], dA[2], sA[2], dA[3], sA[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) read_B(e);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) row_term(e);
+                fsk_hw::first_use(dA[4], sA[4], dA[5], sA[5], dA[6], sA[6], dA[7], sA[7]);
+#pragma unroll
+                for (int e = 4; e < 8; ++e) read_B(e);
+                // the step's last lookup is issued: the next step's offsets land in the registers this step's leave (no copy a step;
+                // a step with a hi pass looks up once more and reads them behind it)
+                if (!last && !hi) next_offs(rg + 256u);
+#pragma unroll
+                for (int e = 4; e < 8; ++e) row_term(e);
+                fsk_hw::first_use(dB[0], sB[0], dB[1], sB[1], dB[2], sB[2], dB[3], sB[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) col_term(e);
+                fsk_hw::first_use(dB[4], sB[4], dB[5], sB[5], dB[6], sB[6], dB[7], sB[7]);
+#pragma unroll
+                for (int e = 4; e < 8; ++e) col_term(e);
+                if ((wu & 1u) != 0u) {  // the batch ends behind this step: every byte of Q joins its int32 sum, and Q starts again
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        acc[0][e] = fsk_hw::add_byte<0>(acc[0][e], Qr[0][e]); acc[1][e] = fsk_hw::add_byte<0>(acc[1][e], Qr[1][e]);
+                        acc[2][e] = fsk_hw::add_byte<1>(acc[2][e], Qr[0][e]); acc[3][e] = fsk_hw::add_byte<1>(acc[3][e], Qr[1][e]);
+                        acc[4][e] = fsk_hw::add_byte<2>(acc[4][e], Qr[0][e]); acc[5][e] = fsk_hw::add_byte<2>(acc[5][e], Qr[1][e]);
+                        acc[6][e] = fsk_hw::add_byte<3>(acc[6][e], Qr[0][e]); acc[7][e] = fsk_hw::add_byte<3>(acc[7][e], Qr[1][e]);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        acc[e][0] = fsk_hw::add_byte<0>(acc[e][0], Qc[0][e]); acc[e][1] = fsk_hw::add_byte<0>(acc[e][1], Qc[1][e]);
+                        acc[e][2] = fsk_hw::add_byte<1>(acc[e][2], Qc[0][e]); acc[e][3] = fsk_hw::add_byte<1>(acc[e][3], Qc[1][e]);
+                        acc[e][4] = fsk_hw::add_byte<2>(acc[e][4], Qc[0][e]); acc[e][5] = fsk_hw::add_byte<2>(acc[e][5], Qc[1][e]);
+                        acc[e][6] = fsk_hw::add_byte<3>(acc[e][6], Qc[0][e]); acc[e][7] = fsk_hw::add_byte<3>(acc[e][7], Qc[1][e]);
+                        Qr[0][e] = Qr[1][e] = Qc[0][e] = Qc[1][e] = 0u;
+                    }
+                }
+                if (hi) {  // (a flagged chain only) the hi planes over the buffer just used, at 16 x the weight
+                    __syncthreads();  // everyone is done with the lo planes
+                    load_stage(KMH, buf, sl);
+                    fsk_hw::wait_panel_rows();
+                    __syncthreads();
+                    const uint32_t mul = 16u * wt;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        read_A(e);
+                        read_B(e);
+#pragma unroll
+                        for (int n = 0; n < 8; ++n) {
+                            acc[n][e] += (((sA[e] >> (4 * n)) & 15u) - ((dA[e] >> (4 * n)) & 15u)) * mul;
+                            acc[e][n] += (((sB[e] >> (4 * n)) & 15u) - ((dB[e] >> (4 * n)) & 15u)) * mul;
+                        }
+                    }
+                    if (!last) next_offs(rg + 256u);
+                }
+                if (last) break;
+                if (in_place) {
+                    fsk_hw::barrier_lds_only();  // everyone is done with the lookups; the prefetch stays in flight
+                    const uint32_t uo = fsk_hw::vgpr_copy(uo_n), od = uo & 0xffffu, os = uo >> 16;
+                    if (od != os) {
+                        const uint32_t p = tid & 127u, t4 = p & 0x3cu, e = (p >> 6) * 4u + (p & 3u);
+                        const uint32_t base = buf * PBUF + (w >> 1) * SIDE, inc = 1u << (4u * e);
+                        atomicAdd(&P[base + ((os ^ t4) >> 2)], inc);
+                        atomicAdd(&P[base + ((od ^ t4) >> 2)], 0u - inc);
+                    }
+                    fsk_hw::barrier_lds_only();  // the planes of the next step are whole
+                } else {
+                    fsk_hw::wait_panel_rows();
+                    __syncthreads();
+                    buf ^= 1u;
+                    xA ^= PBUF * 4u; xB ^= PBUF * 4u;
+                }
+                if (gen != 0u) {  // (the words a clean chain never reads)
+                    sl = ((sl >> 16) + 1u) << 16 | (sl >> 16);
+                    --wt; flw >>= 4;
+                }
+                --rem; wu >>= 1; rg += 256u;
+            }
+            fsk_hw::wait_panel_rows();  // the prefetch — planes, offsets, masks, descriptors — has landed
+            __syncthreads();            // ... everyone's has, and everyone is done with this chain's buffer and ring half
+            buf ^= 1u;
+            xA ^= PBUF * 4u; xB ^= PBUF * 4u;
+            if (c + 1u < n_bases) {
+                half ^= 1u;
+                enter_chain(n0, n1, mk_n);
+                next_offs(rg);
+            }
+            ++c;
+        }
+    }
+    for (uint32_t s = 0; !STRAIGHT && s < n_steps; ++s) {  // the loop over STEPS (every form but the straight one)
         uint32_t oR[8], oC[8];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
